@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — queries/sec of the dense-retrieval hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--dim D] [--batch B] [--k K]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--dim D] [--batch B] [--k K] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself (a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...`,
@@ -13,7 +13,10 @@ prep_queries (L2-normalise + fp16/int8 copies) -> fused MFMA scan + pruning -> c
 sort -> [N>1: pack, ONE RCCL all-gather of (id, score), merge].  The corpus is FIXED (strong
 scaling): `--rows` rows of dimension `--dim`, N(0,1) directions, row-sharded over the N ranks.  Default
 workload = BASELINE.json config 4's corpus (100M x 768 fp16) when it fits the ranks' HBM, otherwise the
-largest power-of-ten row count that does.  The same line also carries, as objects of their own:
+largest power-of-ten row count that does.  A plain run measures that and nothing else: set-up, W warm-up steps, K timed
+steps (every scan launch bracketed by HIP events: `roofline`), the line.  `--dump-outputs DIR` writes the last timed step's
+answer (ids, scores) as .npy files.  With `--full` the line also carries the HBM ceiling measured on the box
+(`peak_measured`), the full-size exactness check of the headline shard (`config.full_size_check`) and, as objects of their own:
   c2  config 2 (1M x 768, one GPU)                                   [N = 1]
   c3  config 3 end to end: c2 + the cross-encoder's LM forward on 256 x 100 prompts + score->order + RRF   [N = 1]
   c5  config 5 end to end: bge-large encoder forward (24 layers, seeded weights) -> fp8 100M x 1024
@@ -140,8 +143,8 @@ def parse(argv=None):
     ap.add_argument("--no-ingest", action="store_true", help="skip the ingest leg (texts -> tokeniser -> encoder -> stored rows)")
     ap.add_argument("--ingest-docs", type=int, default=0, help="documents per ingest configuration (0 = sized for ~1-2 s each)")
     ap.add_argument("--verify-queries", type=int, default=256,
-                    help="queries whose answer is re-checked by an exact canonical re-scan of the whole shard (eight queries "
-                         "per pass over the rows: the default checks the whole batch, ~2 s at 100M rows)")
+                    help="with --full: queries whose answer is re-checked by an exact canonical re-scan of the whole shard "
+                         "(eight queries per pass over the rows: the default checks the whole batch, ~2 s at 100M rows)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="collective backend of the ranks: nccl (= RCCL, the measured configuration) or gloo (rehearsals)")
     ap.add_argument("--one-device", action="store_true",
@@ -150,6 +153,15 @@ def parse(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the multi-rank plumbing (gloo): shard ranges, the (id, score) all-gather, the "
                          "merge and the max-over-ranks timing, with a stand-in local search; no GPU, no kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the measured HBM ceiling, the full-size exactness check and "
+                         "every other leg (c2, c3, c5, cpu_baseline, api, wide, pairs, f32, persistence, ingest; each "
+                         "still switched off by its --no-* option).  Without it a run sets up, warms up, times --steps "
+                         "headline steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the headline path returned in its last step to DIR/ids.npy "
+                         "(float64) and DIR/scores.npy (float32), [batch][k] each (rank 0: the merged answer); above 64 MB "
+                         "in all, a fixed seeded sample of the queries (DIR/query_rows.npy names them)")
     return ap.parse_args(argv)
 
 
@@ -343,6 +355,54 @@ def timed_loop(torch, dist, step_begin, step_end, steps, warmup, use_dist):
     return dt, last
 
 
+def full_size_check(torch, dist, np, idx, q, a, d_pad, dev, world, use_dist):
+    """Full-size exactness property on this rank's shard (--full): the exact repair scan (canonical fp32 scores of EVERY row)
+    must find no row beating the returned k-th entry (local results, before the cross-shard merge); and, on fp16 rows, the
+    fp16-MFMA scan path (a different kernel with a different bound) must return the same ids."""
+    l_ids, l_sc = idx.search_device(q, a.k)
+    nver = max(0, min(a.verify_queries, a.batch))
+    vq = sorted(set(np.linspace(0, a.batch - 1, nver).astype(int).tolist())) if nver else []
+    beat = idx.verify_batch(q, l_ids, l_sc, vq) if vq else 0
+    check = {"queries_verified_by_exact_rescan": len(vq), "rows_beating_kth": int(beat)}
+    if a.storage == "f16" and not a.shadow and d_pad <= 768 and idx._use_q8(a.k):
+        idx.scan = "mfma16"
+        m_ids, m_sc = idx.search_device(q, a.k)
+        idx.scan = a.scan
+        check["queries_cross_checked_vs_fp16_mfma_scan"] = a.batch
+        check["queries_differing"] = int((~((m_ids == l_ids).all(dim=1) & (m_sc == l_sc).all(dim=1))).sum().item())
+    if use_dist:   # every rank's own shard check, summed
+        t = torch.tensor([check["rows_beating_kth"], check.get("queries_differing", 0)], dtype=torch.int64, device=dev)
+        dist.all_reduce(t)
+        check["rows_beating_kth"] = int(t[0].item())
+        if "queries_differing" in check:
+            check["queries_differing"] = int(t[1].item())
+        check["ranks_checked"] = world
+    return check
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(torch, np, out_dir, ids, scores, limit=DUMP_LIMIT_BYTES, seed=20240917):
+    """--dump-outputs: an answer (ids, scores [nq][k]) as out_dir/ids.npy (float64: ids below 2^53 are exact) and
+    out_dir/scores.npy (float32), for two builds to be compared file by file.  When the two would pass `limit` bytes, a fixed
+    sample of the queries (seeded, so the same for every run of the same shape; ascending) is written instead: those rows of
+    both arrays, and their query numbers as out_dir/query_rows.npy (float64)."""
+    nq, k = ids.shape
+    arrays = {}
+    if nq * k * 12 > limit:
+        m = max(1, (limit - 4096) // (k * 12 + 8))      # (4 KiB: the three .npy headers)
+        pick = np.sort(np.random.default_rng(seed).choice(nq, m, replace=False))
+        sel = torch.as_tensor(pick, dtype=torch.int64, device=ids.device)
+        ids, scores = ids.index_select(0, sel), scores.index_select(0, sel)
+        arrays["query_rows"] = pick.astype(np.float64)
+    arrays["ids"] = ids.double().cpu().numpy()
+    arrays["scores"] = scores.float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+
+
 def scan_profile(lib, B, ctypes, fn, max_launches):
     """Run fn() with the library's HIP-event brackets around every scan launch; returns (result, total ms, launches)."""
     B.check(lib.rarc_profile_begin(max_launches), "rarc_profile_begin")
@@ -430,7 +490,8 @@ def main():
     from rag_arc_amd.hip.sharded import ShardedFlatSearch, shard_range, split_range
 
     lib = B.load_library()
-    measure_hbm_peak(torch, lib, B, dev)      # (every rank: their work stays symmetric; HBM_MEASURED feeds every hbm roofline below)
+    if a.full:      # (every rank: their work stays symmetric; HBM_MEASURED feeds every hbm roofline below)
+        measure_hbm_peak(torch, lib, B, dev)
     d_pad = B.padded_dim(a.dim, 256 if a.storage == "f8" else 128)
     esize = 1 if a.storage == "f8" else 2               # bytes per element the SCAN streams (fp32 rows: their fp16 image)
     held = 6 if a.storage == "f32" else esize            # bytes per element the index holds in HBM
@@ -474,6 +535,8 @@ def main():
         8 * a.steps * passes_per_step + 16)
     exch_ms = searcher.exchange_ms() / max(1, a.steps)
     searcher.measure_exchange(False)
+    if a.dump_outputs and rank == 0:     # the last timed step's answer, copied out before anything else searches
+        dump_outputs(torch, np, a.dump_outputs, ids, scores)
     scan_ms = tot_ms / max(1, n_l)
     # algorithmic bytes of one scan launch on this rank (shadow mode: the scan reads the int8 image).  A large
     # shard is scanned in up to four launches of the same kernel (stretches ending at 1/512, 1/64, 1/8 of the shard
@@ -483,27 +546,7 @@ def main():
     launches_per_pass = max(1, round(n_l / max(1, passes)))
     shard_bytes = (hi - lo) * d_pad * (1 if a.shadow else esize) / launches_per_pass
     flagged = len(getattr(idx, "last_repaired", []))
-    # full-size exactness property on this rank's shard: the exact repair scan (canonical fp32 scores of EVERY row)
-    # must find no row beating the returned k-th entry (local results, before the cross-shard merge); and, on fp16
-    # rows, the fp16-MFMA scan path (a different kernel with a different bound) must return the same ids
-    l_ids, l_sc = idx.search_device(q, a.k)
-    nver = max(0, min(a.verify_queries, a.batch))
-    vq = sorted(set(np.linspace(0, a.batch - 1, nver).astype(int).tolist())) if nver else []
-    beat = idx.verify_batch(q, l_ids, l_sc, vq) if vq else 0
-    check = {"queries_verified_by_exact_rescan": len(vq), "rows_beating_kth": int(beat)}
-    if a.storage == "f16" and not a.shadow and d_pad <= 768 and idx._use_q8(a.k):
-        idx.scan = "mfma16"
-        m_ids, m_sc = idx.search_device(q, a.k)
-        idx.scan = a.scan
-        check["queries_cross_checked_vs_fp16_mfma_scan"] = a.batch
-        check["queries_differing"] = int((~((m_ids == l_ids).all(dim=1) & (m_sc == l_sc).all(dim=1))).sum().item())
-    if use_dist:   # every rank's own shard check, summed
-        t = torch.tensor([check["rows_beating_kth"], check.get("queries_differing", 0)], dtype=torch.int64, device=dev)
-        dist.all_reduce(t)
-        check["rows_beating_kth"] = int(t[0].item())
-        if "queries_differing" in check:
-            check["queries_differing"] = int(t[1].item())
-        check["ranks_checked"] = world
+    check = full_size_check(torch, dist, np, idx, q, a, d_pad, dev, world, use_dist) if a.full else None
 
     result = None
     kname = "rarc_scan_q8_kernel" if idx._use_q8(a.k) else "rarc_scan_f16_kernel"
@@ -530,15 +573,16 @@ def main():
                        "exchange_ms_per_step": round(exch_ms, 4) if use_dist else 0.0,
                        "exchange": (f"pack + one {'RCCL' if a.backend == 'nccl' else a.backend} all-gather of (id, score) + merge") if use_dist else "none (one shard)",
                        "repaired_queries_last_step": flagged,
-                       "full_size_check": check},
+                       "full_size_check": check},      # (None: checked under --full only)
             "roofline": hbm_roofline(ach, traffic=traffic, traffic_source=tsrc, kernel=kname, avg_launch_ms=round(scan_ms, 4),
                                      algorithmic_bytes_per_launch=int(shard_bytes), launches_timed=n_l,
                                      launches_per_scan=launches_per_pass, scan_ms_per_pass=round(scan_ms * launches_per_pass, 4),
                                      hbm_measured=dict(HBM_MEASURED)),
+            "cpu_baseline": None,        # (the host oracle's figure: --full)
         }
 
     # ---- config 2 / 3 (1M x 768, one GPU) and the CPU baseline on the same sample -----------------
-    if world == 1 and a.storage == "f16" and not (a.no_c2 and a.no_c3):
+    if a.full and world == 1 and a.storage == "f16" and not (a.no_c2 and a.no_c3):
         n2 = min(1_000_000, rows)
         idx2 = idx if rows == n2 else build_index(torch, lib, B, FlatIndexF16, local_rank, a.dim, 0, n2)
         steps2 = max(a.steps, 400)      # (0.45 ms each: a fifth of a second; short runs of this leg vary by 5 % with the clocks the
@@ -575,17 +619,17 @@ def main():
             del idx2
 
     # ---- rows wider than 1024 dimensions: 10M x 1536 through the wide path (one GPU) ----------------------
-    if world == 1 and a.storage == "f16" and not a.no_wide:
+    if a.full and world == 1 and a.storage == "f16" and not a.no_wide:
         if torch.cuda.mem_get_info(dev)[0] > 45 * (1 << 30):
             result["wide"] = leg_wide(torch, lib, B, FlatIndexF16, a, dev, local_rank)
         else:
             result["wide"] = {"skipped": "needs 45 GiB of free HBM"}
     # ---- all pairs with cosine >= 0.95 among 100k entity embeddings (the graph store's dedup step), one GPU --------
-    if world == 1 and a.storage == "f16" and not a.no_pairs:
+    if a.full and world == 1 and a.storage == "f16" and not a.no_pairs:
         result["pairs"] = leg_pairs(torch, np, lib, B, a, dev)
     # ---- config 5 end to end (every N): encoder forward -> fp8 sharded scan -> RRF ----------------
-    if not a.no_c5 and a.storage == "f16":
-        del searcher, idx, l_ids, l_sc
+    if a.full and not a.no_c5 and a.storage == "f16":
+        del searcher, idx
         import gc
 
         gc.collect()
@@ -596,10 +640,10 @@ def main():
             result["c5"] = c5
     # ---- storage="f32": the reference's own row format AT THE SCALE ONE GPU HOLDS (one GPU; after the headline index and
     #      config 5's corpus are gone): fp32 rows + their fp16 image = 6 bytes per element — 45M x 768 = 207 GB of the 288 ----
-    if world == 1 and a.storage == "f16" and not a.no_f32:
+    if a.full and world == 1 and a.storage == "f16" and not a.no_f32:
         import gc
 
-        searcher = idx = l_ids = l_sc = None
+        searcher = idx = None
         gc.collect()
         torch.cuda.empty_cache()
         free = torch.cuda.mem_get_info(dev)[0]
@@ -611,14 +655,14 @@ def main():
             result["f32"] = {"skipped": f"{rows_f32} fp32 rows need {rows_f32 * per_row >> 30} GiB of HBM, {free >> 30} GiB free"}
         torch.cuda.empty_cache()
     # ---- shard files: a 10M x dim fp16 shard streamed HBM -> file -> HBM by the library, one GPU --------------
-    if world == 1 and not a.no_persist and a.storage == "f16":
+    if a.full and world == 1 and not a.no_persist and a.storage == "f16":
         torch.cuda.empty_cache()
         try:
             result["persistence"] = leg_persist(torch, lib, B, FlatIndexF16, a, local_rank)
         except OSError as exc:      # (no room for the file: the leg reports why instead of failing the bench)
             result["persistence"] = {"skipped": str(exc)}
     # ---- ingest: texts -> host WordPiece -> encoder -> normalise / quantise / append, one GPU ----------
-    if world == 1 and not a.no_ingest and a.storage == "f16":
+    if a.full and world == 1 and not a.no_ingest and a.storage == "f16":
         torch.cuda.empty_cache()
         result["ingest"] = leg_ingest(torch, np, a, dev, local_rank)
     if rank == 0:

@@ -69,3 +69,31 @@ def test_a_measured_line_has_the_same_contract_keys_as_the_dry_run():
     assert 'result["cpu_baseline"]' in main
     for key in ("rows_per_gpu", "exchange_ms_per_step", "n_corpus"):
         assert f'"{key}":' in block, key
+
+
+
+def test_full_and_dump_outputs_are_opt_in_and_reach_the_ranks(monkeypatch):
+    """A plain run is the headline alone: --full and --dump-outputs are off unless asked for.  `--gpus N` hands both on to
+    the N ranks it starts (the command launch_ranks builds, with the child process replaced by a stand-in)."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+
+    started = []
+
+    class _Ranks:
+        def __init__(self, cmd, **kw):
+            started.append(cmd)
+            self.stdout = iter(['{"metric": "stand-in"}\n'])
+
+        def wait(self):
+            return 0
+
+    monkeypatch.setattr(bench.subprocess, "Popen", _Ranks)
+    argv = ["--gpus", "2", "--backend", "gloo", "--one-device", "--full", "--dump-outputs", "out", "--steps", "3"]
+    assert bench.launch_ranks(bench.parse(argv), argv) == 0
+    (cmd,) = started
+    ranks = bench.parse(cmd[cmd.index(os.path.abspath(os.path.join(ROOT, "bench.py"))) + 1:])
+    assert ranks.full is True and ranks.dump_outputs == "out" and ranks.steps == 3 and ranks.gpus == 2

@@ -21,7 +21,7 @@ def test_bench_runs_with_n_ranks_on_one_device(world, split):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo", "--one-device",
-                        "--rows", "4000000", "--c5-rows", "2000000", "--c5-layers", "2", "--steps", "3", "--warmup", "1",
+                        "--full", "--rows", "4000000", "--c5-rows", "2000000", "--c5-layers", "2", "--steps", "3", "--warmup", "1",
                         "--verify-queries", "4", "--c5-split", split], capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -43,7 +43,7 @@ def test_bench_with_fp32_rows_sharded_over_four_ranks():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--one-device",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--one-device", "--full",
                         "--storage", "f32", "--rows", "2000000", "--steps", "3", "--warmup", "1", "--verify-queries", "8"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert p.returncode == 0, p.stderr[-3000:]

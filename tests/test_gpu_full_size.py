@@ -1,4 +1,4 @@
-"""BASELINE configs 4 and 5 at their FULL corpus size on one GPU (the driver's bench checks the same property after its
+"""BASELINE configs 4 and 5 at their FULL corpus size on one GPU (`bench.py --full` checks the same property after its
 timed loop; here it is a test): 100M x 768 fp16 rows and 100M x 1024 fp8 rows resident in HBM, one batch of 256 queries,
 top-100 — the size-independent property: an exhaustive canonical re-scan of the whole shard finds NO row beating any
 query's k-th entry and every returned (id, score) pair is the canonical one (rarc_verify_batch), the answer is sorted by

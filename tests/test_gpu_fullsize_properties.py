@@ -1,5 +1,5 @@
 """Size-independent properties at sizes the CPU oracle cannot finish quickly (5M rows here; bench.py
-runs the same verification at its full 100M size):
+--full runs the same verification at its full 100M size):
   * the exact repair scan finds no row beating the returned k-th entry (top-k is exact),
   * returned scores are the canonical scores of the returned rows (oracle re-scores just those rows),
   * rows are ordered (score desc, id asc) and unique,

@@ -189,7 +189,7 @@ def test_bench_over_rccl(world):
 
     _need_gpus(world, "nccl")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--rows", "4000000", "--steps", "3",
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--full", "--rows", "4000000", "--steps", "3",
                            "--warmup", "1", "--c5-rows", "2000000", "--c5-layers", "2", "--no-cpu-baseline", "--verify-queries", "32"],
                           capture_output=True, text=True, timeout=1200, env=env, cwd=ROOT)
     assert proc.returncode == 0, proc.stderr[-3000:]

@@ -2,7 +2,7 @@
 # ONE entry point for the profiles under profiles/ (run it on the GPU box: `gpurun -- 'tools/prof.sh <what> [args]'`).
 # Everything lands in gpurun_out/prof_<what>/ ; copy what you want judged into profiles/ and list it in profiles/INDEX.md.
 #
-#   tools/prof.sh bench                  rocprofv3 --kernel-trace --stats of the default `python bench.py` (the driver's command)
+#   tools/prof.sh bench                  rocprofv3 --kernel-trace --stats of `python bench.py --full` (every leg)
 #   tools/prof.sh shard <rows>           one rank's shard of the headline corpus, exchange forced on the one rank (RARC_FORCE_DIST=1):
 #                                        bench line + per-kernel trace (12500000 / 25000000 / 50000000 = 100M over 8 / 4 / 2 GPUs)
 #   tools/prof.sh pmc <rows> <dim> <f16|f8> [counters...]   a --pmc pass of the scan alone (tools/gpu_scan_only.py; own run, no
@@ -24,11 +24,11 @@ QUIET="--no-c2 --no-c3 --no-c5 --no-persist --no-ingest --no-api --no-f32 --no-w
 stats() { f=$(ls -t "$1"/*/*kernel_stats.csv "$1"/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cut -d, -f1-5 "$f" | cut -c1-140 | head -${2:-14}; }
 case $what in
   bench)
-    timeout 2400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- python3 bench.py "$@" > "$O/bench.json" 2> "$O/bench.err"
+    timeout 2400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- python3 bench.py --full "$@" > "$O/bench.json" 2> "$O/bench.err"
     stats "$O/kt"; tail -c 600 "$O/bench.json";;
   shard)
     rows=${1:-12500000}; shift
-    RARC_FORCE_DIST=1 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_$rows" -- python3 bench.py --rows $rows $QUIET --verify-queries 32 "$@" > "$O/shard_$rows.json" 2> "$O/shard_$rows.err"
+    RARC_FORCE_DIST=1 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_$rows" -- python3 bench.py --full --rows $rows $QUIET --verify-queries 32 "$@" > "$O/shard_$rows.json" 2> "$O/shard_$rows.err"
     stats "$O/kt_$rows"
     python3 -c "import json; j=json.load(open('$O/shard_$rows.json')); print('SHARD $rows: ms/step', j['ms_per_step'], 'scan ms', j['roofline']['scan_ms_per_pass'], 'scan frac', j['roofline']['frac'], 'exchange ms', j['config']['exchange_ms_per_step'])";;
   pmc)
@@ -36,16 +36,16 @@ case $what in
     timeout 900 rocprofv3 --pmc ${@:-FETCH_SIZE} -d "$O/pmc" -- python3 tools/gpu_scan_only.py > "$O/pmc.log" 2>&1
     python3 tools/pmc_summary.py "$O/pmc" all | tee "$O/pmc_summary.txt" | grep -i scan | head -6;;
   c2)
-    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- python3 bench.py --rows 1000000 --steps 400 --warmup 20 $QUIET --verify-queries 32 "$@" > "$O/c2.json" 2> "$O/c2.err"
+    timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- python3 bench.py --full --rows 1000000 --steps 400 --warmup 20 $QUIET --verify-queries 32 "$@" > "$O/c2.json" 2> "$O/c2.err"
     stats "$O/kt" 12
     python3 -c "import json; j=json.load(open('$O/c2.json')); print('C2 (profiled): ms/step', j['ms_per_step'], j['config']['full_size_check'])"
-    timeout 600 python3 bench.py --rows 1000000 --steps 400 --warmup 20 $QUIET --verify-queries 32 "$@" 2>/dev/null > "$O/c2_unprofiled.json"
+    timeout 600 python3 bench.py --full --rows 1000000 --steps 400 --warmup 20 $QUIET --verify-queries 32 "$@" 2>/dev/null > "$O/c2_unprofiled.json"
     python3 -c "import json; j=json.load(open('$O/c2_unprofiled.json')); print('C2 (unprofiled): ms/step', j['ms_per_step'], 'q/s', j['value'])";;
   encq)  tools/r06_encq.sh;;
-  api)   timeout 900 python3 bench.py --no-c3 --no-c5 --no-persist --no-ingest --no-f32 --no-wide --no-pairs "$@" > "$O/api.json" 2> "$O/api.err"; python3 -c "import json; print(json.dumps(json.load(open('$O/api.json'))['api'], indent=1))";;
-  wide)  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- python3 bench.py --rows 1000000 --no-c2 --no-c3 --no-c5 --no-persist --no-ingest --no-api --no-f32 --no-pairs --no-cpu-baseline --verify-queries 8 "$@" > "$O/wide.json" 2> "$O/wide.err"; stats "$O/kt" 10; python3 -c "import json; print(json.dumps(json.load(open('$O/wide.json'))['wide']))";;
-  f32)   timeout 900 python3 bench.py --rows 1000000 --no-c2 --no-c3 --no-c5 --no-persist --no-ingest --no-api --no-wide --no-pairs --no-cpu-baseline --verify-queries 8 "$@" > "$O/f32.json" 2> "$O/f32.err"; python3 -c "import json; print(json.dumps(json.load(open('$O/f32.json'))['f32']))";;
-  pairs) timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- python3 bench.py --rows 1000000 --no-c2 --no-c3 --no-c5 --no-persist --no-ingest --no-api --no-f32 --no-wide --verify-queries 8 "$@" > "$O/pairs.json" 2> "$O/pairs.err"; stats "$O/kt" 8; python3 -c "import json; print(json.dumps(json.load(open('$O/pairs.json'))['pairs']))";;
+  api)   timeout 900 python3 bench.py --full --no-c3 --no-c5 --no-persist --no-ingest --no-f32 --no-wide --no-pairs "$@" > "$O/api.json" 2> "$O/api.err"; python3 -c "import json; print(json.dumps(json.load(open('$O/api.json'))['api'], indent=1))";;
+  wide)  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- python3 bench.py --full --rows 1000000 --no-c2 --no-c3 --no-c5 --no-persist --no-ingest --no-api --no-f32 --no-pairs --no-cpu-baseline --verify-queries 8 "$@" > "$O/wide.json" 2> "$O/wide.err"; stats "$O/kt" 10; python3 -c "import json; print(json.dumps(json.load(open('$O/wide.json'))['wide']))";;
+  f32)   timeout 900 python3 bench.py --full --rows 1000000 --no-c2 --no-c3 --no-c5 --no-persist --no-ingest --no-api --no-wide --no-pairs --no-cpu-baseline --verify-queries 8 "$@" > "$O/f32.json" 2> "$O/f32.err"; python3 -c "import json; print(json.dumps(json.load(open('$O/f32.json'))['f32']))";;
+  pairs) timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -- python3 bench.py --full --rows 1000000 --no-c2 --no-c3 --no-c5 --no-persist --no-ingest --no-api --no-f32 --no-wide --verify-queries 8 "$@" > "$O/pairs.json" 2> "$O/pairs.err"; stats "$O/kt" 8; python3 -c "import json; print(json.dumps(json.load(open('$O/pairs.json'))['pairs']))";;
   enc)   RARC_ENC_PRECISION=${1:-fp32} python3 tools/enc_batch_sweep.py 2>/dev/null | grep ENC | tee "$O/enc_${1:-fp32}.txt";;
   power) out=$1; shift; tools/power_sample.sh "$O/$out" "$@";;
   vmem)  python3 tools/vmem_probe.py 2>&1 | grep -v amdgpu.ids | tee "$O/vmem_probe.txt";;

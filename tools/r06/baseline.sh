@@ -7,7 +7,7 @@ timeout 900 python3 -m pytest tests/test_gpu_batching.py tests/test_gpu_growable
 tools/enc_small_trace.sh 1 2>&1 | tee "$O/enc_small_n1.txt"
 tools/prof.sh shard 12500000 2>&1 | tee "$O/shard.txt"
 QUIET="--no-c3 --no-c5 --no-persist --no-ingest --no-api --no-f32 --no-wide --no-pairs --no-cpu-baseline"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_c2" -- python3 bench.py --rows 1000000 $QUIET --verify-queries 8 > "$O/c2.json" 2> "$O/c2.err"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt_c2" -- python3 bench.py --full --rows 1000000 $QUIET --verify-queries 8 > "$O/c2.json" 2> "$O/c2.err"
 f=$(ls -t "$O"/kt_c2/*/*kernel_stats.csv | head -1); cut -d, -f1-5 "$f" | cut -c1-150 | head -14 | tee "$O/c2_kernels.txt"
 tail -c 400 "$O/c2.json"
 find "$O" -name "*.db" -delete 2>/dev/null

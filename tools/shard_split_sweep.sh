@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 rows=${1:-12500000}; shift
 for divs in "${@:-512,64,8}"; do
-  RARC_SPLIT_DIVS=$divs RARC_FORCE_DIST=1 python3 bench.py --rows $rows --steps 60 --warmup 5 --no-c2 --no-c3 --no-c5 --no-persist --no-ingest --no-api --no-f32 --no-wide --no-pairs --no-cpu-baseline --verify-queries 8 2>/dev/null > /tmp/split.json
+  RARC_SPLIT_DIVS=$divs RARC_FORCE_DIST=1 python3 bench.py --full --rows $rows --steps 60 --warmup 5 --no-c2 --no-c3 --no-c5 --no-persist --no-ingest --no-api --no-f32 --no-wide --no-pairs --no-cpu-baseline --verify-queries 8 2>/dev/null > /tmp/split.json
   python3 - "$divs" <<'PY'
 import json, sys
 j = json.load(open("/tmp/split.json"))
