@@ -311,6 +311,28 @@ int rarc_search_batch(const RarcSearchBatch* batch, void* stream);
  */
 int rarc_stream_read(const void* d_src, size_t n_bytes, void* d_sink, void* stream);
 
+/*
+ * Okapi BM25 (core/retrieval/bm25.py: BM25Retriever over rank_bm25 0.2.2's BM25Okapi.get_scores), ABI 600.
+ * Index: a term-major CSR built on the host — d_post_off [n_terms + 1] int64, d_post_doc int32 (ascending within each
+ * term), d_post_w fp64 (the reference's per-posting fraction tf*(k1+1) / (tf + k1*((1-b) + b*dl/avgdl))).
+ * Queries: d_q_off [nq + 1] int32 into d_q_term int32 / d_q_idf fp64 (tokens in query order, duplicates kept, OOV tokens
+ * left out).  score[d] = sum over the query's tokens in order of idf * w, fp64, no fused multiply-add: bit-identical to
+ * the reference.  Limits: 1 <= n_docs <= 2^31 - 1 - 8192, nq <= 65535.
+ * rarc_bm25_topk: the k best per query (1 <= k <= min(1024, n_docs)), score descending, doc index ascending among equal
+ * scores, into d_out_ids [nq][k] / d_out_scores [nq][k].  Documents no token reaches score 0.0 and take part.
+ * rarc_bm25_scores: every score, d_out_scores [nq][n_docs].
+ * d_workspace: rarc_bm25_workspace_bytes(nq, n_query_tokens, n_docs, k) bytes (k = 0 for rarc_bm25_scores); 0 = bad sizes.
+ */
+size_t rarc_bm25_workspace_bytes(int nq, int64_t n_query_tokens, int64_t n_docs, int k);
+int rarc_bm25_topk(const int64_t* d_post_off, const int32_t* d_post_doc, const double* d_post_w, int64_t n_terms,
+                   int64_t n_docs, const int32_t* d_q_off, const int32_t* d_q_term, const double* d_q_idf, int nq,
+                   int64_t n_query_tokens, int k, void* d_workspace, size_t workspace_bytes, int64_t* d_out_ids,
+                   double* d_out_scores, void* stream);
+int rarc_bm25_scores(const int64_t* d_post_off, const int32_t* d_post_doc, const double* d_post_w, int64_t n_terms,
+                     int64_t n_docs, const int32_t* d_q_off, const int32_t* d_q_term, const double* d_q_idf, int nq,
+                     int64_t n_query_tokens, void* d_workspace, size_t workspace_bytes, double* d_out_scores,
+                     void* stream);
+
 int rarc_repair_f32(const float* d_corpus_f32, int64_t n_rows, int d_pad, const void* d_qblock, int q, int k,
                     int64_t id_base, int64_t* d_out_ids, float* d_out_scores, uint32_t* d_found, void* d_workspace,
                     size_t workspace_bytes, void* stream);

@@ -7,7 +7,8 @@ JSON -> <Config>(**data).build() -> module graph, e.g.
      "retrievers": [{"type": "vectorstore_retriever", "search_type": "similarity",
                      "vectorstore": {"type": "hip_flat_vectorstore", "metric": "cosine",
                                      "embedding": {"type": "table_embeddings", "path": "emb.npz"},
-                                     "corpus_path": "corpus.npz"}}]}
+                                     "corpus_path": "corpus.npz"}},
+                    {"type": "hip_bm25_retriever", "corpus_path": "corpus.npz", "k1": 1.5, "b": 0.75}]}
 """
 from dataclasses import dataclass, field
 from typing import ClassVar, Annotated, Any, Dict, List, Literal, Optional, Union
@@ -214,6 +215,39 @@ class VectorStoreRetrieverConfig(AbstractConfig):
                                                                   search_kwargs=dict(self.search_kwargs)))
 
 
+class HipBM25RetrieverConfig(AbstractConfig):
+    """The lexical arm of hybrid retrieval (the reference's BM25Retriever, core/retrieval/bm25.py) on the MI355X.
+    `corpus_path`: .npz with `texts` (and optional `ids`), tokenised by whitespace split (the reference's default
+    preprocess_func); `index_path`: a file written by HipBM25Retriever.save_to_disk (the index is not rebuilt; its own
+    k1 / b / epsilon and preprocess_func hold).  k1, b, epsilon: BM25Okapi's parameters."""
+    type: Literal["hip_bm25_retriever"] = "hip_bm25_retriever"
+    corpus_path: Optional[str] = None
+    index_path: Optional[str] = None
+    k: int = 5
+    k1: float = 1.5
+    b: float = 0.75
+    epsilon: float = 0.25
+    device: int = 0
+
+    def build(self) -> AbstractModule:
+        import numpy as np
+
+        from ..core.retrieval.bm25 import HipBM25Retriever
+
+        if self.index_path:
+            retriever = HipBM25Retriever.load_from_disk(self.index_path, device=self.device)
+            retriever.update_k(self.k)
+        elif self.corpus_path:
+            data = np.load(self.corpus_path, allow_pickle=False)
+            ids = [str(i) for i in data["ids"]] if "ids" in data else None
+            retriever = HipBM25Retriever.from_texts([str(t) for t in data["texts"]], ids=ids, k=self.k,
+                                                    bm25_params={"k1": self.k1, "b": self.b, "epsilon": self.epsilon},
+                                                    device=self.device, warn_default_preprocess=False)
+        else:
+            raise ValueError("hip_bm25_retriever: give corpus_path or index_path")
+        return BuiltModule(config=self, impl=retriever)
+
+
 class HipLogitRerankerConfig(AbstractConfig):
     """The yes/no-logit reranker as a registered module (core/rerank/Reranker_Qwen3.py:6-75).  The score -> order
     step runs in the rarc_rerank_order kernel; the (no, yes) logits come from `logits_path`, an .npz table of
@@ -331,7 +365,7 @@ class RRFusionConfig(AbstractConfig):
 
 class MultiPathRetrieverConfig(AbstractConfig):
     type: Literal["multipath_retriever"] = "multipath_retriever"
-    retrievers: List[Annotated[Union[VectorStoreRetrieverConfig], Field(discriminator="type")]]
+    retrievers: List[Annotated[Union[VectorStoreRetrieverConfig, HipBM25RetrieverConfig], Field(discriminator="type")]]
     fusion: RRFusionConfig = Field(default_factory=RRFusionConfig)
     top_k_per_retriever: int = 50
 

@@ -211,6 +211,11 @@ SIGNATURES = {
     "rarc_vmem_destroy": (c_int, [c_void_p]),
     "rarc_profile_begin": (c_int, [c_int]),
     "rarc_profile_end": (c_int, [ctypes.POINTER(c_double), ctypes.POINTER(c_int)]),
+    "rarc_bm25_workspace_bytes": (c_size_t, [c_int, c_int64, c_int64, c_int]),
+    "rarc_bm25_topk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                               c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "rarc_bm25_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                                 c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 
