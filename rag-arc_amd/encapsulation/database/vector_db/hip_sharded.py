@@ -133,7 +133,10 @@ class _ShardedIndex:
         it made them: the collectives line up) and returns the merged answer as numpy."""
         if not hasattr(self.local, "search_async") or self.local.ntotal < k:
             return _Ready(self.search(queries, k))         # (short shards take the padded synchronous path)
-        return _PendingShard(self, self.local.search_async(queries, k), k)
+        # the local -> global map of the rows this scan reads: a remove_rows() before host() replaces self._l2g (it is never
+        # changed in place), and the answer must be mapped with the map of its launch
+        l2g = self._global_ids(self.torch.device(getattr(self.local, "device", "cpu")))
+        return _PendingShard(self, self.local.search_async(queries, k), k, l2g)
 
     @property
     def max_norm(self):
@@ -151,13 +154,13 @@ class _Ready:
 class _PendingShard:
     """A local scan in flight; host() = status check (+ rare repair) -> global ids -> exchange -> numpy."""
 
-    def __init__(self, index: _ShardedIndex, handle, k: int):
-        self.index, self.handle, self.k = index, handle, k
+    def __init__(self, index: _ShardedIndex, handle, k: int, l2g):
+        self.index, self.handle, self.k, self.l2g = index, handle, k, l2g
 
     def host(self):
         idx, t = self.index, self.index.torch
         ids, sc = self.handle.result()
-        l2g = idx._global_ids(ids.device)
+        l2g = self.l2g if self.l2g.device == ids.device else self.l2g.to(ids.device)
         base = int(getattr(idx.local, "id_base", 0))
         ids = t.where(ids >= 0, l2g[(ids - base).clamp(min=0)], ids)
         ids, sc = idx.exchange._exchange(ids.contiguous(), sc.contiguous(), self.k)

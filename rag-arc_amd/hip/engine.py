@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
+import weakref
 from typing import Optional, Tuple
 
 import numpy as np
@@ -253,6 +254,7 @@ class FlatIndexF16:
         self._pins = _PinnedPool()  # pinned staging for answers (shared with the index's twins: copy.copy keeps the object)
         self._flags = _FlagPool()   # pinned status words, one per launch in flight
         self._own_stream = None    # twin(): the side stream its searches are enqueued on
+        self._contexts = weakref.WeakSet()   # the live twin() contexts of this index (the pipelined pair included)
         # growable=True: the row buffers live in DeviceArenas (HIP virtual memory) — add() past the capacity maps more
         # memory behind the same pointer instead of allocating a bigger buffer and copying (peak = live rows + one step
         # of at most 1 GiB; the reallocating form peaks at 3x).  max_rows: the address space to reserve (0 = what the
@@ -408,6 +410,18 @@ class FlatIndexF16:
     def _stream(self):
         return self.torch.cuda.current_stream(self.device).cuda_stream
 
+    def _fence_contexts(self) -> None:
+        """Every change of the rows starts here (caller holds self._lock): the caller's stream waits for what the search
+        contexts (twin(), the pipelined pair) have enqueued on their side streams, so a batch still in flight there reads the
+        rows, tile metadata and shadow image as they were at its launch.  No host synchronisation.  Lock order: index, then
+        context (a context never takes its index's lock); holding the context's lock covers a launch another thread is
+        enqueueing right now."""
+        cur = self.torch.cuda.current_stream(self.device)
+        for ctx in list(self._contexts):
+            with ctx._lock:
+                if ctx._own_stream is not None and ctx._own_stream != cur:
+                    cur.wait_stream(ctx._own_stream)
+
     def _workspace(self, k: int = 0, scale: int = 1):
         """Scratch for one search.  The candidate buffer grows with k (the int8 margin lets through a number of
         candidates roughly proportional to k): `cand_cap` is per 128 results — k = 996 takes 8 x 268 MB.
@@ -481,6 +495,7 @@ class FlatIndexF16:
         self._not_a_twin()
         t = self.torch
         with self._lock, t.cuda.device(self.device):
+            self._fence_contexts()
             x = t.as_tensor(vectors, dtype=t.float32).to(self.device).contiguous()
             if x.ndim != 2 or x.shape[1] != self.dim:
                 raise ValueError(f"expected [n][{self.dim}] vectors, got {tuple(x.shape)}")
@@ -525,6 +540,7 @@ class FlatIndexF16:
         if self.storage != "f16":
             raise B.RarcError("add_rows_f16 needs fp16 storage")
         with self._lock, t.cuda.device(self.device):
+            self._fence_contexts()
             if rows_f16.dtype != t.float16 or rows_f16.shape[1] != self.d_pad:
                 raise ValueError("rows must be float16 [n][d_pad]")
             n = rows_f16.shape[0] if n_valid is None else int(n_valid)
@@ -550,6 +566,7 @@ class FlatIndexF16:
         if (self.storage == "f8") != (row_scales is not None):
             raise ValueError("row_scales go with fp8 storage (and only with it)")
         with self._lock, t.cuda.device(self.device):
+            self._fence_contexts()
             n = rows_host.shape[0]
             if rows_host.shape[1] != self.d_pad:
                 raise ValueError("rows must be [n][d_pad]")
@@ -665,6 +682,7 @@ class FlatIndexF16:
                 raise ValueError(f"{path}: rows [{a}, {a + c}) outside the file's {hdr.n_rows}")
         n_new = sum(c for _, c in ranges)
         with self._lock, t.cuda.device(self.device):
+            self._fence_contexts()
             old = self.ntotal
             if n_new == 0:
                 return dict(bytes=0, seconds=0.0, gb_per_s=0.0)
@@ -702,6 +720,7 @@ class FlatIndexF16:
         if holes[0] < 0 or holes[-1] >= self.ntotal:
             raise IndexError(f"rows to remove must lie in [0, {self.ntotal})")
         with self._lock, t.cuda.device(self.device):
+            self._fence_contexts()
             adj = t.from_numpy(holes - np.arange(holes.size, dtype=np.int64)).to(self.device)
             first, n = int(holes[0]), int(self.ntotal)
             bufs = [(self._rows, self._rows.shape[1] * self._rows.element_size())]
@@ -730,6 +749,7 @@ class FlatIndexF16:
     def reset(self) -> None:
         self._not_a_twin()
         with self._lock:
+            self._fence_contexts()
             self._version += 1
             self.ntotal = 0
             self.max_norm = 0.0
@@ -742,7 +762,8 @@ class FlatIndexF16:
         searches are enqueued on.  Alternating batches between an index and its twin keeps two searches in flight on
         two streams, so the small kernels either side of one batch's scan (query prep, seed, finalize) run under the
         other's (1M x 768: 0.480 -> 0.463 ms per batch).  Read-only: it refuses to search once the parent's rows have
-        changed (take a new twin), and it cannot be added to."""
+        changed (take a new twin), and it cannot be added to.  A batch already in flight on it when the parent's rows
+        change answers on the rows as they were at its launch: the parent's mutators wait for the side stream first."""
         import copy
 
         t = self.torch
@@ -752,8 +773,10 @@ class FlatIndexF16:
             other._ws, other._qbuf, other._cap_eff = None, None, 0
             other._parent, other._parent_version = self, self._version
             other._pair, other._partner, other._fin_event = None, None, None
+            other._contexts = weakref.WeakSet()
             with t.cuda.device(self.device):
                 other._own_stream = t.cuda.Stream()
+            self._contexts.add(other)       # this index's mutators wait for its side stream (_fence_contexts)
         return other
 
     # the fp16-scan path (small shards: config 2) spends a sixth of a batch in small dependent kernels either side of the scan
@@ -771,8 +794,6 @@ class FlatIndexF16:
             return None
         pair = self.__dict__.get("_pair")
         if pair is None or pair[0]._parent_version != self._version:
-            import weakref
-
             a, b = self.twin(), self.twin()
             # (the pair belongs to this index and to nothing else: no reference cycle through it — contexts see their index and
             #  each other weakly — so an index dropped by its last reference frees its rows at once, not at the cyclic
@@ -937,7 +958,12 @@ class FlatIndexF16:
         identical to search_device().  More than 256 queries are enqueued as consecutive 256-query launches.
         to_host=True: the answer is written into pinned host memory by the search's own finalize kernel — `.host()` /
         `.host_view()` wait for this batch only and no device copy of the answer exists (`.result()` of such a handle returns
-        the pinned host tensors)."""
+        the pinned host tensors).
+        A batch answers on the rows as they were when it was enqueued, whatever add() / remove_rows() / reset() follows
+        before it is collected (one with a flagged query raises RarcError in result() instead: its repair would read the
+        changed rows).  A query tensor already on the device is read in place, not copied: leave it untouched
+        until result() (the batch's query prep reads it on the search's stream, and the repair of a flagged query reads it
+        again)."""
         t = self.torch
         if k < 1:
             raise ValueError("k out of range")
@@ -1354,6 +1380,11 @@ class PendingSearch:
         self.stream = stream    # the stream the search was enqueued on (a twin's side stream, else the caller's)
         self.version = version  # version of the rows when it was enqueued
         self.repaired = None
+        self.released = False   # release() was called: the answer is gone (a to_host=True one went back with its slot)
+
+    def _check_live(self) -> None:
+        if self.released:
+            raise B.RarcError("this search handle was released (host() releases it): its answer is no longer available")
 
     def _flag_word(self) -> int:
         """The launch's status word, read once; its pinned word goes back to the pool."""
@@ -1382,6 +1413,7 @@ class PendingSearch:
         reading.  So the repair is enqueued on the stream the search itself ran on: behind everything already queued
         there, ahead of everything queued later, whatever stream the collecting thread happens to be on; and that
         stream is drained before the answer is handed out, so it is safe to use on any stream."""
+        self._check_live()
         if self.repaired is None:
             t = self.index.torch
             self.repaired = []
@@ -1432,10 +1464,15 @@ class PendingSearch:
         return scores, ids
 
     def release(self) -> None:
-        """Give the pinned staging slot back (arrays from host_view() must not be read afterwards)."""
-        self.host_copy = None
+        """End the handle: the pinned staging slot goes back to the pool (arrays from host_view() must not be read
+        afterwards) and result() / host_view() / host() raise from now on — the slot's next search writes its answer where
+        this one's was.  A batch not collected yet is waited for first: its finalize kernel may still be writing the slot."""
+        self.released = True
+        self.ids = self.scores = self.host_copy = None
         slot, self.slot = self.slot, None
         if slot is not None:
+            if self.done is not None and self.flag is not None:
+                self.done.synchronize()
             slot.release()
 
 
@@ -1449,8 +1486,12 @@ class PendingBatches:
         for p in parts:             # the one slot is this handle's: a part must not hand it back on its own
             p.slot = None
         self.repaired = None
+        self.released = False
+
+    _check_live = PendingSearch._check_live
 
     def result(self):
+        self._check_live()
         if self.repaired is None:
             self.repaired = []
             for i, p in enumerate(self.parts):
@@ -1476,9 +1517,13 @@ class PendingBatches:
         return scores, ids
 
     def release(self) -> None:
-        self.host_copy = None
-        for p in self.parts:
-            p.host_copy = None
+        """As PendingSearch.release(), for every launch of the call (they share one slot)."""
         slot, self.slot = self.slot, None
+        for p in self.parts:
+            if slot is not None and p.done is not None and p.flag is not None:
+                p.done.synchronize()
+            p.release()
+        self.released = True
+        self.ids = self.scores = self.host_copy = None
         if slot is not None:
             slot.release()
