@@ -653,6 +653,23 @@ int rarc_search_wide(const void* d_rows, const uint16_t* d_image16, int fmt, int
                      float* d_out_scores, uint32_t* d_status, void* d_ws, size_t ws_bytes, int cand_cap, void* stream);
 
 /*
+ * Metric "l2": exact squared-Euclidean top-k (faiss.IndexFlatL2; VectorStore_Faiss.py:73-146 takes "l2" next to "cosine" and
+ * "ip") on the same chunked GEMM + select + canonical finalize.  With dot() the canonical fp32 inner product,
+ *     dist = max(0, (dot(q, q) + dot(x, x)) - 2 dot(q, x))      every operation fp32, x the stored row
+ * ordered by (dist ascending, id ascending) — faiss's own expansion for batched L2 with summation and tie order pinned
+ * (csrc/wide.hip has the bound that makes the nominee lists complete).
+ * rarc_row_sqnorms: d_xn[r] = dot(x_r, x_r) for r in [first_row, n_rows) — fmt 0: fp16 rows [n_rows][d_pad], fmt 2: fp32 rows.
+ * Derived data: recompute it for appended rows, from the first hole after rarc_compact_rows, for all rows after a load.
+ * rarc_search_wide_l2: the arguments of rarc_search_wide plus d_xn (fp32 [n_rows]); d_out_scores receives the squared
+ * distances, smallest first (+inf with id -1 beyond the stored rows); workspace and overflow protocol are rarc_search_wide's.
+ * Takes every d_pad <= 4096 and k <= 8192 (there is no register-resident L2 scan).
+ */
+int rarc_row_sqnorms(const void* d_rows, int fmt, int64_t n_rows, int d_pad, int64_t first_row, float* d_xn, void* stream);
+int rarc_search_wide_l2(const void* d_rows, const uint16_t* d_image16, int fmt, int64_t n_rows, int d_pad, float max_norm,
+                        float rho, const float* d_xn, const void* d_qblock, int nq, int k, int64_t id_base, int64_t* d_out_ids,
+                        float* d_out_scores, uint32_t* d_status, void* d_ws, size_t ws_bytes, int cand_cap, void* stream);
+
+/*
  * All pairs (i < j) of n embeddings whose cosine reaches a threshold — the entity de-duplication of the reference's graph
  * store (encapsulation/database/graph_db/Base_Neo4j.py:538-583: sklearn.metrics.pairwise.cosine_similarity over every entity
  * embedding, then a python loop over i < j keeping similarity >= 0.95); SURVEY 8(f) rank 4.  The n x n matrix is never

@@ -107,7 +107,7 @@ EmbeddingsConfig = Annotated[Union[TableEmbeddingsConfig, HipBertEmbeddingsConfi
 class HipFlatVectorStoreConfig(AbstractConfig):
     type: Literal["hip_flat_vectorstore"] = "hip_flat_vectorstore"
     embedding: EmbeddingsConfig
-    metric: Literal["cosine", "ip"] = "cosine"
+    metric: Literal["cosine", "ip", "l2"] = "cosine"   # "l2": squared Euclidean distances, nearest first (fp16 / fp32 rows)
     normalize_L2: bool = False
     device: int = 0
     storage: Literal["f16", "f8", "f32"] = "f16"  # rows in HBM: fp16, fp8 e4m3fn + per-row scale, or fp32 (the reference's)

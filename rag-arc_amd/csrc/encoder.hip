@@ -307,6 +307,9 @@ struct GemmSplitEpi {
   // a query's list is `shards` (1 or 8) sub-lists of cap / shards entries with a counter each (count is [N][shards]); a workgroup
   // nominates into sub-list blockIdx.x % shards — 1000 workgroups adding to ONE counter per query serialise on it (wide.hip)
   uint32_t shards = 1;
+  // ACT 7 (wide.hip, metric "l2"): ACT 6 on the key acc - xn[r] / 2, xn the squared norms of the tile's rows (fp32 [M]): the
+  // largest keys are the smallest squared distances |q|^2 + xn - 2 acc.  One 4-byte load per row and lane group.
+  const float* xn = nullptr;
 };
 __device__ __forceinline__ float gemm_gelu_libm(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
@@ -593,7 +596,19 @@ __global__ __launch_bounds__(512, 1) void rarc_gemm256_f16_kernel(const half_t* 
       }
       __builtin_amdgcn_wave_barrier();
     }
-  } else if constexpr (BASE == 6) {  // scores against per-column thresholds -> candidate lists; nothing is stored (wide.hip)
+  } else if constexpr (BASE == 6 || BASE == 7) {  // scores against per-column thresholds -> candidate lists; nothing is stored (wide.hip)
+    if constexpr (BASE == 7) {   // the L2 key, in place (no register beyond the eight norms, dead after this block): xn / 2 is exact,
+                                 // the subtraction rounds once — contracted into an FMA or not, the same bits
+      float xh[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) xh[i] = 0.5f * fx.xn[(size_t)tm * 256 + wr * 128 + i * 16 + row_e];
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[i][j][e] = acc[i][j][e] - xh[i];
+    }
     float t16[4][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1458,8 +1473,16 @@ __global__ __launch_bounds__(512, 1) void rarc_gemm128pp_f16_kernel(const half_t
         *(uint4*)(rowp + (c - 4) * 8) = v;
       }
     }
-  } else if (BASE == 6) {  // scores against per-column thresholds -> candidate lists, nothing stored (as the 256 x 256 kernel's ACT 6;
+  } else if (BASE == 6 || BASE == 7) {  // scores against per-column thresholds -> candidate lists, nothing stored (as the 256 x 256 kernel's ACT 6;
                            // wide.hip's chunks of at most one 256 x 256 tile per CU: four of these tiles per CU pipeline, one does not)
+    if constexpr (BASE == 7) {   // the L2 key acc - xn[r] / 2, in place (see the 256 x 256 kernel's ACT 7)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const float xh = 0.5f * fx.xn[(size_t)tm * 128 + wr * 64 + i * 32 + row];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) acc[i][c] = acc[i][c] - xh;
+      }
+    }
     // register (i, 4g + e): rows wr*64 + i*32 + row, column wc*32 + 8g + 4hh + e — one query per half-wave (hh), 32 rows across it;
     // counted first, one atomic per column and half-wave, then written (see the 256 x 256 kernel's ACT 6)
     const unsigned long long grp_mask = hh ? 0xFFFFFFFF00000000ull : 0x00000000FFFFFFFFull;
@@ -2108,6 +2131,7 @@ static int gemm_attrs() {
   RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_gemm256_f16_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, G256_LDS));
   RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_gemm256_f16_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, G256_LDS));
   RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_gemm256_f16_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, G256_LDS));
+  RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_gemm256_f16_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, G256_LDS));
   RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_gemm256_f16_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, G256_LDS));
   RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_gemm256_f16_kernel<19>, hipFuncAttributeMaxDynamicSharedMemorySize, G256_LDS));
   RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_gemm256_f16_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, G256_LDS));
@@ -2130,6 +2154,7 @@ static int gemm_attrs() {
   RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_gemm128pp_f16_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, G128S_LDS));
   RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_gemm128pp_f16_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, G128S_LDS));
   RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_gemm128pp_f16_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, G128S_LDS));
+  RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_gemm128pp_f16_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, G128S_LDS));
   attr = 1;
   return RARC_OK;
 }
@@ -2331,9 +2356,10 @@ int rarc_gemm_fused_norm(const uint16_t* d_a, const uint16_t* d_w, const void* d
 // The score GEMM of the wide search path with its select in the epilogue (wide.hip, round 5): S = A[M][K]·W[256][K]ᵀ in fp32,
 // never stored — S[r][q] >= thr[q] sends (score, row0 + r) to query q's candidate list.  M a multiple of 256, K of 64, >= 256.
 bool rarc_gemm_f16_select_takes(int m, int k) { return m > 0 && m % 256 == 0 && k % GK == 0 && k >= 4 * GK; }
-int rarc_gemm_f16_select(const uint16_t* a, const uint16_t* w, int m, int k, const float* thr, unsigned long long* cand,
-                         uint32_t* count, uint32_t* status, uint32_t cap, uint32_t row0, uint32_t n_valid, uint32_t shards,
-                         hipStream_t s) {
+// xn: null = ACT 6 (inner-product scores); else ACT 7, the L2 key acc - xn[r] / 2 (xn fp32 [m]: the squared norms of the rows of a)
+static int gemm_f16_select_impl(const uint16_t* a, const uint16_t* w, int m, int k, const float* thr, unsigned long long* cand,
+                                uint32_t* count, uint32_t* status, uint32_t cap, uint32_t row0, uint32_t n_valid, uint32_t shards,
+                                const float* xn, hipStream_t s) {
   RARC_REQUIRE(a && w && thr && cand && count && status && rarc_gemm_f16_select_takes(m, k) && (shards == 1 || shards == 8) &&
                    cap % shards == 0,
                RARC_E_INVALID, "rarc_gemm_f16_select: bad arguments (m=%d k=%d shards=%u cap=%u)", m, k, shards, cap);
@@ -2343,21 +2369,45 @@ int rarc_gemm_f16_select(const uint16_t* a, const uint16_t* w, int m, int k, con
   GemmSplitEpi fx;
   fx.thr = thr; fx.cand = cand; fx.count = count; fx.status = status; fx.cap = cap; fx.row0 = row0; fx.n_valid = n_valid;
   fx.shards = shards;
+  fx.xn = xn;
   const int tiles = m / 256;
   // up to one 256 x 256 tile per CU: the tiles start in lockstep, every CU fetches, then every CU multiplies — a lone tile took
   // 169 us where a streamed one takes 53.  The 128 x 128 ping-pong kernel (four tiles per CU's worth of work, a four-deep
   // operand ring) takes those chunks: the ramp of every search and all of a small shard.
   static const int small_max = getenv("RARC_WIDE_SMALL_TILES") ? atoi(getenv("RARC_WIDE_SMALL_TILES")) : 256;   // (A/B: 0 = never)
   if (tiles <= small_max) {
-    hipLaunchKernelGGL((rarc_gemm128pp_f16_kernel<6>), dim3((m / 128) * 2, 1), dim3(512), G128S_LDS, s, (const half_t*)a, (const half_t*)w,
-                       (const half_t*)nullptr, (half_t*)nullptr, m, 256, k, k, order, (float*)nullptr, fx);
+    if (xn) {
+      hipLaunchKernelGGL((rarc_gemm128pp_f16_kernel<7>), dim3((m / 128) * 2, 1), dim3(512), G128S_LDS, s, (const half_t*)a, (const half_t*)w,
+                         (const half_t*)nullptr, (half_t*)nullptr, m, 256, k, k, order, (float*)nullptr, fx);
+    } else {
+      hipLaunchKernelGGL((rarc_gemm128pp_f16_kernel<6>), dim3((m / 128) * 2, 1), dim3(512), G128S_LDS, s, (const half_t*)a, (const half_t*)w,
+                         (const half_t*)nullptr, (half_t*)nullptr, m, 256, k, k, order, (float*)nullptr, fx);
+    }
     RARC_HIP_CHECK(hipGetLastError());
     return RARC_OK;
   }
-  hipLaunchKernelGGL((rarc_gemm256_f16_kernel<6>), dim3(tiles > 256 ? 256 : tiles), dim3(512), G256_LDS, s, (const half_t*)a,
-                     (const half_t*)w, (const half_t*)nullptr, (half_t*)nullptr, m, 256, k, order, (float*)nullptr, fx);
+  if (xn) {
+    hipLaunchKernelGGL((rarc_gemm256_f16_kernel<7>), dim3(tiles > 256 ? 256 : tiles), dim3(512), G256_LDS, s, (const half_t*)a,
+                       (const half_t*)w, (const half_t*)nullptr, (half_t*)nullptr, m, 256, k, order, (float*)nullptr, fx);
+  } else {
+    hipLaunchKernelGGL((rarc_gemm256_f16_kernel<6>), dim3(tiles > 256 ? 256 : tiles), dim3(512), G256_LDS, s, (const half_t*)a,
+                       (const half_t*)w, (const half_t*)nullptr, (half_t*)nullptr, m, 256, k, order, (float*)nullptr, fx);
+  }
   RARC_HIP_CHECK(hipGetLastError());
   return RARC_OK;
+}
+
+int rarc_gemm_f16_select(const uint16_t* a, const uint16_t* w, int m, int k, const float* thr, unsigned long long* cand,
+                         uint32_t* count, uint32_t* status, uint32_t cap, uint32_t row0, uint32_t n_valid, uint32_t shards,
+                         hipStream_t s) {
+  return gemm_f16_select_impl(a, w, m, k, thr, cand, count, status, cap, row0, n_valid, shards, nullptr, s);
+}
+// The L2 form (wide.hip, rarc_search_wide_l2): candidates are (acc - xn[r] / 2, row0 + r), thr is a threshold on that key.
+int rarc_gemm_f16_select_l2(const uint16_t* a, const uint16_t* w, int m, int k, const float* xn, const float* thr,
+                            unsigned long long* cand, uint32_t* count, uint32_t* status, uint32_t cap, uint32_t row0,
+                            uint32_t n_valid, uint32_t shards, hipStream_t s) {
+  RARC_REQUIRE(xn, RARC_E_INVALID, "rarc_gemm_f16_select_l2: null row norms");
+  return gemm_f16_select_impl(a, w, m, k, thr, cand, count, status, cap, row0, n_valid, shards, xn, s);
 }
 
 // The same with N columns (a multiple of 256; thr / count / status are [N], cand is [N][cap]): the all-pairs cosine of pairs.hip,

@@ -29,12 +29,37 @@
 // HBM traffic per row: the 2·d_pad bytes of the row, once (PMC: 31.7 GB fetched per search of 30.7 GB of rows).
 // Bound: the MFMA pipe (2·256·n·d_pad flops on the encoder's GEMM, which runs at the board's power limit: 10M x 1536 rows in
 // 8.3 ms where the GEMM alone takes 8.28).
+//
+// Metric "l2" (rarc_search_wide_l2): exact squared-Euclidean top-k on the same machinery.  With dot() the canonical fp32
+// inner product, qn = dot(q, q), xn = dot(x, x) (l2.hip: rarc_row_sqnorms, one fp32 per stored row) and ip = dot(q, x), the answer is
+//     dist = max(0, (qn + xn) - 2 ip)          every operation fp32; 2 ip is exact and the subtraction rounds once, so a
+//                                              contracted FMA gives the same bits
+// ordered by (dist asc, id asc) — faiss's own expansion for batched L2 (norms - 2 GEMM, clamped at 0) with the summation and
+// tie order pinned.  Every pass ranks by the KEY  key = s - xn / 2  (s the approximate inner product: fp32 from the fused GEMM's
+// accumulator — encoder.hip ACT 7 — or the first chunk's fp16 score; xn / 2 exact, one fp32 rounding in the subtraction), largest
+// first: with kappa = ip - xn / 2 in real arithmetic, qn - 2 kappa is the unrounded distance.
+//
+// Exactness.  Let eps_k[q] >= |key - kappa| for every row: the eps of the inner product above plus the subtraction's rounding,
+// 2^-24 (|s| + xn / 2) <= 2^-24 (|q| M + M^2 / 2 + eps), M the largest stored norm.  Let delta[q] >= |dist - max(0, qn - 2 kappa)|:
+// the two roundings of dist, 2^-24 (qn + xn) + 2^-24 (qn + xn + 2 |ip|) (1 + 2^-24) <= 2^-23 (|q| + M)^2 (the clamp is 1-Lipschitz
+// and does not widen it).  If a_k is the k-th best key seen so far, k rows have kappa >= a_k - eps_k, hence
+// dist <= max(0, qn - 2 (a_k - eps_k)) + delta: the k-th smallest dist L is at most that.  A row of the answer has dist <= L
+// (ties included, whatever its id), so qn - 2 kappa <= max(0, qn - 2 a_k + 2 eps_k) + 2 delta, i.e.
+//     kappa >= min(a_k - eps_k, qn / 2) - delta      and      key >= min(a_k - eps_k, qn / 2) - eps_k - delta = thr.
+// Nothing under thr can be in the answer, ever (a_k only rises; thr is rounded DOWN wherever fp32 forms it).  The min with
+// qn / 2 is what the clamp costs: once k rows sit within eps_k of distance 0, rows are only dropped for lying further than
+// 2 delta from it — they may all tie at dist = 0, where the id decides.  The nominees are rescored canonically (ip in the
+// oracle's order, xn as stored, qn canonical from wide_eps_kernel), dist is formed as above and ranked as the 64-bit key
+// (ordered(0 - dist), ~row): largest first = (dist asc, id asc).  A list that fills up flags the query as before.
 #include "rarc_common.h"
 
 bool rarc_gemm_f16_select_takes(int m, int k);   // encoder.hip: the same GEMM with the select in its epilogue (no score matrix)
 int rarc_gemm_f16_select(const uint16_t* a, const uint16_t* w, int m, int k, const float* thr, unsigned long long* cand,
                          uint32_t* count, uint32_t* status, uint32_t cap, uint32_t row0, uint32_t n_valid, uint32_t shards,
                          hipStream_t s);
+int rarc_gemm_f16_select_l2(const uint16_t* a, const uint16_t* w, int m, int k, const float* xn, const float* thr,
+                            unsigned long long* cand, uint32_t* count, uint32_t* status, uint32_t cap, uint32_t row0,
+                            uint32_t n_valid, uint32_t shards, hipStream_t s);   // encoder.hip ACT 7: the key acc - xn[r] / 2
 extern "C" int rarc_enc_gemm_zero_bias(const uint16_t* d_a, const uint16_t* d_w, const uint16_t* d_zero_bias, uint16_t* d_c, int m,
                                        int n, int k, int act, void* stream);
 
@@ -60,6 +85,8 @@ struct WideWs {
   uint32_t* count2;     // [256][WIDE_SHARDS]
   uint64_t* cand;       // [256][cap]
   uint64_t* cand2;      // [256][cap]  (compaction target; the two swap roles)
+  float* qn;            // [256]  metric "l2": canonical |q|^2
+  float* epsd;          // [256]  metric "l2": eps_k + delta (the file header's bound)
 };
 size_t wide_ws_bytes(int d_pad, int cap) {
   return (size_t)WIDE_CHUNK * WIDE_NQ * 2 + 4096 + (size_t)128 * d_pad * 2 + 8 * 4096 + 2 * (size_t)WIDE_NQ * cap * 8;
@@ -74,6 +101,8 @@ WideWs wide_carve(void* base, int d_pad, int cap) {
   w.eps = (float*)b; b += 1024;
   w.count = (uint32_t*)b; b += 8192;
   w.count2 = (uint32_t*)b; b += 8192;
+  w.qn = (float*)b;
+  w.epsd = (float*)(b + 1024);
   b += 8 * 4096 - (2 * 1024 + 2 * 8192);
   w.cand = (uint64_t*)b; b += (size_t)WIDE_NQ * cap * 8;
   w.cand2 = (uint64_t*)b;
@@ -85,9 +114,12 @@ WideWs wide_carve(void* base, int d_pad, int cap) {
 //   query rounding ||q32 - q16||·||d||, both fp32 accumulations (d_pad·2^-23·||q||·||d||, Cauchy-Schwarz over the
 //   |q_i d_i|), the fp16 rounding of the stored score (2^-11·||q||·||d||, + 2^-24 absolute under the normal range), and for
 //   fp32 storage the image's distance rho = qmeta[1] from the rows the canonical score is taken on.
+// L2: eps[q] becomes eps_k, epsd[q] = eps_k + delta and qn_out[q] the canonical |q|^2 (eight chains + tree, lanes 0..7) — see the header.
+template <bool L2>
 __global__ __launch_bounds__(256) void wide_eps_kernel(const float* q32, const uint16_t* q16, int d_pad, int nq,
                                                        float max_norm, float rho, float* eps, float* thr, uint32_t* count,
-                                                       uint32_t* count2, uint32_t* status, uint16_t* zero_bias) {
+                                                       uint32_t* count2, uint32_t* status, uint16_t* zero_bias, float* qn_out,
+                                                       float* epsd) {
   __shared__ double s_red[4][2];
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   double dn = 0.0, qn = 0.0;
@@ -104,13 +136,30 @@ __global__ __launch_bounds__(256) void wide_eps_kernel(const float* q32, const u
   }
   if (lane == 0) { s_red[tid >> 6][0] = dn; s_red[tid >> 6][1] = qn; }
   __syncthreads();
+  float qn_c = 0.f;
+  if (L2 && tid < 8) {
+    for (int m = tid; m < d_pad; m += 8) qn_c = __builtin_fmaf(q32[(size_t)q * d_pad + m], q32[(size_t)q * d_pad + m], qn_c);
+    qn_c = qn_c + __shfl_xor(qn_c, 4, 8);
+    qn_c = qn_c + __shfl_xor(qn_c, 2, 8);
+    qn_c = qn_c + __shfl_xor(qn_c, 1, 8);
+  }
   if (tid == 0) {
     dn = (s_red[0][0] + s_red[1][0]) + (s_red[2][0] + s_red[3][0]);
     qn = (s_red[0][1] + s_red[1][1]) + (s_red[2][1] + s_red[3][1]);
     const double nq2 = sqrt(qn), mn = (double)max_norm;
     const double e = (sqrt(dn) + ((double)d_pad * 1.1920928955078125e-07 + 4.8828125e-04) * nq2) * mn * 1.01 + (double)rho * nq2 * 1.0001 +
                      6.0e-08 + 1e-30;
-    eps[q] = (float)e * 1.0001f;
+    if (L2) {
+      const double u = 5.9604644775390625e-08;   // 2^-24
+      const double e_ip = e * 1.0002;
+      const double e_k = e_ip + u * 1.01 * (nq2 * mn + 0.5 * mn * mn + e_ip) + 1e-36;
+      const double delta = 2.0 * u * 1.01 * (nq2 + mn) * (nq2 + mn) + 1e-36;
+      eps[q] = (float)e_k * 1.0001f;
+      epsd[q] = (float)(e_k + delta) * 1.0001f;
+      qn_out[q] = qn_c;
+    } else {
+      eps[q] = (float)e * 1.0001f;
+    }
     thr[q] = q < nq ? -INFINITY : INFINITY;     // padding queries never nominate anything
     for (int sh = 0; sh < WIDE_SHARDS; ++sh) {
       count[q * WIDE_SHARDS + sh] = 0;
@@ -124,9 +173,12 @@ __global__ __launch_bounds__(256) void wide_eps_kernel(const float* q32, const u
 // One pass over a chunk's scores: thread t of a 32-thread group takes 8 queries of a row (one 16-byte load); a workgroup
 // walks 8 rows per step.  A survivor goes to its query's list with one global atomic (survivors are k per shard plus a
 // margin — and the whole first chunk, which is what sizes it).
+// L2: the candidate's key is score - xn[row] / 2, formed in fp32 (xn: the squared norms of ALL stored rows); no fp16 pre-screen.
+template <bool L2>
 __global__ __launch_bounds__(256) void wide_select_kernel(const uint16_t* __restrict__ scores, uint32_t m_rows, uint32_t row0,
                                                           uint32_t n_valid, const float* __restrict__ thr, uint64_t* cand,
-                                                          uint32_t* count, uint32_t cap, uint32_t* status, uint32_t nq, int first) {
+                                                          uint32_t* count, uint32_t cap, uint32_t* status, uint32_t nq, int first,
+                                                          const float* __restrict__ xn) {
   const int tid = threadIdx.x;
   const int qg = tid & 31;                       // queries [8 qg, 8 qg + 8)
   if (first) {
@@ -138,9 +190,11 @@ __global__ __launch_bounds__(256) void wide_select_kernel(const uint16_t* __rest
       const half8 s8 = *(const half8*)(scores + (size_t)r * WIDE_NQ + 8 * qg);
       const uint32_t sh = r / per;
       const size_t at = (size_t)sh * cap_f + (r - sh * per);
+      float xh = 0.f;
+      if constexpr (L2) xh = 0.5f * xn[row0 + r];
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        if ((uint32_t)(8 * qg + j) < nq) cand[(size_t)(8 * qg + j) * cap + at] = rarc_candkey((float)s8[j], row0 + r);
+        if ((uint32_t)(8 * qg + j) < nq) cand[(size_t)(8 * qg + j) * cap + at] = rarc_candkey(L2 ? (float)s8[j] - xh : (float)s8[j], row0 + r);
     }
     if (blockIdx.x == 0 && (uint32_t)tid < nq)
       for (uint32_t sh = 0; sh < WIDE_SHARDS; ++sh)
@@ -162,10 +216,12 @@ __global__ __launch_bounds__(256) void wide_select_kernel(const uint16_t* __rest
   }
   const bool dead = thr[8 * qg] > 65504.f && thr[8 * qg + 7] > 65504.f;   // (a whole group of padding queries)
   auto take = [&](uint32_t r, const half8& s8) {
+    float xh = 0.f;
+    if constexpr (L2) xh = 0.5f * xn[row0 + r];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      if (s8[j] >= t[j]) {
-        const float s = (float)s8[j];
+      if (L2 || s8[j] >= t[j]) {
+        const float s = L2 ? (float)s8[j] - xh : (float)s8[j];
         const uint32_t q = 8 * qg + j;
         if (s >= thr[q]) {                       // the exact (fp32) threshold decides: the fp16 one only pre-screens
           const uint32_t pos = atomicAdd(&count[q * WIDE_SHARDS + shard], 1u);
@@ -188,7 +244,7 @@ __global__ __launch_bounds__(256) void wide_select_kernel(const uint16_t* __rest
       half_t mx = v[u][0];
 #pragma unroll
       for (int j = 1; j < 8; ++j) mx = v[u][j] > mx ? v[u][j] : mx;
-      if (mx >= tmin) take(r + u * stride, v[u]);
+      if (L2 || mx >= tmin) take(r + u * stride, v[u]);
     }
   }
   for (; r < n_valid; r += stride) {
@@ -261,9 +317,12 @@ __device__ uint32_t wide_kth_largest_each(Each each, uint32_t k, uint32_t* s_his
 // thr[q] = max(thr[q], (k-th best approximate score so far) - 2 eps[q]); the list is copied without what fell under it: the
 // sub-lists are read one after the other (entry L of the query = entry L - first[s] of sub-list s), the survivors dealt
 // round-robin over the target's sub-lists — or laid out flat from its start (flat_out: the last pass, before the finalize).
+// L2: the entries are keys s - xn / 2 and thr[q] = max(thr[q], min(a_k - eps_k, qn / 2) - (eps_k + delta)) (the file header's bound).
+template <bool L2>
 __global__ __launch_bounds__(1024) void wide_tighten_kernel(const uint64_t* __restrict__ cand, uint64_t* __restrict__ cand2,
                                                             uint32_t* count, uint32_t* count2, uint32_t cap, uint32_t k,
-                                                            const float* __restrict__ eps, float* thr, int flat_out) {
+                                                            const float* __restrict__ eps, float* thr, int flat_out,
+                                                            const float* __restrict__ qn, const float* __restrict__ epsd) {
   __shared__ uint32_t s_hist[256];
   __shared__ uint32_t s_pick[2];
   __shared__ uint32_t s_n;
@@ -303,7 +362,16 @@ __global__ __launch_bounds__(1024) void wide_tighten_kernel(const uint64_t* __re
       kth = wide_kth_largest_each([&](auto&& g) { each_key([&](uint64_t key) { g((uint32_t)(key >> 32)); }); }, k, s_hist, s_pick);
     }
     const float a_k = rarc_unordkey(kth);
-    float nt = a_k - 2.0f * eps[q] * 1.000001f;
+    float nt;
+    if constexpr (L2) {
+      float u = a_k - eps[q] * 1.000001f;
+      u = u - fabsf(u) * 1.2e-7f - 1e-37f;         // (every fp32 step rounded down)
+      const float qh = 0.5f * qn[q];
+      u = u < qh ? u : qh;
+      nt = u - epsd[q] * 1.000001f;
+    } else {
+      nt = a_k - 2.0f * eps[q] * 1.000001f;
+    }
     nt = nt - fabsf(nt) * 1.2e-7f - 1e-37f;        // (rounded down: the bound must not be overstated by the subtraction)
     if (nt > t) t = nt;
   }
@@ -363,11 +431,14 @@ __device__ __forceinline__ float wide_canon_dot8(const float* q, const void* __r
 }
 
 // One workgroup per query: canonical scores of its candidates, the k best by (score desc, id asc), written out.
-template <bool F32ROWS>
+// L2: dist = max(0, (qn + xn) - 2 ip) per candidate, ranked as the key (0 - dist, ~row) — largest first = (dist asc, id asc); the
+// scores written out are the distances (+inf beyond the stored rows).
+template <bool F32ROWS, bool L2>
 __global__ __launch_bounds__(1024) void wide_finalize_kernel(const void* __restrict__ rows, int d_pad, const float* __restrict__ q32,
                                                              uint64_t* cand, const uint32_t* count, uint32_t cap, uint32_t k,
                                                              uint32_t nq, int64_t id_base, int64_t* out_ids, float* out_scores,
-                                                             uint32_t* status) {
+                                                             uint32_t* status, const float* __restrict__ xn,
+                                                             const float* __restrict__ qn) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint64_t* s_top = (uint64_t*)smem;                       // [pow2 >= k]
   __shared__ uint32_t s_hist[256];
@@ -389,7 +460,13 @@ __global__ __launch_bounds__(1024) void wide_finalize_kernel(const void* __restr
     for (uint32_t i = threadIdx.x >> 3; i < ((c + 127u) & ~127u); i += blockDim.x >> 3) {
       const bool live = i < c;
       const uint32_t row = live ? rarc_candrow(keys[i]) : 0u;
-      const float s = wide_canon_dot8<F32ROWS>(s_q, rows, row, d_pad, j, stage);
+      float s = wide_canon_dot8<F32ROWS>(s_q, rows, row, d_pad, j, stage);
+      if constexpr (L2) {
+        // 2 ip is exact and the subtraction rounds once: contracted into an FMA or not, the same bits.  0 - dist: +0 stays +0
+        // (one key for distance zero), every other distance changes sign exactly.
+        const float dd = (qn[q] + xn[row]) - 2.0f * s;
+        s = 0.f - (dd > 0.f ? dd : 0.f);
+      }
       if (live && j == 0) keys[i] = rarc_candkey(s, row);
     }
   }
@@ -441,7 +518,7 @@ __global__ __launch_bounds__(1024) void wide_finalize_kernel(const void* __restr
     const bool have = i < kk;
     const uint64_t key = have ? s_top[i] : 0;
     out_ids[(size_t)q * k + i] = have ? id_base + (int64_t)rarc_candrow(key) : -1;
-    out_scores[(size_t)q * k + i] = have ? rarc_candscore(key) : -INFINITY;
+    out_scores[(size_t)q * k + i] = L2 ? (have ? 0.f - rarc_candscore(key) : INFINITY) : (have ? rarc_candscore(key) : -INFINITY);
   }
 }
 
@@ -453,10 +530,12 @@ extern "C" size_t rarc_wide_workspace_bytes(int d_pad, int cand_cap) {
 // d_qblock: written by rarc_prep_queries (q32, q16).  max_norm: the largest stored row norm; rho: fmt 2, >= ||row32 - image16||.
 // d_status: uint32 [256], per-query flag words (RARC_Q_OVERFLOW: re-run with a larger cand_cap; cand_cap >= n_rows cannot
 // overflow).  cand_cap >= max(16384, 2k) rounded up to 256, + 256.
-extern "C" int rarc_search_wide(const void* d_rows, const uint16_t* d_image16, int fmt, int64_t n_rows, int d_pad, float max_norm,
-                                float rho, const void* d_qblock, int nq, int k, int64_t id_base, int64_t* d_out_ids,
-                                float* d_out_scores, uint32_t* d_status, void* d_ws, size_t ws_bytes, int cand_cap, void* stream) {
-  RARC_RANGE();
+// d_xn: null = inner-product scores (rarc_search_wide); else the squared norms of the stored rows (rarc_search_wide_l2)
+template <bool L2>
+static int wide_search_impl(const void* d_rows, const uint16_t* d_image16, int fmt, int64_t n_rows, int d_pad, float max_norm,
+                            float rho, const void* d_qblock, int nq, int k, int64_t id_base, int64_t* d_out_ids,
+                            float* d_out_scores, uint32_t* d_status, void* d_ws, size_t ws_bytes, int cand_cap, const float* d_xn,
+                            void* stream) {
   RARC_REQUIRE(d_rows && d_qblock && d_out_ids && d_out_scores && d_status && d_ws, RARC_E_INVALID, "rarc_search_wide: null pointer");
   RARC_REQUIRE((fmt == 0 && !d_image16) || (fmt == 2 && d_image16), RARC_E_INVALID,
                "rarc_search_wide: fmt 0 (fp16 rows) or 2 (fp32 rows + their fp16 image)");
@@ -480,8 +559,8 @@ extern "C" int rarc_search_wide(const void* d_rows, const uint16_t* d_image16, i
   hipStream_t s = (hipStream_t)stream;
   WideWs w = wide_carve(wsb, d_pad, cand_cap);
   const RarcQb qb = rarc_qb_carve(d_qblock, d_pad);
-  hipLaunchKernelGGL(wide_eps_kernel, dim3(WIDE_NQ), dim3(256), 0, s, qb.q32, qb.q16, d_pad, nq, max_norm, rho, w.eps, w.thr,
-                     w.count, w.count2, d_status, w.zero_bias);
+  hipLaunchKernelGGL(wide_eps_kernel<L2>, dim3(WIDE_NQ), dim3(256), 0, s, qb.q32, qb.q16, d_pad, nq, max_norm, rho, w.eps, w.thr,
+                     w.count, w.count2, d_status, w.zero_bias, w.qn, w.epsd);
   RARC_HIP_CHECK(hipGetLastError());
   const uint16_t* a16 = fmt == 2 ? d_image16 : (const uint16_t*)d_rows;
   uint64_t *cur = w.cand, *other = w.cand2;
@@ -503,16 +582,20 @@ extern "C" int rarc_search_wide(const void* d_rows, const uint16_t* d_image16, i
     static const bool fuse = !(getenv("RARC_WIDE_FUSE") && atoi(getenv("RARC_WIDE_FUSE")) == 0);
     if (fuse && at > 0 && m >= 256 && rarc_gemm_f16_select_takes((int)(m / 256 * 256), d_pad)) {
       const int64_t mf = m / 256 * 256;
-      if ((rc = rarc_gemm_f16_select(a16 + (size_t)at * d_pad, qb.q16, (int)mf, d_pad, w.thr, (unsigned long long*)cur, ccur, d_status,
-                                     (uint32_t)cand_cap, (uint32_t)at, (uint32_t)mf, (uint32_t)WIDE_SHARDS, s)) != RARC_OK)
-        return rc;
+      if (L2)
+        rc = rarc_gemm_f16_select_l2(a16 + (size_t)at * d_pad, qb.q16, (int)mf, d_pad, d_xn + at, w.thr, (unsigned long long*)cur, ccur,
+                                     d_status, (uint32_t)cand_cap, (uint32_t)at, (uint32_t)mf, (uint32_t)WIDE_SHARDS, s);
+      else
+        rc = rarc_gemm_f16_select(a16 + (size_t)at * d_pad, qb.q16, (int)mf, d_pad, w.thr, (unsigned long long*)cur, ccur, d_status,
+                                  (uint32_t)cand_cap, (uint32_t)at, (uint32_t)mf, (uint32_t)WIDE_SHARDS, s);
+      if (rc != RARC_OK) return rc;
       at += mf;
       m -= mf;
       if (m == 0) {
         ++n_chunk;
         if (chunk < fused_max || chunk >= 4 * WIDE_CHUNK || n_chunk % 4 == 0 || at >= n_rows) {   // (every chunk while they still grow: a stale threshold lets chunk/seen x k rows through)
-          hipLaunchKernelGGL(wide_tighten_kernel, dim3(WIDE_NQ), dim3(1024), 0, s, cur, other, ccur, cother, (uint32_t)cand_cap,
-                             (uint32_t)k, w.eps, w.thr, at >= n_rows ? 1 : 0);
+          hipLaunchKernelGGL(wide_tighten_kernel<L2>, dim3(WIDE_NQ), dim3(1024), 0, s, cur, other, ccur, cother, (uint32_t)cand_cap,
+                             (uint32_t)k, w.eps, w.thr, at >= n_rows ? 1 : 0, w.qn, w.epsd);
           RARC_HIP_CHECK(hipGetLastError());
           { uint64_t* t = cur; cur = other; other = t; }
           { uint32_t* t = ccur; ccur = cother; cother = t; }
@@ -547,8 +630,8 @@ extern "C" int rarc_search_wide(const void* d_rows, const uint16_t* d_image16, i
     }
     const uint32_t m_sel = (uint32_t)((m + 127) / 128 * 128);
     const int grid = (int)((m + 7) / 8 < 2048 ? (m + 7) / 8 : 2048);
-    hipLaunchKernelGGL(wide_select_kernel, dim3(grid), dim3(256), 0, s, w.scores, m_sel, (uint32_t)at, (uint32_t)m, w.thr, cur, ccur,
-                       (uint32_t)cand_cap, d_status, (uint32_t)nq, at == 0 ? 1 : 0);
+    hipLaunchKernelGGL(wide_select_kernel<L2>, dim3(grid), dim3(256), 0, s, w.scores, m_sel, (uint32_t)at, (uint32_t)m, w.thr, cur, ccur,
+                       (uint32_t)cand_cap, d_status, (uint32_t)nq, at == 0 ? 1 : 0, d_xn);
     RARC_HIP_CHECK(hipGetLastError());
     at += m;
     // the threshold is raised (and the lists cut back) after every chunk while the chunks still grow, then after every
@@ -556,8 +639,8 @@ extern "C" int rarc_search_wide(const void* d_rows, const uint16_t* d_image16, i
     // third of the chunk's GEMM does
     ++n_chunk;
     if (chunk < WIDE_CHUNK || n_chunk % 4 == 0 || at >= n_rows) {
-      hipLaunchKernelGGL(wide_tighten_kernel, dim3(WIDE_NQ), dim3(1024), 0, s, cur, other, ccur, cother, (uint32_t)cand_cap,
-                         (uint32_t)k, w.eps, w.thr, at >= n_rows ? 1 : 0);
+      hipLaunchKernelGGL(wide_tighten_kernel<L2>, dim3(WIDE_NQ), dim3(1024), 0, s, cur, other, ccur, cother, (uint32_t)cand_cap,
+                         (uint32_t)k, w.eps, w.thr, at >= n_rows ? 1 : 0, w.qn, w.epsd);
       RARC_HIP_CHECK(hipGetLastError());
       { uint64_t* t = cur; cur = other; other = t; }
       { uint32_t* t = ccur; ccur = cother; cother = t; }
@@ -575,20 +658,40 @@ extern "C" int rarc_search_wide(const void* d_rows, const uint16_t* d_image16, i
   if (fmt == 2) {
     static RarcPerDevice attr_done;
     if (size_t& done = attr_done.cur(); !done) {
-      RARC_HIP_CHECK(hipFuncSetAttribute((const void*)wide_finalize_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+      RARC_HIP_CHECK(hipFuncSetAttribute((const void*)wide_finalize_kernel<true, L2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
       done = 1;
     }
-    hipLaunchKernelGGL(wide_finalize_kernel<true>, dim3(WIDE_NQ), dim3(1024), lds, s, d_rows, d_pad, qb.q32, cur, ccur,
-                       (uint32_t)cand_cap, (uint32_t)k, (uint32_t)nq, id_base, d_out_ids, d_out_scores, d_status);
+    hipLaunchKernelGGL((wide_finalize_kernel<true, L2>), dim3(WIDE_NQ), dim3(1024), lds, s, d_rows, d_pad, qb.q32, cur, ccur,
+                       (uint32_t)cand_cap, (uint32_t)k, (uint32_t)nq, id_base, d_out_ids, d_out_scores, d_status, d_xn, w.qn);
   } else {
     static RarcPerDevice attr_done;
     if (size_t& done = attr_done.cur(); !done) {
-      RARC_HIP_CHECK(hipFuncSetAttribute((const void*)wide_finalize_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+      RARC_HIP_CHECK(hipFuncSetAttribute((const void*)wide_finalize_kernel<false, L2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
       done = 1;
     }
-    hipLaunchKernelGGL(wide_finalize_kernel<false>, dim3(WIDE_NQ), dim3(1024), lds, s, d_rows, d_pad, qb.q32, cur, ccur,
-                       (uint32_t)cand_cap, (uint32_t)k, (uint32_t)nq, id_base, d_out_ids, d_out_scores, d_status);
+    hipLaunchKernelGGL((wide_finalize_kernel<false, L2>), dim3(WIDE_NQ), dim3(1024), lds, s, d_rows, d_pad, qb.q32, cur, ccur,
+                       (uint32_t)cand_cap, (uint32_t)k, (uint32_t)nq, id_base, d_out_ids, d_out_scores, d_status, d_xn, w.qn);
   }
   RARC_HIP_CHECK(hipGetLastError());
   return RARC_OK;
+}
+
+extern "C" int rarc_search_wide(const void* d_rows, const uint16_t* d_image16, int fmt, int64_t n_rows, int d_pad, float max_norm,
+                                float rho, const void* d_qblock, int nq, int k, int64_t id_base, int64_t* d_out_ids,
+                                float* d_out_scores, uint32_t* d_status, void* d_ws, size_t ws_bytes, int cand_cap, void* stream) {
+  RARC_RANGE();
+  return wide_search_impl<false>(d_rows, d_image16, fmt, n_rows, d_pad, max_norm, rho, d_qblock, nq, k, id_base, d_out_ids,
+                                 d_out_scores, d_status, d_ws, ws_bytes, cand_cap, nullptr, stream);
+}
+
+// Metric "l2": the arguments of rarc_search_wide plus d_xn, fp32 [n_rows] = rarc_row_sqnorms of the same stored rows.  d_out_scores
+// receives the squared distances, smallest first (+inf, id -1 beyond the stored rows).  The workspace is rarc_search_wide's.
+extern "C" int rarc_search_wide_l2(const void* d_rows, const uint16_t* d_image16, int fmt, int64_t n_rows, int d_pad, float max_norm,
+                                   float rho, const float* d_xn, const void* d_qblock, int nq, int k, int64_t id_base,
+                                   int64_t* d_out_ids, float* d_out_scores, uint32_t* d_status, void* d_ws, size_t ws_bytes,
+                                   int cand_cap, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_xn, RARC_E_INVALID, "rarc_search_wide_l2: null pointer (d_xn: the rows' squared norms, rarc_row_sqnorms)");
+  return wide_search_impl<true>(d_rows, d_image16, fmt, n_rows, d_pad, max_norm, rho, d_qblock, nq, k, id_base, d_out_ids,
+                                d_out_scores, d_status, d_ws, ws_bytes, cand_cap, d_xn, stream);
 }

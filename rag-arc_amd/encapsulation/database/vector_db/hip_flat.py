@@ -1,11 +1,13 @@
 """HBM-resident exact vector store — the MI355X answer to the reference's
 "TODO: needs GPU support to go faster" (encapsulation/database/vector_db/VectorStore_Faiss.py:14).
 
-Same behaviour as FaissVectorStore for index_type "flat" with metric "cosine" or "ip"
+Same behaviour as FaissVectorStore for index_type "flat" with metric "cosine", "ip" or "l2"
 (VectorStore_Faiss.py:65-512): embed -> fp32 -> (L2-normalise) -> add; query -> fp32 ->
 (normalise) -> k = min(k, ntotal) -> search -> (Document, float(score)).  Rows are stored as fp16
 in HBM and scored by the HIP kernels behind `FlatIndexF16`; scores are the canonical fp32 inner
-products defined in DESIGN.md, ties ordered by insertion index.  IVF / HNSW / L2 are out of scope
+products defined in DESIGN.md, ties ordered by insertion index.  Metric "l2" (faiss.IndexFlatL2) returns squared
+Euclidean distances, nearest first, formed from three canonical inner products (fp16 / fp32 rows, on the
+chunked-GEMM path at every d and k — slower than the inner-product scans at d <= 1024).  IVF / HNSW are out of scope
 (SURVEY.md §8 a4).  There is no CPU fallback: without a GPU the default engine raises.
 """
 import logging
@@ -381,8 +383,13 @@ class HipFlatVectorStore(VectorStore):
         self.storage = storage
         if index_type != "flat":
             raise ValueError(f"unsupported index type: {index_type} (exact flat scan only)")
-        if metric not in ("cosine", "ip"):
+        if metric not in ("cosine", "ip", "l2"):
             raise ValueError(f"unsupported metric: {metric}")
+        if metric == "l2" and storage == "f8":
+            from ....hip.binding import RarcUnsupported
+
+            raise RarcUnsupported("metric 'l2' reads fp16 / fp32 rows: use storage 'f16' or 'f32' (fp8 rows answer metric "
+                                  "'cosine' / 'ip')")
         self.embedding = embedding
         self.metric, self.normalize_L2, self.index_type, self.device = metric, normalize_L2, index_type, device
         self._engine_factory = engine_factory or _default_engine
@@ -405,6 +412,8 @@ class HipFlatVectorStore(VectorStore):
 
     # ------------------------------------------------------------------ helpers
     def _engine_metric(self) -> str:
+        if self.metric == "l2":        # (normalize_L2 is a flag of the engine's there: _make_engine)
+            return "l2"
         return "cosine" if (self.metric == "cosine" or self.normalize_L2) else "ip"
 
     @property
@@ -857,6 +866,8 @@ class HipFlatVectorStore(VectorStore):
         return [self.docstore[i] for i in ids if i in self.docstore]
 
     def _select_relevance_score_fn(self):
+        if self.metric == "l2":            # (before normalize_L2, as the reference: VectorStore_Faiss.py:423-430)
+            return self._euclidean_relevance_score_fn
         if self.metric == "cosine" or self.normalize_L2:
             return self._cosine_relevance_score_fn
         if self.metric == "ip":
@@ -865,7 +876,11 @@ class HipFlatVectorStore(VectorStore):
 
     def _make_engine(self, dim: int):
         if self._engine_factory is _default_engine:
-            return _default_engine(dim, self._engine_metric(), self.device, self.storage, **self._engine_kwargs)
+            extra = {"normalize": True} if (self.metric == "l2" and self.normalize_L2) else {}
+            return _default_engine(dim, self._engine_metric(), self.device, self.storage, **self._engine_kwargs, **extra)
+        if self.metric == "l2" and self.normalize_L2:
+            raise ValueError("metric 'l2' with normalize_L2 needs the default engine (a custom engine factory takes no "
+                             "normalisation flag)")
         if self.storage == "f16":  # (custom factories keep their three-argument signature)
             return self._engine_factory(dim, self._engine_metric(), self.device)
         return self._engine_factory(dim, self._engine_metric(), self.device, self.storage)

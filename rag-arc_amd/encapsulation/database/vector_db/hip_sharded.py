@@ -170,6 +170,11 @@ class _PendingShard:
 class HipShardedFlatVectorStore(HipFlatVectorStore):
     def __init__(self, embedding, *args: Any, group=None, merge_fn: Optional[Callable] = None, **kwargs: Any):
         kwargs["coalesce"] = False        # SPMD: see the module docstring
+        if (args[0] if args else kwargs.get("metric", "cosine")) == "l2":
+            from ....hip.binding import RarcUnsupported
+
+            raise RarcUnsupported("metric 'l2' is answered by the one-GPU store (HipFlatVectorStore): the sharded store's merge "
+                                  "orders by score descending")
         super().__init__(embedding, *args, **kwargs)
         self._group, self._merge_fn = group, merge_fn
 

@@ -197,6 +197,9 @@ SIGNATURES = {
     "rarc_wide_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rarc_search_wide": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_float, c_void_p, c_int, c_int, c_int64,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "rarc_row_sqnorms": (c_int, [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_void_p]),
+    "rarc_search_wide_l2": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_float, c_void_p, c_void_p, c_int, c_int,
+                                    c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "rarc_similar_pairs_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "rarc_similar_pairs": (c_int, [c_void_p, c_int64, c_int64, c_int, ctypes.c_double, c_void_p, c_size_t, c_int, c_void_p, c_void_p,
                                    c_int64, c_void_p, c_void_p, c_void_p]),

@@ -185,6 +185,10 @@ class FlatIndexF16:
     metric "cosine": rows and queries are L2-normalised in fp32 before use (faiss.normalize_L2);
     metric "ip": raw inner product.  Returned scores are the canonical fp32 inner products of the
     fp32 query with the stored fp16 rows; ties are ordered by id ascending.
+    metric "l2" (faiss.IndexFlatL2): squared Euclidean distances max(0, (|q|^2 + |x|^2) - 2 q.x) of three canonical fp32
+    inner products, smallest first, ties by id ascending; `normalize=True` normalises rows and queries first (the
+    reference's normalize_L2 + IndexFlatL2).  Every L2 search takes the chunked-GEMM path (csrc/wide.hip), whatever d and k
+    are; fp16 / fp32 rows, d_pad <= 4096, k <= 8192.  `normalize` defaults to what the metric implies (cosine: True).
     """
 
     # rows live in a virtual-memory arena that grows in place (DeviceArena) unless told otherwise: measured on the part,
@@ -194,9 +198,21 @@ class FlatIndexF16:
 
     def __init__(self, dim: int, metric: str = "cosine", device: int = 0, capacity: int = 0,
                  id_base: int = 0, cand_cap: int = 131072, scan: str = "auto", storage: str = "f16",
-                 shadow: bool = False, growable: Optional[bool] = None, max_rows: int = 0):
-        if metric not in ("cosine", "ip"):
+                 shadow: bool = False, growable: Optional[bool] = None, max_rows: int = 0, normalize: Optional[bool] = None):
+        if metric not in ("cosine", "ip", "l2"):
             raise ValueError(f"unsupported metric: {metric}")
+        if metric == "cosine" and normalize is not None and not normalize:
+            raise ValueError("metric 'cosine' normalises rows and queries: use metric 'ip' for raw inner products")
+        if metric == "l2":
+            # refused before anything is loaded or launched, naming what does answer ("What the backend refuses")
+            if storage == "f8":
+                raise B.RarcUnsupported("metric 'l2' reads fp16 / fp32 rows (the GEMM path, csrc/wide.hip): store the rows as 'f16' or "
+                                        "'f32' (fp8 rows answer metric 'cosine' / 'ip')")
+            if shadow:
+                raise B.RarcUnsupported("metric 'l2' has no int8 prefilter: shadow=True (the int8 image) goes with metric 'cosine' / "
+                                        "'ip'; use storage 'f16' or 'f32' without it")
+            if scan != "auto":
+                raise B.RarcUnsupported("metric 'l2' takes the GEMM path only: leave scan='auto'")
         if dim <= 0:
             raise ValueError("dim must be positive")
         if storage not in ("f16", "f8", "f32"):
@@ -216,7 +232,7 @@ class FlatIndexF16:
         limit = 768 if scan == "mfma16" else 1024
         # rows beyond 1024 padded dimensions (up to 4096: the reference's OpenAI embeddings are 1536- / 3072-d) take the
         # WIDE path — score GEMM in chunks + select + canonical finalize (csrc/wide.hip) — as does k beyond 1024
-        self.wide = self.d_pad > 1024
+        self.wide = self.d_pad > 1024 or metric == "l2"
         if self.wide and (scan != "auto" or storage == "f8" or shadow or self.d_pad > B.WIDE_MAX_DPAD):
             raise B.RarcUnsupported(f"dim {dim} pads to {self.d_pad}: rows wider than 1024 take the wide path (storage 'f16' or "
                                     f"'f32', scan='auto', no shadow image, at most {B.WIDE_MAX_DPAD} padded dimensions)")
@@ -227,6 +243,9 @@ class FlatIndexF16:
         # "auto": q8 from AUTO_Q8_ROWS rows up (and always beyond 768 dims), mfma16 below
         self.scan = scan
         self.metric = metric
+        # rows and queries L2-normalised on the way in: what metric "cosine" means, and a flag of its own for metric "l2"
+        self.normalize = (metric == "cosine") if normalize is None else bool(normalize)
+        self._xn = None   # metric "l2": torch.float32 [capacity], canonical |row|^2 of the stored rows (rarc_row_sqnorms)
         self.device = self.torch.device("cuda", device)
         self.id_base = int(id_base)
         self.cand_cap = int(cand_cap)
@@ -296,6 +315,11 @@ class FlatIndexF16:
             if self._image16 is not None and self.ntotal:
                 ni[: self.ntotal].copy_(self._image16[: self.ntotal])
             self._image16 = ni
+        if self.metric == "l2":
+            nx = t.zeros(cap, dtype=t.float32, device=self.device)
+            if self._xn is not None and self.ntotal:
+                nx[: self.ntotal].copy_(self._xn[: self.ntotal])
+            self._xn = nx
         self._fit_qmeta()
 
     def _arena_view(self, name: str, row_bytes: int, cap: int, dtype, cols: Optional[int]):
@@ -344,8 +368,13 @@ class FlatIndexF16:
             self._rowscale[(had if from_arena else self.ntotal):].fill_(1.0)     # rows not yet written: scale 1, as t.ones() gave
         if self.storage == "f32":
             self._image16 = adopt("image16", self.d_pad * 2, t.float16, self.d_pad, self._image16)
+        if self.metric == "l2":
+            if self._xn is not None and self._xn.shape[0] < self.ntotal:
+                self._xn = None          # (behind rows adopted without a copy: recomputed by _update_xn)
+            self._xn = adopt("xn", 4, t.float32, None, self._xn)
         # every buffer covers the same rows: the smallest backing decides
-        n = min(x.shape[0] for x in (self._rows, self._shadow, self._rowscale, self._image16) if x is not None)
+        n = min(x.shape[0] for x in (self._rows, self._shadow, self._rowscale, self._image16, self._xn) if x is not None)
+        self._xn = None if self._xn is None else self._xn[:n]
         self._rows = self._rows[:n]
         self._shadow = None if self._shadow is None else self._shadow[:n]
         self._rowscale = None if self._rowscale is None else self._rowscale[:n]
@@ -355,7 +384,7 @@ class FlatIndexF16:
         """HBM held by the row buffers: {'live': bytes of the stored rows, 'backed': bytes physically mapped / allocated}."""
         esz = {"f8": 1, "f16": 2, "f32": 4}[self.storage]
         per_row = self.d_pad * esz + (self.d_pad if self.shadow else 0) + (4 if self.storage == "f8" else 0) \
-            + (2 * self.d_pad if self.storage == "f32" else 0)
+            + (2 * self.d_pad if self.storage == "f32" else 0) + (4 if self.metric == "l2" else 0)
         if self._arenas:
             backed = sum(a.mapped for a in self._arenas.values())
         else:
@@ -381,6 +410,8 @@ class FlatIndexF16:
 
     def _requant(self, first_row: int) -> None:
         """(Re)compute tile scales + residual bound for the tiles touched by rows [first_row, ntotal)."""
+        if self.metric == "l2":
+            self._update_xn(first_row)
         if self.wide:
             return            # no int8 prefilter over wide rows: nothing to keep up to date
         self._fit_qmeta()
@@ -406,6 +437,23 @@ class FlatIndexF16:
             return
         B.check(self.lib.rarc_quant_meta_f16(self._rows.data_ptr(), self.ntotal, self.d_pad, int(first_row),
                                              self._qmeta.data_ptr(), self._stream()), "rarc_quant_meta_f16")
+
+    def _update_xn(self, first_row: int) -> None:
+        """metric "l2": xn[r] = canonical |row r|^2 for the rows [first_row, ntotal) — derived data, recomputed behind every
+        change of the rows (appended rows, from the first hole after a removal, everything after a load), on the stream the
+        change itself was enqueued on (so behind _fence_contexts, like the rows)."""
+        t = self.torch
+        if self._xn is None or self._xn.shape[0] < self.ntotal:
+            # rows adopted without a copy (add_rows_f16): a plain array of their capacity, everything recomputed
+            self._xn = t.zeros(max(int(self._rows.shape[0]), self.ntotal), dtype=t.float32, device=self.device)
+            first_row = 0
+        B.check(self.lib.rarc_row_sqnorms(self._rows.data_ptr(), 2 if self.storage == "f32" else 0, self.ntotal, self.d_pad,
+                                          int(first_row), self._xn.data_ptr(), self._stream()), "rarc_row_sqnorms")
+
+    @property
+    def row_sqnorms(self):
+        """metric "l2": the squared norms of the stored rows as a torch view [ntotal] (fp32), None otherwise."""
+        return None if self._xn is None else self._xn[: self.ntotal]
 
     def _stream(self):
         return self.torch.cuda.current_stream(self.device).cuda_stream
@@ -473,7 +521,7 @@ class FlatIndexF16:
 
     def _prep(self, q, k: int = 100, force_q8: bool = False) -> None:
         """rarc_prep_queries into the shared query block (caller holds the lock)."""
-        norm = 1 if self.metric == "cosine" else 0
+        norm = 1 if self.normalize else 0
         qm = self._qmeta.data_ptr() if ((force_q8 or self._use_q8(k)) and self._qmeta is not None) else 0
         B.check(self.lib.rarc_prep_queries(q.data_ptr(), q.shape[1], q.shape[0], self.dim, self.d_pad, norm,
                                            max(self.max_norm, 1.0) if norm else self.max_norm, qm,
@@ -512,18 +560,18 @@ class FlatIndexF16:
                 B.check(self.lib.rarc_ingest_f8(x.data_ptr(), x.shape[1], dst.data_ptr(), self.d_pad,
                                                 self._rowscale[self.ntotal: self.ntotal + n].data_ptr(),
                                                 norm2.data_ptr(), n, self.dim,
-                                                1 if self.metric == "cosine" else 0, self._stream()),
+                                                1 if self.normalize else 0, self._stream()),
                         "rarc_ingest_f8")
             elif self.storage == "f32":
                 B.check(self.lib.rarc_ingest_f32(x.data_ptr(), x.shape[1], dst.data_ptr(),
                                                  self._image16[self.ntotal: self.ntotal + n].data_ptr(), self.d_pad,
                                                  norm2.data_ptr(), n, self.dim,
-                                                 1 if self.metric == "cosine" else 0, self._stream()),
+                                                 1 if self.normalize else 0, self._stream()),
                         "rarc_ingest_f32")
             else:
                 B.check(self.lib.rarc_ingest_f16(x.data_ptr(), x.shape[1], dst.data_ptr(), self.d_pad,
                                                  norm2.data_ptr(), n, self.dim,
-                                                 1 if self.metric == "cosine" else 0, self._stream()),
+                                                 1 if self.normalize else 0, self._stream()),
                         "rarc_ingest_f16")
             self.max_norm = max(self.max_norm, float(norm2.max().sqrt().item()))
             old = self.ntotal
@@ -827,7 +875,7 @@ class FlatIndexF16:
 
     def search(self, queries, k: int, repair: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """index.search: returns (scores fp32 [nq][k], ids int64 [nq][k]) like faiss (D, I);
-        entries beyond ntotal are (-inf, -1)."""
+        entries beyond ntotal are (-inf, -1).  Metric "l2": squared distances, ascending; (+inf, -1) beyond ntotal."""
         if k < 1:
             raise ValueError("k must be >= 1")
         if repair and self.ntotal and not self._takes_wide_path(k):
@@ -873,7 +921,7 @@ class FlatIndexF16:
             nq = q.shape[0]
             if self.ntotal == 0:        # an empty index answers (-1, -inf) like faiss; no kernel has anything to read
                 return (t.full((nq, k), -1, dtype=t.int64, device=self.device),
-                        t.full((nq, k), float("-inf"), dtype=t.float32, device=self.device))
+                        t.full((nq, k), float("inf" if self.metric == "l2" else "-inf"), dtype=t.float32, device=self.device))
             out_ids = t.empty((nq, k), dtype=t.int64, device=self.device)
             out_sc = t.empty((nq, k), dtype=t.float32, device=self.device)
             for s in range(0, nq, B.MAX_QUERIES):
@@ -908,7 +956,7 @@ class FlatIndexF16:
         t = self.torch
         nq = q.shape[0]
         self._ensure_qbuf()
-        norm = 1 if self.metric == "cosine" else 0
+        norm = 1 if self.normalize else 0
         mn = max(self.max_norm, 1.0) if norm else self.max_norm
         stream = self._stream()
         # metric "ip" takes rows and queries of any scale, and the wide path keeps its first chunk's scores as fp16 (finite by
@@ -917,8 +965,13 @@ class FlatIndexF16:
         # multiplied by its inverse (exact) — an infinite first-chunk score would set an infinite threshold and drop every
         # later row.  Cosine scores are at most 1: no read-back on that path.
         unscale = 1.0
+        l2 = self.metric == "l2"
         if not norm:
             bound = float(q.norm(dim=1).max().item()) * float(self.max_norm) * 1.01
+            if bound >= 32768.0 and l2:
+                # (a distance is not linear in q: the power-of-two scaling below does not carry over)
+                raise B.RarcUnsupported(f"metric 'l2': |q| * max |row| = {bound:.4g} is beyond the fp16 range of the first chunk's "
+                                        "scores (2^15): scale the vectors down, or use normalize=True")
             if bound >= 32768.0:
                 e = int(np.ceil(np.log2(bound / 32768.0))) + 1
                 q, unscale = q * (2.0 ** -e), 2.0 ** e
@@ -936,10 +989,17 @@ class FlatIndexF16:
             if getattr(self, "_wide_ws", None) is None or self._wide_ws.numel() < nbytes:
                 self._wide_ws = None
                 self._wide_ws = t.empty(nbytes, dtype=t.uint8, device=self.device)
-            B.check(self.lib.rarc_search_wide(self._rows.data_ptr(), image, fmt, self.ntotal, self.d_pad, mn, rho,
-                                              self._qbuf["qblock"].data_ptr(), nq, k, self.id_base, out_ids.data_ptr(),
-                                              out_sc.data_ptr(), status.data_ptr(), self._wide_ws.data_ptr(),
-                                              self._wide_ws.numel(), cap, stream), "rarc_search_wide")
+            if l2:
+                B.check(self.lib.rarc_search_wide_l2(self._rows.data_ptr(), image, fmt, self.ntotal, self.d_pad, mn, rho,
+                                                     self._xn.data_ptr(), self._qbuf["qblock"].data_ptr(), nq, k, self.id_base,
+                                                     out_ids.data_ptr(), out_sc.data_ptr(), status.data_ptr(),
+                                                     self._wide_ws.data_ptr(), self._wide_ws.numel(), cap, stream),
+                        "rarc_search_wide_l2")
+            else:
+                B.check(self.lib.rarc_search_wide(self._rows.data_ptr(), image, fmt, self.ntotal, self.d_pad, mn, rho,
+                                                  self._qbuf["qblock"].data_ptr(), nq, k, self.id_base, out_ids.data_ptr(),
+                                                  out_sc.data_ptr(), status.data_ptr(), self._wide_ws.data_ptr(),
+                                                  self._wide_ws.numel(), cap, stream), "rarc_search_wide")
             flagged = bool((status[:nq] != 0).any().item())
             self.last_wide_cap = cap          # (diagnostics: the capacity this batch was answered at)
             if not flagged:
@@ -1199,7 +1259,7 @@ class FlatIndexF16:
                                              ws.data_ptr(), ws.numel(), stream), "rarc_repair_f16")
 
     def _bins(self, q) -> Tuple[float, float]:
-        if self.metric == "cosine":
+        if self.normalize:
             return -1.0, 1.0
         bound = float(q.norm(dim=1).max().item()) * max(self.max_norm, 1e-30) * 1.001
         return -bound, bound
@@ -1221,7 +1281,7 @@ class FlatIndexF16:
         kp = k if self._use_q8(k) else self.kprime_for(k)
         rows_ptr = self._rows.data_ptr() if self._rows is not None else 0
         qm = self._qmeta.data_ptr() if (self._use_q8(k) and self._qmeta is not None and self.ntotal) else 0
-        norm = 1 if self.metric == "cosine" else 0
+        norm = 1 if self.normalize else 0
         fmt, aux = 0, 0
         if self.storage == "f8":
             fmt, aux = 1, (self._rowscale.data_ptr() if self._rowscale is not None else 0)

@@ -50,6 +50,11 @@ class ShardedFlatSearch:
         import torch
         import torch.distributed as dist
 
+        if getattr(local_index, "metric", None) == "l2":
+            from .binding import RarcUnsupported
+
+            raise RarcUnsupported("metric 'l2' is answered by one FlatIndexF16 (one GPU): the sharded merge orders by score "
+                                  "descending, distances are ranked ascending")
         self.torch, self.dist = torch, dist
         self.local = local_index
         self.group = group
