@@ -286,7 +286,10 @@ def score_rows_f16(corpus_u16: np.ndarray, qv: np.ndarray, rows: np.ndarray) -> 
 
 
 def topk_merge(ids: np.ndarray, scores: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
-    """Merge [G][nq][k] per-shard results into [nq][k]: score desc, id asc; id -1 entries ignored."""
+    """Merge [G][nq][k] per-shard results into [nq][k]: score desc, id asc; id -1 entries ignored.
+    Scores are ordered as a search orders them (ordkey in rarc_oracle.c: the sign-magnitude bit pattern), so +0.0 ranks
+    ABOVE -0.0 whatever the ids: merging shard answers must equal searching the whole, and a search never compares the
+    two zeros equal.  For every other pair of non-NaN scores this is the numeric order."""
     G, nq, kk = ids.shape
     I = np.transpose(ids, (1, 0, 2)).reshape(nq, G * kk)
     S = np.transpose(scores, (1, 0, 2)).reshape(nq, G * kk).astype(np.float32)
@@ -295,7 +298,9 @@ def topk_merge(ids: np.ndarray, scores: np.ndarray, k: int) -> Tuple[np.ndarray,
     for q in range(nq):
         valid = I[q] >= 0
         ii, ss = I[q][valid], S[q][valid]
-        order = np.lexsort((ii, -ss.astype(np.float64)))[:k]
+        bits = ss.view(np.uint32).astype(np.int64)
+        key = np.where(bits & 0x80000000, 0xFFFFFFFF - bits, bits | 0x80000000)
+        order = np.lexsort((ii, -key))[:k]
         out_i[q, : order.size] = ii[order]
         out_s[q, : order.size] = ss[order]
     return out_i, out_s

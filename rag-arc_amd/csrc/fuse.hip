@@ -2,13 +2,16 @@
 //   rarc_rrf_fuse      RRFusion.fuse                 core/utils/Fusion.py:45-76
 //   rarc_rerank_order  Qwen3Reranker score -> order  core/rerank/Reranker_Qwen3.py:41-49, :70-74
 //
-// Both are tiny per-query problems (<= a few hundred items); one workgroup per query, O(n^2)
+// Both are small per-query problems (usually a few hundred items, at most 4096); one workgroup per query, O(n^2)
 // all-pairs in LDS.  What matters here is bit-exactness, not bandwidth:
 //   * RRF adds 1.0/(k + rank) in fp64 in the reference's order: lists in order, positions in
 //     order, per key (Python float += is fp64; `sorted(..., reverse=True)` is stable, so ties
 //     keep first-insertion order).
 //   * rerank: p_yes = exp(log_softmax([z_no, z_yes])[1]) through fp16 tensors, then Python's
-//     stable sort descending (ties keep retrieval order).
+//     stable sort descending (ties keep retrieval order).  A NaN p_yes — (inf, inf) or (-inf, -inf) logits, which is
+//     what a pair beyond +-65504 becomes in fp16, or a NaN logit — ranks below every number and NaNs keep retrieval
+//     order among themselves (oracle.stable_desc_order: a stable argsort of -s puts NaN last).  The score written out
+//     stays NaN; only the order key is replaced.  out_perm is a permutation of [0, n) for every input.
 #include "rarc_common.h"
 
 constexpr int RRF_MAX_ITEMS = 4096;
@@ -150,15 +153,18 @@ __global__ __launch_bounds__(256) void rarc_rerank_kernel(const half_t* z_no, co
     const half_t ls = (half_t)((zy - m) - logf(sum));  // log_softmax output tensor is fp16
     const half_t pr = (half_t)expf((float)ls);         // .exp() on the fp16 tensor
     out_scores[(size_t)b * n + i] = pr;
-    s_p[i] = (float)pr;
+    const float pf = (float)pr;
+    s_p[i] = pf == pf ? pf : -INFINITY;   // the ORDER key: NaN below every number (p_yes itself is never below 0)
   }
   __syncthreads();
+  // position = #{u ahead of i} under the total order (key desc, index asc): a bijection onto [0, n), so every slot of
+  // out_perm is written exactly once — which needs NO NaN among the keys (a NaN compares false both ways)
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
     const float s = s_p[i];
     int pos = 0;
     for (int u = 0; u < n; ++u) {
       const float su = s_p[u];
-      pos += (su > s) || (su == s && u < i);
+      pos += (int)(su > s) | ((int)(su == s) & (int)(u < i));
     }
     out_perm[(size_t)b * n + pos] = i;
   }
@@ -192,7 +198,7 @@ __global__ __launch_bounds__(256) void rarc_mmr_kernel(const float* cand, int64_
   __shared__ double s_maxsim[MMR_MAX_N];
   __shared__ int32_t s_taken[MMR_MAX_N];
   __shared__ double s_red[256];
-  __shared__ int32_t s_best;
+  __shared__ int32_t s_best, s_first;
   const int tid = threadIdx.x;
   double* e = work;                 // [n][d] widened (normalised) candidates
   double* qn = work + (size_t)n * d;  // [d]
@@ -226,9 +232,10 @@ __global__ __launch_bounds__(256) void rarc_mmr_kernel(const float* cand, int64_
   int last = 0;
   for (int step = 1; step < k && step < n; ++step) {
     double best = -INFINITY;
-    int best_i = 0x7fffffff;
+    int best_i = 0x7fffffff, first_i = 0x7fffffff;
     for (int i = tid; i < n; i += blockDim.x) {
       if (s_taken[i]) continue;
+      first_i = min(first_i, i);
       double s = 0.0;
       for (int m = 0; m < d; ++m) s += e[(size_t)last * d + m] * e[(size_t)i * d + m];
       const double mx = s > s_maxsim[i] ? s : s_maxsim[i];
@@ -243,11 +250,15 @@ __global__ __launch_bounds__(256) void rarc_mmr_kernel(const float* cand, int64_
       for (int t = 0; t < (int)blockDim.x; ++t) b = s_red[t] > b ? s_red[t] : b;
       s_red[0] = b;
       s_best = 0x7fffffff;
+      s_first = 0x7fffffff;
     }
     __syncthreads();
     if (best_i != 0x7fffffff && best == s_red[0]) atomicMin(&s_best, best_i);  // the lowest index among equal scores
+    if (first_i != 0x7fffffff) atomicMin(&s_first, first_i);
     __syncthreads();
-    last = s_best;
+    // nothing left compares above -inf (NaN values: a zero vector under `normalize`): the lowest remaining index, never
+    // an index outside [0, n)
+    last = s_best != 0x7fffffff ? s_best : s_first;
     if (tid == 0) { out[step] = last; s_taken[last] = 1; }
     __syncthreads();
   }

@@ -82,6 +82,8 @@ class ShardedFlatSearch:
         t = self.torch
         lib = B.load_library()
         G, nq, kk = ids.shape
+        if k != kk:   # the kernel writes kk entries per query
+            raise ValueError("merge width must equal the per-shard list width")
         out_i = t.empty((nq, k), dtype=t.int64, device=ids.device)
         out_s = t.empty((nq, k), dtype=t.float32, device=ids.device)
         B.check(lib.rarc_topk_merge(ids.contiguous().data_ptr(), scores.contiguous().data_ptr(), G, nq, kk,
