@@ -126,6 +126,10 @@ int rarc_quant_meta_f16(const uint16_t* d_corpus_f16, int64_t n_rows, int d_pad,
  */
 int rarc_debug_q8_scores(const uint16_t* d_corpus_f16, int64_t n_rows, int d_pad, const float* d_qmeta,
                          const void* d_qblock, int nq, float* d_out, void* stream);
+/* The same for fp8 rows (d_qmeta from rarc_quant_meta_f8, d_pad a multiple of 256): the scan's fp8 quantisation with the
+ * per-row multipliers of the tile metadata.  Same limits; not used by any search. */
+int rarc_debug_q8_scores_f8(const uint8_t* d_corpus_f8, int64_t n_rows, int d_pad, const float* d_qmeta,
+                            const void* d_qblock, int nq, float* d_out, void* stream);
 
 /*
  * Query preparation: fp32 queries [nq][ld_in] -> the "query block" the search reads:

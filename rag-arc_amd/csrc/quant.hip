@@ -334,3 +334,41 @@ extern "C" int rarc_debug_q8_scores(const uint16_t* d_corpus_f16, int64_t n_rows
   RARC_HIP_CHECK(hipGetLastError());
   return RARC_OK;
 }
+
+// fp8 rows: the same matrix with the scan's fp8 quantisation — d8 = rarc_quant8_chunk_f8(bytes, mul_r) with the row's multiplier
+// from the tile's metadata, dequantised by the tile's 1/s_t.  Same shape and limits as rarc_debug_q8_scores.
+__global__ __launch_bounds__(256) void rarc_q8_scores_f8_kernel(const uint4* __restrict__ corpus, int d_pad,
+                                                                uint32_t n_rows, const float* __restrict__ meta,
+                                                                const int8_t* __restrict__ q8,
+                                                                const float* __restrict__ qinv, int nq,
+                                                                float* __restrict__ out) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  const int q = blockIdx.y;
+  if (r >= n_rows || q >= nq) return;
+  const float* mt = meta + RARC_QMETA_HDR + RARC_QMETA_F8_STRIDE * (size_t)(r / 32);
+  const float tinv = mt[1];
+  const half_t mul = (half_t)mt[2 + (r & 31)];  // fp16-representable by construction: the conversion is exact
+  const uint4* row = corpus + (size_t)r * (d_pad / 16);
+  const int8_t* qp = q8 + (size_t)q * d_pad;
+  int acc = 0;
+  for (int c = 0; c < d_pad / 16; ++c) {
+    const uint4 o = rarc_quant8_chunk_f8(row[c], mul);
+    const uint32_t w[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc += (int)(int8_t)(w[e >> 2] >> (8 * (e & 3))) * (int)qp[16 * c + e];
+  }
+  out[(size_t)q * n_rows + r] = (float)acc * (qinv[q] * tinv);
+}
+
+extern "C" int rarc_debug_q8_scores_f8(const uint8_t* d_corpus_f8, int64_t n_rows, int d_pad, const float* d_qmeta,
+                                       const void* d_qblock, int nq, float* d_out, void* stream) {
+  RARC_REQUIRE(d_corpus_f8 && d_qmeta && d_qblock && d_out && n_rows > 0 && n_rows <= (1 << 22) && nq >= 1 &&
+                   nq <= RARC_MAX_QUERIES && d_pad > 0 && d_pad % RARC_DIM_ALIGN_F8 == 0,
+               RARC_E_INVALID, "rarc_debug_q8_scores_f8: bad arguments");
+  const RarcQb qb = rarc_qb_carve(d_qblock, d_pad);
+  hipLaunchKernelGGL(rarc_q8_scores_f8_kernel, dim3((unsigned)((n_rows + 255) / 256), (unsigned)nq), dim3(256), 0,
+                     (hipStream_t)stream, (const uint4*)d_corpus_f8, d_pad, (uint32_t)n_rows, d_qmeta, qb.q8, qb.qinv,
+                     nq, d_out);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}

@@ -550,6 +550,7 @@ class FlatIndexF16:
             n = x.shape[0]
             if n == 0:
                 return
+            self._refuse_rows_without_image(x)
             if self._rows is None or self.ntotal + n > self._rows.shape[0]:
                 # an arena grows in place, slab by slab: ask for what is needed; a plain buffer is reallocated and copied:
                 # double it so that a stream of adds copies O(log) times
@@ -578,6 +579,35 @@ class FlatIndexF16:
             self.ntotal += n
             self._version += 1
             self._requant(old)
+
+    FP16_IMAGE_LIMIT = 65520.0     # the smallest magnitude that rounds to infinity as an fp16
+
+    def _refuse_rows_without_image(self, x) -> None:
+        """fp32 storage keeps the rows as they come, but every scan reads their fp16 IMAGE, and rho — the distance between the
+        two that the error bounds carry — only covers a finite one.  Rows that are not normalised on the way in (metric "ip",
+        or "l2" without normalize) may hold an element the image turns into an infinity: refused here, before anything is
+        written or launched on the rows (one reduction over the block that is being added)."""
+        if self.storage != "f32" or self.normalize or x.numel() == 0:
+            return
+        amax = float(x.abs().max().item())
+        if not amax < self.FP16_IMAGE_LIMIT:
+            raise B.RarcUnsupported(
+                f"storage 'f32' with metric '{self.metric}': a row element of magnitude {amax:.6g} has no finite fp16 image (the scan "
+                f"reads one; elements must stay below {self.FP16_IMAGE_LIMIT:.0f}).  Scale rows and queries down by a common power "
+                "of two (inner products scale with it exactly), or use metric 'cosine' / normalize=True, which takes rows of "
+                "any scale")
+
+    def _refuse_queries_without_fp16(self, q) -> None:
+        """Narrow path: the scans read an fp16 copy of the queries (q16 in the query block) and the error bounds carry its
+        distance from them — infinite for an element of 65520 or more, which ends in an empty answer.  Called by _bins(), and
+        only where the norm it reads back anyway does not already rule such an element out (|element| <= norm): a batch of
+        ordinary queries pays no reduction and no read-back for this check."""
+        amax = float(q.abs().max().item())
+        if not amax < self.FP16_IMAGE_LIMIT:
+            raise B.RarcUnsupported(
+                f"metric '{self.metric}': a query element of magnitude {amax:.6g} has no finite fp16 copy (the scan kernels read "
+                f"one; elements must stay below {self.FP16_IMAGE_LIMIT:.0f}).  Scale the queries down by a power of two and the "
+                "scores back up (inner products scale with it exactly), or use metric 'cosine', which takes queries of any scale")
 
     def add_rows_f16(self, rows_f16, max_norm: float, n_valid: Optional[int] = None) -> None:
         """Adopt rows that are already in storage format ([n][d_pad] fp16 on this device).  A buffer
@@ -626,6 +656,7 @@ class FlatIndexF16:
             if row_scales is not None:
                 self._rowscale[self.ntotal: self.ntotal + n].copy_(t.from_numpy(np.array(row_scales, dtype=np.float32, copy=True)))
             if self.storage == "f32":   # the scan's image: the rows rounded to fp16 (round to nearest even)
+                self._refuse_rows_without_image(self._rows[self.ntotal: self.ntotal + n])   # (ntotal unchanged: nothing was added)
                 self._image16[self.ntotal: self.ntotal + n].copy_(self._rows[self.ntotal: self.ntotal + n])
             old = self.ntotal
             self.ntotal += n
@@ -746,6 +777,7 @@ class FlatIndexF16:
             if self.storage == "f8":
                 self._io_call("rarc_file_to_device", path, ssegs, self._rowscale, threads, direct)
             if self.storage == "f32":   # the scan's image: the rows rounded to fp16 (round to nearest even)
+                self._refuse_rows_without_image(self._rows[old: old + n_new])   # (a file written by something else)
                 self._image16[old: old + n_new].copy_(self._rows[old: old + n_new])
             self.ntotal = old + n_new
             self._version += 1
@@ -922,6 +954,8 @@ class FlatIndexF16:
             if self.ntotal == 0:        # an empty index answers (-1, -inf) like faiss; no kernel has anything to read
                 return (t.full((nq, k), -1, dtype=t.int64, device=self.device),
                         t.full((nq, k), float("inf" if self.metric == "l2" else "-inf"), dtype=t.float32, device=self.device))
+            # (every launch's score range first: _bins() refuses queries out of the fp16 range before anything is launched)
+            bins = None if wide else [self._bins(q[s: s + B.MAX_QUERIES]) for s in range(0, nq, B.MAX_QUERIES)]
             out_ids = t.empty((nq, k), dtype=t.int64, device=self.device)
             out_sc = t.empty((nq, k), dtype=t.float32, device=self.device)
             for s in range(0, nq, B.MAX_QUERIES):
@@ -929,7 +963,7 @@ class FlatIndexF16:
                 if wide:
                     self._search_wide_chunk(q[s:e], k, out_ids[s:e], out_sc[s:e])
                 else:
-                    self._search_chunk(q[s:e], k, out_ids[s:e], out_sc[s:e], repair)
+                    self._search_chunk(q[s:e], k, out_ids[s:e], out_sc[s:e], repair, bins=bins[s // B.MAX_QUERIES])
             return out_ids, out_sc
 
     # ------------------------------------------------------------------ wide rows / large k (csrc/wide.hip)
@@ -968,6 +1002,11 @@ class FlatIndexF16:
         l2 = self.metric == "l2"
         if not norm:
             bound = float(q.norm(dim=1).max().item()) * float(self.max_norm) * 1.01
+            if not np.isfinite(bound):      # the fp32 sum of squares overflowed (elements beyond 1.8e19): the norm in float64
+                bound = float(q.double().norm(dim=1).max().item()) * float(self.max_norm) * 1.01
+            if not np.isfinite(bound):
+                raise B.RarcUnsupported(f"metric '{self.metric}': the queries hold a non-finite element (rows of dim {self.dim} "
+                                        "on the wide path, storage 'f16' / 'f32'): scale them into the fp32 range")
             if bound >= 32768.0 and l2:
                 # (a distance is not linear in q: the power-of-two scaling below does not carry over)
                 raise B.RarcUnsupported(f"metric 'l2': |q| * max |row| = {bound:.4g} is beyond the fp16 range of the first chunk's "
@@ -1047,6 +1086,9 @@ class FlatIndexF16:
             if q.ndim != 2 or q.shape[1] != self.dim or q.shape[0] < 1:
                 raise ValueError(f"expected [nq][{self.dim}] queries, got {tuple(q.shape)}")
             nq = q.shape[0]
+            # every launch's score range first: _bins() refuses queries out of the fp16 range before anything is launched or
+            # taken from the pools (and its read-back, metric "ip", does not wait behind an earlier launch of this batch)
+            bins = [self._bins(q[s0: s0 + B.MAX_QUERIES]) for s0 in range(0, nq, B.MAX_QUERIES)]
             parts = []
             # the answer's pinned staging slot belongs to the handle returned below until it is released / dies
             slot = self._pins.acquire(t, nq, k) if to_host else None
@@ -1075,7 +1117,8 @@ class FlatIndexF16:
                     except ReferenceError:
                         gate = None
                 self._search_chunk(q[s0:e0], k, out_ids[s0:e0], out_sc[s0:e0], repair=False, status=status,
-                                   flag_host=flag_h.data_ptr(), gate=gate.cuda_event if gate is not None else 0)
+                                   flag_host=flag_h.data_ptr(), gate=gate.cuda_event if gate is not None else 0,
+                                   bins=bins[s0 // B.MAX_QUERIES])
                 done = t.cuda.Event()
                 done.record()
                 self._fin_event = done
@@ -1261,10 +1304,13 @@ class FlatIndexF16:
     def _bins(self, q) -> Tuple[float, float]:
         if self.normalize:
             return -1.0, 1.0
-        bound = float(q.norm(dim=1).max().item()) * max(self.max_norm, 1e-30) * 1.001
+        qn = float(q.norm(dim=1).max().item())
+        if not qn < self.FP16_IMAGE_LIMIT:      # (an element is at most the norm: below the limit no query has one beyond it)
+            self._refuse_queries_without_fp16(q)
+        bound = qn * max(self.max_norm, 1e-30) * 1.001
         return -bound, bound
 
-    def _search_chunk(self, q, k, out_ids, out_sc, repair, status=None, flag_host: int = 0, gate: int = 0) -> None:
+    def _search_chunk(self, q, k, out_ids, out_sc, repair, status=None, flag_host: int = 0, gate: int = 0, bins=None) -> None:
         """One batch of at most 256 queries through rarc_search_batch: query prep + seed + scan + finalize in one foreign
         call; `status` (257 words) is zeroed by the prep kernel, `flag_host` (address of a pinned word, 0 = none) receives
         the any-flag word, `gate` (a hipEvent_t, 0 = none) holds the scan back until a neighbouring context has finished."""
@@ -1275,7 +1321,7 @@ class FlatIndexF16:
             status = b["status"]
         nq = q.shape[0]
         stream = self._stream()
-        lo, hi = self._bins(q)
+        lo, hi = self._bins(q) if bins is None else bins
         # the int8 path's threshold proof needs the k-th best approximate score, nothing beyond it (its 2·eps8
         # margin is the slack); the fp16 path's certificate wants k' > k candidates
         kp = k if self._use_q8(k) else self.kprime_for(k)

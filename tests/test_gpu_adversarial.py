@@ -6,14 +6,27 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _run(oracle, X, Q, k, metric="cosine"):
+def _oracle_search(oracle, storage, X, Q, k, metric):
+    """The oracle of the storage format (as tests/test_gpu_fuzz_shapes.py): (ids, scores)."""
+    norm = metric == "cosine"
+    qn = oracle.normalize_L2(Q) if norm else Q
+    if storage == "f16":
+        rows, _ = oracle.ingest_f16(X, normalize=norm)
+        return oracle.flat_search_f16(rows, qn, k)[:2]
+    if storage == "f8":
+        b8, s8, _ = oracle.ingest_f8(X, normalize=norm)
+        return oracle.flat_search_f8(b8, s8, qn, k)[:2]
+    rows, _ = oracle.ingest_f32(X, normalize=norm)
+    return oracle.flat_search_f32(rows, qn, k)[:2]
+
+
+def _run(oracle, X, Q, k, metric="cosine", storage="f16", shadow=False, ref=None):
     from rag_arc_amd.hip.engine import FlatIndexF16
 
-    rows, _ = oracle.ingest_f16(X, normalize=(metric == "cosine"))
-    qn = oracle.normalize_L2(Q) if metric == "cosine" else Q
-    rI, rD, _ = oracle.flat_search_f16(rows, qn, k)
-    for scan in ("q8", "mfma16"):        # both scan kernels must survive the same abuse
-        idx = FlatIndexF16(X.shape[1], metric=metric, scan=scan)
+    rI, rD = ref if ref is not None else _oracle_search(oracle, storage, X, Q, k, metric)
+    # both scan kernels must survive the same abuse (fp8 / fp32 rows and the int8 image have the int8 scan only)
+    for scan in (("q8", "mfma16") if storage == "f16" and not shadow else ("q8",)):
+        idx = FlatIndexF16(X.shape[1], metric=metric, scan=scan, storage=storage, shadow=shadow)
         idx.add(X)
         D, I = idx.search(Q, k)
         assert np.array_equal(I, rI), f"ids differ ({scan})"
@@ -287,3 +300,127 @@ def test_warm_up_is_a_no_op_on_a_corpus_the_default_capacity_fits(storage):
     D, I = idx.search(X[pick], 1)
     assert np.array_equal(I[:, 0], pick)
     assert FlatIndexF16(256, storage=storage).warm_up() == 0          # empty index
+
+
+# ---- the same corpora on every row format ------------------------------------------------------------------------------
+# (storage, shadow): fp8 rows, fp32 rows, fp16 rows with the stored int8 image.  Each case states what makes its corpus hard
+# and asserts that from the ORACLE's answer alone, before anything runs on the GPU.  The int8 image needs a dimension that
+# pads to a multiple of 256: the two corpora whose size is not one take it at the next such dimension.
+FORMATS = [pytest.param("f8", False, id="f8"), pytest.param("f32", False, id="f32"), pytest.param("f16", True, id="shadow")]
+
+
+def _int8_margin(v):
+    """What "inside the margin" means below, worked out from the data on the host: the int8 image of a vector rounds every
+    element to a step of at least max|x| / 127 (the scale is shared by a tile: its step is no finer), noise of RMS
+    step / sqrt(12) per element — sqrt(d / 12) * max|x| / 127 in norm for the unit vector v / ||v||.  A score moves by about
+    that much for the row's image and as much again for the query's: rows whose scores are closer cannot be told apart by
+    the prefilter, on any row format."""
+    v = np.asarray(v, np.float64)
+    return float(np.sqrt(v.size / 12.0) * np.abs(v).max() / np.linalg.norm(v) / 127.0)
+
+
+@pytest.mark.parametrize("storage, shadow", FORMATS)
+def test_every_format_corpus_sorted_by_similarity_to_a_query(oracle, storage, shadow):
+    """Premise: query 0's best 100 rows all lie in the last 1 % of the corpus (the thresholds chase the data to the end)."""
+    rng = np.random.default_rng(100)
+    n, d, k = 20_000, 256, 100
+    X = rng.standard_normal((n, d)).astype(np.float32)
+    Q = rng.standard_normal((8, d)).astype(np.float32)
+    X = X[np.argsort(X @ Q[0])]
+    ref = _oracle_search(oracle, storage, X, Q, k, "cosine")
+    assert ref[0][0].min() >= n - n // 100
+    _run(oracle, X, Q, k, storage=storage, shadow=shadow, ref=ref)
+
+
+@pytest.mark.parametrize("storage, shadow", FORMATS)
+def test_every_format_tight_cluster_of_near_duplicates(oracle, storage, shadow):
+    """Premise: for the two queries at the cluster, at least 2000 rows score within the margin of the k-th best."""
+    rng = np.random.default_rng(101)
+    n, d, k = 20_000, (512 if shadow else 384), 100
+    X = rng.standard_normal((n, d)).astype(np.float32)
+    c = rng.standard_normal(d).astype(np.float32)
+    X[5000:7000] = c + 0.01 * rng.standard_normal((2000, d)).astype(np.float32)
+    Q = np.stack([c, c + 0.02 * rng.standard_normal(d).astype(np.float32), rng.standard_normal(d).astype(np.float32)])
+    deep_ids, deep = _oracle_search(oracle, storage, X, Q, 2000, "cosine")
+    margin = _int8_margin(c) + min(_int8_margin(Q[0]), _int8_margin(Q[1]))        # (the cluster's rows are c to 1 %)
+    print("gap to the 2000th:", deep[:2, k - 1] - deep[:2, 1999], "margin:", margin)
+    assert (deep[:2, 1999] >= deep[:2, k - 1] - margin).all()
+    _run(oracle, X, Q, k, storage=storage, shadow=shadow, ref=(deep_ids[:, :k].copy(), deep[:, :k].copy()))
+
+
+@pytest.mark.parametrize("storage, shadow", FORMATS)
+def test_every_format_all_rows_identical(oracle, storage, shadow):
+    """Premise: every row has the same score bits for a query, so the answer is decided by the id order alone."""
+    rng = np.random.default_rng(102)
+    n, d, k = 6000, 256, 50
+    X = np.tile(rng.standard_normal((1, d)).astype(np.float32), (n, 1))
+    Q = rng.standard_normal((3, d)).astype(np.float32)
+    allI, allD = _oracle_search(oracle, storage, X, Q, n, "cosine")
+    assert (allD.view(np.uint32) == allD.view(np.uint32)[:, :1]).all() and (allI == np.arange(n)).all()
+    _run(oracle, X, Q, k, storage=storage, shadow=shadow, ref=(allI[:, :k].copy(), allD[:, :k].copy()))
+
+
+@pytest.mark.parametrize("storage, shadow", FORMATS)
+def test_every_format_scores_spanning_many_magnitudes_ip(oracle, storage, shadow):
+    """Premise: the stored rows' norms span more than three decades, and so do the scores of every query's top 64."""
+    rng = np.random.default_rng(103)
+    n, d, k = 20_000, 512, 64
+    X = rng.standard_normal((n, d)).astype(np.float32) * np.exp(rng.uniform(-6, 3, (n, 1))).astype(np.float32)
+    Q = rng.standard_normal((5, d)).astype(np.float32) * 3
+    norm2 = {"f16": lambda: oracle.ingest_f16(X, normalize=False)[1], "f8": lambda: oracle.ingest_f8(X, normalize=False)[2],
+             "f32": lambda: oracle.ingest_f32(X, normalize=False)[1]}[storage]()
+    assert norm2.max() / norm2.min() > 1e6
+    ref = _oracle_search(oracle, storage, X, Q, k, "ip")
+    allD = _oracle_search(oracle, storage, X, Q, n, "ip")[1]
+    assert (np.abs(allD[:, 0]) / np.abs(allD).min(axis=1).clip(1e-30) > 1e3).all()
+    _run(oracle, X, Q, k, metric="ip", storage=storage, shadow=shadow, ref=ref)
+
+
+@pytest.mark.parametrize("storage, shadow", FORMATS)
+def test_every_format_dense_score_band_large_k(oracle, storage, shadow):
+    """Premise: more rows than the finalize's 6144-row rescore buffer holds score within 0.03 — two error bounds at this
+    dimension — of query 0's k-th best, k = 996: they are rescored in bands, and the answer needs no repair."""
+    rng = np.random.default_rng(104)
+    n, m, d, k = 20_000, 12_000, (256 if shadow else 128), 996
+    X = rng.standard_normal((n, d)).astype(np.float32)
+    X /= np.linalg.norm(X, axis=1, keepdims=True)
+    q = np.zeros((3, d), np.float32)
+    q[0, 0] = 1.0
+    q[1:] = rng.standard_normal((2, d)).astype(np.float32)
+    c = rng.uniform(0.80, 0.83, m).astype(np.float32)
+    u = X[:m].copy()
+    u[:, 0] = 0.0
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    X[:m] = c[:, None] * q[0] + np.sqrt(1.0 - c * c)[:, None] * u
+    X = X[rng.permutation(n)]
+    deep = _oracle_search(oracle, storage, X, q, 7000, "cosine")
+    assert deep[1][0, 6999] >= deep[1][0, k - 1] - 0.03
+    idx = _run(oracle, X, q, k, storage=storage, shadow=shadow, ref=(deep[0][:, :k].copy(), deep[1][:, :k].copy()))
+    assert len(idx.last_repaired) == 0
+
+
+@pytest.mark.parametrize("metric", ["cosine", "ip"])
+def test_fp32_rows_on_the_wide_path_with_near_duplicate_clusters(oracle, metric):
+    """rho (the distance of the fp16 image from the fp32 rows) enters the wide path's margin too (csrc/wide.hip), and fp32
+    wide rows have only met Gaussian data.  Premise: 4 distinct rows, copied 5000 times each with perturbations of 1e-4 on a
+    third of them — for the two queries that ARE base rows, 4000 rows lie within the margin of the k-th best."""
+    from rag_arc_amd.hip.engine import FlatIndexF16
+
+    rng = np.random.default_rng(105)
+    n, d, k = 20_000, 1536, 300
+    base = rng.standard_normal((4, d)).astype(np.float32)
+    X = np.repeat(base, n // 4, axis=0)
+    X[::3] += (rng.standard_normal((len(X[::3]), d)) * 1e-4).astype(np.float32)
+    rng.shuffle(X)
+    Q = np.concatenate([base[:2], rng.standard_normal((3, d)).astype(np.float32)])
+    deep = _oracle_search(oracle, "f32", X, Q, 4000, metric)
+    # the wide path's first scores are fp16 products of the fp16 image: uncertain by 2^-11 relative and more
+    rel = 2.0 ** -11 * (1.0 if metric == "cosine" else float(np.sum(base[:2] ** 2, axis=1).min()))
+    print("gap to the 4000th:", deep[1][:2, k - 1] - deep[1][:2, 3999], "margin:", rel)
+    assert (deep[1][:2, 3999] >= deep[1][:2, k - 1] - rel).all()
+    idx = FlatIndexF16(d, metric=metric, storage="f32")
+    assert idx._takes_wide_path(k)
+    idx.add(X)
+    D, I = idx.search(Q, k)
+    assert np.array_equal(I, deep[0][:, :k]), "ids differ"
+    assert np.array_equal(D.view(np.uint32), deep[1][:, :k].view(np.uint32)), "scores differ"
