@@ -672,6 +672,11 @@ int rarc_row_sqnorms(const void* d_rows, int fmt, int64_t n_rows, int d_pad, int
 int rarc_search_wide_l2(const void* d_rows, const uint16_t* d_image16, int fmt, int64_t n_rows, int d_pad, float max_norm,
                         float rho, const float* d_xn, const void* d_qblock, int nq, int k, int64_t id_base, int64_t* d_out_ids,
                         float* d_out_scores, uint32_t* d_status, void* d_ws, size_t ws_bytes, int cand_cap, void* stream);
+/* Test hook for the bound behind the two searches above (csrc/wide.hip): after a search on d_ws (same d_pad and cand_cap, same
+ * stream or one ordered behind it) copies out what the search left there, d_out fp32 [4][256]: per query eps, the final
+ * threshold thr (+inf for the padding queries), and after rarc_search_wide_l2 epsd = eps_k + delta and the canonical |q|^2
+ * (undefined after rarc_search_wide).  Reads the workspace only; not used by any search. */
+int rarc_debug_wide_bounds(const void* d_ws, size_t ws_bytes, int d_pad, int cand_cap, float* d_out, void* stream);
 
 /*
  * All pairs (i < j) of n embeddings whose cosine reaches a threshold — the entity de-duplication of the reference's graph

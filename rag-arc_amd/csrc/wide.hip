@@ -695,3 +695,19 @@ extern "C" int rarc_search_wide_l2(const void* d_rows, const uint16_t* d_image16
   return wide_search_impl<true>(d_rows, d_image16, fmt, n_rows, d_pad, max_norm, rho, d_qblock, nq, k, id_base, d_out_ids,
                                 d_out_scores, d_status, d_ws, ws_bytes, cand_cap, d_xn, stream);
 }
+
+// Test hook (tests/test_gpu_wide_bound.py): what a finished search left in its workspace — eps, the final thr, and for metric
+// "l2" epsd and qn — as d_out fp32 [4][256].  Carved like the search carves it; reads only.
+extern "C" int rarc_debug_wide_bounds(const void* d_ws, size_t ws_bytes, int d_pad, int cand_cap, float* d_out, void* stream) {
+  RARC_REQUIRE(d_ws && d_out, RARC_E_INVALID, "rarc_debug_wide_bounds: null pointer");
+  RARC_REQUIRE(d_pad > 0 && d_pad % RARC_DIM_ALIGN == 0 && d_pad <= 4096 && cand_cap > 0 && cand_cap % WIDE_SHARDS == 0, RARC_E_INVALID,
+               "rarc_debug_wide_bounds: bad arguments (d_pad=%d cand_cap=%d)", d_pad, cand_cap);
+  char* wsb = (char*)(((uintptr_t)d_ws + 255) & ~(uintptr_t)255);
+  RARC_REQUIRE(wsb + wide_ws_bytes(d_pad, cand_cap) <= (const char*)d_ws + ws_bytes, RARC_E_WORKSPACE,
+               "rarc_debug_wide_bounds: workspace of %zu bytes, %zu needed", ws_bytes, wide_ws_bytes(d_pad, cand_cap) + 256);
+  const WideWs w = wide_carve(wsb, d_pad, cand_cap);
+  const float* part[4] = {w.eps, w.thr, w.epsd, w.qn};
+  for (int i = 0; i < 4; ++i)
+    RARC_HIP_CHECK(hipMemcpyAsync(d_out + i * WIDE_NQ, part[i], WIDE_NQ * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return RARC_OK;
+}
