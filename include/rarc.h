@@ -679,6 +679,37 @@ int rarc_search_wide_l2(const void* d_rows, const uint16_t* d_image16, int fmt, 
 int rarc_debug_wide_bounds(const void* d_ws, size_t ws_bytes, int d_pad, int cand_cap, float* d_out, void* stream);
 
 /*
+ * Exact top-k over a LIST of rows of one index — the search behind a metadata filter (a LangChain-style `filter=` on the
+ * store's search calls; the reference's FAISS store has no filter at all: encapsulation/database/vector_db/VectorStore_Faiss.py:212-274
+ * ignores its kwargs).  Every listed row is scored once per query with the canonical fp32 inner product and ranked by the key
+ * of rarc_search_wide's finalize: the answer is the unfiltered ranking (score desc, id asc; metric "l2": dist asc, id asc) with
+ * the rows outside the list struck out, cut at k — ids and score bits are the oracle's.  No approximate pass, no bound, no
+ * overflow: d_status (uint32 [256]) comes back all RARC_Q_OK.
+ *   d_rows    fmt 0: fp16 rows [n_rows][d_pad]; fmt 2: fp32 rows.  d_pad a multiple of 128, <= 4096
+ *   d_qblock  as written by rarc_prep_queries (the fp32 queries are what is read), 1 <= nq <= 256
+ *   d_list    m row numbers (int64).  THE CALLER'S CONTRACT, not checked: strictly ascending, each in [0, n_rows).
+ *             m == 0 is valid (d_list may then be NULL): every answer is padding
+ *   k         1 <= k <= 8192; d_out_ids / d_out_scores [nq][k], (-1, -inf) beyond min(k, m) — metric "l2": (-1, +inf)
+ *   l2, d_xn  l2 != 0: squared distances max(0, (|q|^2 + |x|^2) - 2 q.x) as rarc_search_wide_l2 forms them, d_xn = the rows'
+ *             squared norms (rarc_row_sqnorms, fp32 [n_rows]); l2 == 0: d_xn is not read
+ *   d_ws      rarc_search_rows_workspace_bytes(nq, k) bytes — each query's k best so far plus one slab of the list: it does
+ *             not grow with m (0 = nq or k out of range)
+ * A row fetched from HBM serves up to eight queries of the batch; one query (the reference's call) is a gather of m rows.
+ *
+ * rarc_strike_rows — the over-fetch way to the same answer: d_ids / d_scores [nq][kprime] is an ordinary answer (ids =
+ * id_base + row, padding -1), d_bits a bitmask over the rows (uint32 [ceil(n_rows / 32)], bit r & 31 of word r >> 5).  Entries
+ * whose row has no bit are struck, each query's first k survivors kept in order into d_out_ids / d_out_scores [nq][k]
+ * (padding as above behind them), d_count[q] = survivors found (at most k).  A query with d_count[q] < min(k, allowed rows) did
+ * not see all of its answer among the kprime: answer it with rarc_search_rows.
+ */
+size_t rarc_search_rows_workspace_bytes(int nq, int k);
+int rarc_search_rows(const void* d_rows, int fmt, int64_t n_rows, int d_pad, const void* d_qblock, int nq, const int64_t* d_list,
+                     int64_t m, int k, int64_t id_base, const float* d_xn, int l2, int64_t* d_out_ids, float* d_out_scores,
+                     uint32_t* d_status, void* d_ws, size_t ws_bytes, void* stream);
+int rarc_strike_rows(const int64_t* d_ids, const float* d_scores, int nq, int kprime, const uint32_t* d_bits, int64_t n_rows,
+                     int64_t id_base, int k, int l2, int64_t* d_out_ids, float* d_out_scores, uint32_t* d_count, void* stream);
+
+/*
  * All pairs (i < j) of n embeddings whose cosine reaches a threshold — the entity de-duplication of the reference's graph
  * store (encapsulation/database/graph_db/Base_Neo4j.py:538-583: sklearn.metrics.pairwise.cosine_similarity over every entity
  * embedding, then a python loop over i < j keeping similarity >= 0.95); SURVEY 8(f) rank 4.  The n x n matrix is never

@@ -5,7 +5,7 @@
 //
 // Eight lanes per row, lane j runs chain j (elements 8m + j, m ascending).  fp16 rows: the group fetches 128 contiguous bytes
 // per step (lane j the 16 bytes of elements 8(8b + j) .. + 7) and passes them through its 128 bytes of LDS, from which lane j
-// picks element j of each of the eight pieces in ascending order (as wide.hip's wide_canon_dot8; a wave's LDS operations
+// picks element j of each of the eight pieces in ascending order (as canon_topk.h's wide_canon_dot8; a wave's LDS operations
 // execute in order, and a group sits inside one wave).  fp32 rows go the same way, 32 elements per step.  One read of the rows
 // in 128-byte pieces, 4 bytes written per row (the measured rate is in DESIGN 4.10b).
 #include "rarc_common.h"

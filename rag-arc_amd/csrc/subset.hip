@@ -1,0 +1,253 @@
+// subset.hip — exact top-k over a LIST of rows of one index: the search behind a metadata filter (FlatIndexF16.search_filtered,
+// HipFlatVectorStore's `filter=`).  The scans and the chunked-GEMM search read every stored row; a filter that lets a
+// thousandth of them through wants the allowed rows and nothing else.
+//
+//   rarc_search_rows      every listed row scored canonically, once per query, and ranked by the finalize's own 64-bit key
+//                         (rarc_candkey; (0 - dist, ~row) for metric "l2"): no approximate pass, no bound, nothing to overflow
+//   rarc_strike_rows      the other way to a filtered answer: an ordinary top-k' answer with the rows outside a bitmask struck
+//                         out and each query's first k survivors kept in order (the over-fetch leg; a query with fewer
+//                         survivors than it should have is then answered by rarc_search_rows)
+//
+// rarc_search_rows walks the list in slabs.  Per slab:
+//   subset_score_kernel   a workgroup stages QT queries in LDS (fp32; QT = 8 up to 2048 padded dimensions, 4 beyond: at most
+//                         64 KB) and walks 32 listed rows per step, eight lanes per row (canon_topk.h: wide_canon_dot8n — a row
+//                         is fetched from HBM once for the QT queries, in 16-byte loads, two in flight per lane).  The key of
+//                         (query, row) goes to the query's list, behind the k best kept from the slabs before.
+//                         QT = 1 (the reference's call: one query) is a pure gather, m · 2 · d_pad bytes.
+//   subset_select_kernel  one workgroup per query: the k best keys of (kept + slab) by radix select (canon_topk.h) back to the
+//                         front of the list; behind the last slab they are sorted and written out.
+// The workspace is 256 lists of k + slab keys, whatever m is: slab = 8M keys / nq - k clamped to [32768, 262144] rows — a
+// single query takes long slabs (its select is one workgroup: few of them), a full batch short ones (84 MB at k = 8192).
+//
+// The caller's contract: d_list holds m row numbers, STRICTLY ASCENDING, each < n_rows.  Neither is checked (a check would
+// read the list back); distinct rows are what makes a query's keys distinct, which the select counts on.
+#include "rarc_common.h"
+#include "canon_topk.h"
+
+namespace {
+constexpr int SUB_KMAX = 8192;                 // largest k (the select holds its answer in LDS: 64 KB)
+constexpr int SUB_BUDGET_KEYS = 8 << 20;       // keys of one slab over all queries (64 MB)
+constexpr int SUB_SLAB_MIN = 32768, SUB_SLAB_MAX = 262144;
+
+int sub_slab_rows(int nq, int k) {
+  int64_t s = (int64_t)SUB_BUDGET_KEYS / nq - k;
+  s = s < SUB_SLAB_MIN ? SUB_SLAB_MIN : (s > SUB_SLAB_MAX ? SUB_SLAB_MAX : s);
+  return (int)(s / 32 * 32);
+}
+size_t sub_ws_bytes(int nq, int k) { return 1024 + (size_t)nq * ((size_t)k + sub_slab_rows(nq, k)) * 8; }
+
+// metric "l2": qn[q] = canonical dot(q, q) — the finalize's arithmetic with the query block as the "rows"
+__global__ __launch_bounds__(256) void subset_qn_kernel(const float* __restrict__ q32, int d_pad, int nq, float* __restrict__ qn) {
+  const int q = blockIdx.x * 32 + (threadIdx.x >> 3), j = threadIdx.x & 7;
+  const int qc = q < nq ? q : nq - 1;
+  const float s = wide_canon_dot8<true>(q32 + (size_t)qc * d_pad, q32, (size_t)qc, d_pad, j, nullptr);
+  if (q < nq && j == 0) qn[q] = s;
+}
+
+// keys[q][kept + i] = key of (query q, row list[i]) for i < n_list, q in [QT blockIdx.y, + QT) below nq.
+// xn: null = inner-product keys; else the rows' squared norms and qn the queries' (metric "l2").
+template <bool F32ROWS, int QT>
+__global__ __launch_bounds__(256) void subset_score_kernel(const void* __restrict__ rows, int d_pad, const float* __restrict__ q32,
+                                                           int nq, const int64_t* __restrict__ list, uint32_t n_list,
+                                                           uint64_t* __restrict__ keys, uint32_t stride, uint32_t kept,
+                                                           const float* __restrict__ xn, const float* __restrict__ qn) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* s_q = (float*)smem;                                // [QT][d_pad]
+  __shared__ uint4 s_stage[256];                            // 128 bytes per 8-lane group
+  const int q0 = blockIdx.y * QT;
+  for (int i = threadIdx.x; i < QT * d_pad; i += 256) {
+    const int t = i / d_pad;
+    s_q[i] = q0 + t < nq ? q32[(size_t)q0 * d_pad + i] : 0.f;
+  }
+  __syncthreads();
+  const int j = threadIdx.x & 7;
+  uint4* stage = s_stage + (threadIdx.x & ~7);
+  // whole groups of 32 rows per step: the lanes of a group stay together through the shuffles; entries past the end of the
+  // list are read as its last one and not written
+  for (uint32_t i0 = blockIdx.x * 32; i0 < n_list; i0 += gridDim.x * 32) {
+    const uint32_t i = i0 + (threadIdx.x >> 3);
+    const bool live = i < n_list;
+    const uint32_t row = (uint32_t)list[live ? i : n_list - 1];
+    float s[QT];
+    wide_canon_dot8n<F32ROWS, QT>(s_q, d_pad, rows, (size_t)row, d_pad, j, stage, s);
+    if (live && j == 0) {
+      const float xr = xn ? xn[row] : 0.f;
+#pragma unroll
+      for (int t = 0; t < QT; ++t)
+        if (q0 + t < nq)
+          keys[(size_t)(q0 + t) * stride + kept + i] = rarc_candkey(xn ? wide_l2_neg_dist(qn[q0 + t], xr, s[t]) : s[t], row);
+    }
+  }
+}
+
+// One workgroup per query over its c keys.  last == 0: the k best (c > k) move to the front of the list, in no particular
+// order.  last != 0: the min(k, c) best in exact order are the answer; (-1, -inf) — metric "l2": (-1, +inf) — behind them.
+template <bool L2>
+__global__ __launch_bounds__(1024) void subset_select_kernel(uint64_t* keys_all, uint32_t stride, uint32_t c, uint32_t k, int last,
+                                                             int64_t id_base, int64_t* out_ids, float* out_scores, uint32_t* status) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint64_t* s_top = (uint64_t*)smem;                       // [pow2 >= min(k, c)]
+  __shared__ uint32_t s_hist[256];
+  __shared__ uint32_t s_pick[2];
+  __shared__ uint32_t s_cnt[2];
+  const uint32_t q = blockIdx.x;
+  uint64_t* keys = keys_all + (size_t)q * stride;
+  const uint32_t kk = k < c ? k : c;
+  uint32_t pow2 = 1;
+  while (pow2 < kk) pow2 <<= 1;
+  wide_topk_keys(keys, c, kk, pow2, s_top, s_hist, s_pick, s_cnt, last != 0);
+  if (!last) {          // (every read of the list is behind the barriers of wide_topk_keys)
+    for (uint32_t i = threadIdx.x; i < kk; i += blockDim.x) keys[i] = s_top[i];
+    return;
+  }
+  wide_write_topk<L2>(s_top, kk, k, id_base, out_ids + (size_t)q * k, out_scores + (size_t)q * k);
+  if (q == 0)
+    for (uint32_t i = threadIdx.x; i < RARC_MAX_QUERIES; i += blockDim.x) status[i] = RARC_Q_OK;     // nothing here can overflow
+}
+
+// out[q][0 .. k) = the first k entries of in[q][0 .. kp) whose row has its bit set, in order, padding behind them; count[q] =
+// how many were found before the walk ended (it ends at k).  256 threads walk 256 entries per step.
+__global__ __launch_bounds__(256) void strike_rows_kernel(const int64_t* __restrict__ ids, const float* __restrict__ scores, int kp,
+                                                          const uint32_t* __restrict__ bits, int64_t n_rows, int64_t id_base, int k,
+                                                          float pad, int64_t* __restrict__ out_ids, float* __restrict__ out_scores,
+                                                          uint32_t* __restrict__ count) {
+  __shared__ uint32_t s_wave[4];
+  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  uint32_t base = 0;
+  for (int i0 = 0; i0 < kp && base < (uint32_t)k; i0 += 256) {      // (base is the same in every thread)
+    const int i = i0 + tid;
+    bool ok = false;
+    int64_t id = -1;
+    float s = pad;
+    if (i < kp) {
+      id = ids[(size_t)q * kp + i];
+      s = scores[(size_t)q * kp + i];
+      const int64_t r = id - id_base;
+      ok = id >= 0 && r >= 0 && r < n_rows && ((bits[r >> 5] >> (r & 31)) & 1u);
+    }
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(ok);
+    if (lane == 0) s_wave[w] = (uint32_t)__builtin_popcountll(b);
+    __syncthreads();
+    uint32_t pos = base + (uint32_t)__builtin_popcountll(b & ((1ull << lane) - 1ull));
+    for (int v = 0; v < w; ++v) pos += s_wave[v];
+    if (ok && pos < (uint32_t)k) {
+      out_ids[(size_t)q * k + pos] = id;
+      out_scores[(size_t)q * k + pos] = s;
+    }
+    base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    __syncthreads();
+  }
+  for (uint32_t i = base + tid; i < (uint32_t)k; i += 256) {
+    out_ids[(size_t)q * k + i] = -1;
+    out_scores[(size_t)q * k + i] = pad;
+  }
+  if (tid == 0) count[q] = base < (uint32_t)k ? base : (uint32_t)k;
+}
+
+template <bool F32ROWS, int QT>
+int sub_launch_score(const void* d_rows, int d_pad, const float* q32, int nq, const int64_t* list, uint32_t n_list, uint64_t* keys,
+                     uint32_t stride, uint32_t kept, const float* xn, const float* qn, hipStream_t s) {
+  const size_t lds = (size_t)QT * d_pad * 4;
+  static RarcPerDevice attr_done;
+  if (size_t& done = attr_done.cur(); !done) {
+    RARC_HIP_CHECK(hipFuncSetAttribute((const void*)subset_score_kernel<F32ROWS, QT>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+    done = 1;
+  }
+  const uint32_t steps = (n_list + 31) / 32, qtiles = (uint32_t)((nq + QT - 1) / QT);
+  // enough workgroups to fill 256 CUs a few times over, each staging its queries once for several steps
+  uint32_t gx = 2048 / qtiles;
+  gx = gx < 8 ? 8 : gx;
+  gx = gx > steps ? steps : gx;
+  hipLaunchKernelGGL((subset_score_kernel<F32ROWS, QT>), dim3(gx, qtiles), dim3(256), lds, s, d_rows, d_pad, q32, nq, list, n_list,
+                     keys, stride, kept, xn, qn);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+template <bool L2>
+int sub_launch_select(uint64_t* keys, uint32_t stride, uint32_t c, int k, int last, int nq, int64_t id_base, int64_t* out_ids,
+                      float* out_scores, uint32_t* status, hipStream_t s) {
+  static RarcPerDevice attr_done;
+  if (size_t& done = attr_done.cur(); !done) {
+    RARC_HIP_CHECK(hipFuncSetAttribute((const void*)subset_select_kernel<L2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+    done = 1;
+  }
+  uint32_t pow2 = 1;
+  while (pow2 < (uint32_t)k) pow2 <<= 1;
+  hipLaunchKernelGGL(subset_select_kernel<L2>, dim3(nq), dim3(1024), (size_t)pow2 * 8, s, keys, stride, c, (uint32_t)k, last, id_base,
+                     out_ids, out_scores, status);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+}  // namespace
+
+extern "C" size_t rarc_search_rows_workspace_bytes(int nq, int k) {
+  return (nq >= 1 && nq <= RARC_MAX_QUERIES && k >= 1 && k <= SUB_KMAX) ? sub_ws_bytes(nq, k) + 256 : 0;
+}
+
+extern "C" int rarc_search_rows(const void* d_rows, int fmt, int64_t n_rows, int d_pad, const void* d_qblock, int nq,
+                                const int64_t* d_list, int64_t m, int k, int64_t id_base, const float* d_xn, int l2,
+                                int64_t* d_out_ids, float* d_out_scores, uint32_t* d_status, void* d_ws, size_t ws_bytes,
+                                void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_rows && d_qblock && d_out_ids && d_out_scores && d_status && d_ws && (d_list || m == 0), RARC_E_INVALID,
+               "rarc_search_rows: null pointer");
+  RARC_REQUIRE(fmt == 0 || fmt == 2, RARC_E_INVALID, "rarc_search_rows: fmt 0 (fp16 rows) or 2 (fp32 rows), got %d", fmt);
+  RARC_REQUIRE(!l2 || d_xn, RARC_E_INVALID, "rarc_search_rows: null pointer (d_xn: metric l2 needs the rows' squared norms, rarc_row_sqnorms)");
+  RARC_REQUIRE(d_pad > 0 && d_pad % RARC_DIM_ALIGN == 0 && d_pad <= 4096, RARC_E_UNSUPPORTED,
+               "rarc_search_rows: padded dim %d unsupported (multiple of %d, <= 4096)", d_pad, RARC_DIM_ALIGN);
+  RARC_REQUIRE(nq >= 1 && nq <= RARC_MAX_QUERIES && k >= 1 && k <= SUB_KMAX, RARC_E_INVALID,
+               "rarc_search_rows: need 1 <= nq <= %d, 1 <= k <= %d (nq=%d k=%d)", RARC_MAX_QUERIES, SUB_KMAX, nq, k);
+  RARC_REQUIRE(n_rows >= 0 && n_rows < (int64_t)0xffffff00ll && m >= 0 && m <= n_rows, RARC_E_INVALID,
+               "rarc_search_rows: need 0 <= m <= n_rows < 2^32 - 256 (m=%lld n_rows=%lld)", (long long)m, (long long)n_rows);
+  char* wsb = (char*)(((uintptr_t)d_ws + 255) & ~(uintptr_t)255);
+  RARC_REQUIRE(wsb + sub_ws_bytes(nq, k) <= (char*)d_ws + ws_bytes, RARC_E_WORKSPACE,
+               "rarc_search_rows: workspace of %zu bytes, %zu needed", ws_bytes, sub_ws_bytes(nq, k) + 256);
+  hipStream_t s = (hipStream_t)stream;
+  float* qn = (float*)wsb;                                  // [256]
+  uint64_t* keys = (uint64_t*)(wsb + 1024);                 // [nq][k + slab]
+  const int slab = sub_slab_rows(nq, k);
+  const uint32_t stride = (uint32_t)(k + slab);
+  const RarcQb qb = rarc_qb_carve(d_qblock, d_pad);
+  const float* xn = l2 ? d_xn : nullptr;
+  if (l2 && m > 0) {
+    hipLaunchKernelGGL(subset_qn_kernel, dim3((nq + 31) / 32), dim3(256), 0, s, qb.q32, d_pad, nq, qn);
+    RARC_HIP_CHECK(hipGetLastError());
+  }
+  const bool wide_rows = d_pad > 2048;
+  uint32_t kept = 0;
+  int rc;
+  for (int64_t at = 0; at < m; at += slab) {
+    const uint32_t n = (uint32_t)(m - at < slab ? m - at : slab);
+    const int64_t* list = d_list + at;
+#define SUB_SCORE(F32, QT) sub_launch_score<F32, QT>(d_rows, d_pad, qb.q32, nq, list, n, keys, stride, kept, xn, qn, s)
+    if (fmt == 2) rc = nq == 1 ? SUB_SCORE(true, 1) : (wide_rows ? SUB_SCORE(true, 4) : SUB_SCORE(true, 8));
+    else rc = nq == 1 ? SUB_SCORE(false, 1) : (wide_rows ? SUB_SCORE(false, 4) : SUB_SCORE(false, 8));
+#undef SUB_SCORE
+    if (rc != RARC_OK) return rc;
+    const uint32_t c = kept + n;
+    if (at + slab < m && c > (uint32_t)k) {       // more slabs follow: keep the k best (the last slab's select is the answer's)
+      rc = l2 ? sub_launch_select<true>(keys, stride, c, k, 0, nq, id_base, d_out_ids, d_out_scores, d_status, s)
+              : sub_launch_select<false>(keys, stride, c, k, 0, nq, id_base, d_out_ids, d_out_scores, d_status, s);
+      if (rc != RARC_OK) return rc;
+      kept = (uint32_t)k;
+    } else {
+      kept = c;
+    }
+  }
+  return l2 ? sub_launch_select<true>(keys, stride, kept, k, 1, nq, id_base, d_out_ids, d_out_scores, d_status, s)
+            : sub_launch_select<false>(keys, stride, kept, k, 1, nq, id_base, d_out_ids, d_out_scores, d_status, s);
+}
+
+extern "C" int rarc_strike_rows(const int64_t* d_ids, const float* d_scores, int nq, int kprime, const uint32_t* d_bits,
+                                int64_t n_rows, int64_t id_base, int k, int l2, int64_t* d_out_ids, float* d_out_scores,
+                                uint32_t* d_count, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_ids && d_scores && d_bits && d_out_ids && d_out_scores && d_count, RARC_E_INVALID, "rarc_strike_rows: null pointer");
+  RARC_REQUIRE(nq >= 1 && k >= 1 && kprime >= 1 && n_rows >= 0, RARC_E_INVALID,
+               "rarc_strike_rows: need nq >= 1, k >= 1, kprime >= 1 (nq=%d k=%d kprime=%d)", nq, k, kprime);
+  hipLaunchKernelGGL(strike_rows_kernel, dim3(nq), dim3(256), 0, (hipStream_t)stream, d_ids, d_scores, kprime, d_bits, n_rows, id_base,
+                     k, l2 ? INFINITY : -INFINITY, d_out_ids, d_out_scores, d_count);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}

@@ -52,6 +52,7 @@
 // oracle's order, xn as stored, qn canonical from wide_eps_kernel), dist is formed as above and ranked as the 64-bit key
 // (ordered(0 - dist), ~row): largest first = (dist asc, id asc).  A list that fills up flags the query as before.
 #include "rarc_common.h"
+#include "canon_topk.h"   // the canonical row score, the radix select and the exact top-k: shared with subset.hip
 
 bool rarc_gemm_f16_select_takes(int m, int k);   // encoder.hip: the same GEMM with the select in its epilogue (no score matrix)
 int rarc_gemm_f16_select(const uint16_t* a, const uint16_t* w, int m, int k, const float* thr, unsigned long long* cand,
@@ -254,37 +255,7 @@ __global__ __launch_bounds__(256) void wide_select_kernel(const uint16_t* __rest
   (void)m_rows;
 }
 
-// k-th largest 32-bit value among n words read through `at(i)` by the whole block: four rounds of an 8-bit radix
-// histogram in LDS.  Returns the value (every thread); n >= k >= 1.
-template <typename At>
-__device__ uint32_t wide_kth_largest_u32(At at, uint32_t n, uint32_t k, uint32_t* s_hist, uint32_t* s_pick) {
-  uint32_t prefix = 0, mask = 0, need = k;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    for (uint32_t i = threadIdx.x; i < 256; i += blockDim.x) s_hist[i] = 0;
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-      const uint32_t v = at(i);
-      if ((v & mask) == prefix) atomicAdd(&s_hist[(v >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) {      // the bin holding the need-th largest, by one wave (a serial walk of the 256 counters by one
-      uint32_t above = 0;        //  thread was 7 us a round — 28 of the 40 us a tighten took)
-      int b = rarc_wave_find_from_top(s_hist, 256, need, &above);
-      if (b < 0) { b = 0; above = 0; }           // (n >= need: cannot happen)
-      if (threadIdx.x == 0) {
-        s_pick[0] = (uint32_t)b;
-        s_pick[1] = need - above;
-      }
-    }
-    __syncthreads();
-    prefix |= s_pick[0] << shift;
-    mask |= 255u << shift;
-    need = s_pick[1];
-    __syncthreads();
-  }
-  return prefix;
-}
-
+// (wide_kth_largest_u32 — the k-th largest 32-bit value among n words read through `at(i)` — lives in canon_topk.h.)
 // The same over entries a caller ENUMERATES (each(f): f(value) for every entry of this thread's share): the tighten's sub-lists.
 template <typename Each>
 __device__ uint32_t wide_kth_largest_each(Each each, uint32_t k, uint32_t* s_hist, uint32_t* s_pick) {
@@ -392,44 +363,6 @@ __global__ __launch_bounds__(1024) void wide_tighten_kernel(const uint64_t* __re
   }
 }
 
-// canonical fp32 score of a query with one stored row, by 8 lanes: lane j runs chain j (elements 8m + j, m ascending), the
-// tree of rarc_canon_tree joins them — the same arithmetic, in the same order, as canon_dot_f16 / oracle canon_dot.
-// fp16 rows: the group fetches 128 contiguous bytes per step (lane j the 16 bytes of elements 8(8b + j) .. + 7) and passes them
-// through its 128 bytes of LDS, from which lane j picks element j of each of the eight pieces in ascending order — one
-// 16-byte load per 64 elements and lane instead of eight 2-byte ones (the finalize was 100 us of a 490 us search of 100,000
-// rows, 2 ms of 13 at k = 2000: all of it these loads).  A wave's LDS operations execute in order, so the lanes of a group
-// (always inside one wave) see each other's writes without a barrier.  q: the query in LDS (fp32).
-template <bool F32ROWS>
-__device__ __forceinline__ float wide_canon_dot8(const float* q, const void* __restrict__ rows, size_t row, int d_pad, int j,
-                                                 uint4* stage) {
-  float a = 0.f;
-  if (F32ROWS) {
-    const float* r = (const float*)rows + row * (size_t)d_pad;
-    for (int m = j; m < d_pad; m += 8) a = __builtin_fmaf(q[m], r[m], a);
-  } else {
-    const uint4* r = (const uint4*)((const half_t*)rows + row * (size_t)d_pad) + j;
-    const half_t* sh = (const half_t*)stage + j;
-    const int nblk = d_pad >> 6;                    // 64 elements per step (d_pad is a multiple of 64)
-    uint4 v0 = r[0], v1 = nblk > 1 ? r[8] : v0;     // two steps in flight
-    for (int b = 0; b < nblk; ++b) {
-      const uint4 vn = b + 2 < nblk ? r[(b + 2) * 8] : v1;
-      stage[j] = v0;
-      asm volatile("" ::: "memory");
-      const float* qb = q + 64 * b + j;
-#pragma unroll
-      for (int mm = 0; mm < 8; ++mm) a = __builtin_fmaf(qb[8 * mm], (float)sh[8 * mm], a);
-      asm volatile("" ::: "memory");
-      v0 = v1;
-      v1 = vn;
-    }
-  }
-  // ((a0 + a4) + (a2 + a6)) + ((a1 + a5) + (a3 + a7)): lanes j and j ^ 4, then j ^ 2, then j ^ 1
-  a = a + __shfl_xor(a, 4, 8);
-  a = a + __shfl_xor(a, 2, 8);
-  a = a + __shfl_xor(a, 1, 8);
-  return a;
-}
-
 // One workgroup per query: canonical scores of its candidates, the k best by (score desc, id asc), written out.
 // L2: dist = max(0, (qn + xn) - 2 ip) per candidate, ranked as the key (0 - dist, ~row) — largest first = (dist asc, id asc); the
 // scores written out are the distances (+inf beyond the stored rows).
@@ -443,7 +376,7 @@ __global__ __launch_bounds__(1024) void wide_finalize_kernel(const void* __restr
   uint64_t* s_top = (uint64_t*)smem;                       // [pow2 >= k]
   __shared__ uint32_t s_hist[256];
   __shared__ uint32_t s_pick[2];
-  __shared__ uint32_t s_n;
+  __shared__ uint32_t s_cnt[2];
   const uint32_t q = blockIdx.x;
   if (q >= nq) return;
   const uint32_t c_all = count[q * WIDE_SHARDS], c = c_all < cap ? c_all : cap;     // (laid out flat by the last tighten pass)
@@ -461,65 +394,17 @@ __global__ __launch_bounds__(1024) void wide_finalize_kernel(const void* __restr
       const bool live = i < c;
       const uint32_t row = live ? rarc_candrow(keys[i]) : 0u;
       float s = wide_canon_dot8<F32ROWS>(s_q, rows, row, d_pad, j, stage);
-      if constexpr (L2) {
-        // 2 ip is exact and the subtraction rounds once: contracted into an FMA or not, the same bits.  0 - dist: +0 stays +0
-        // (one key for distance zero), every other distance changes sign exactly.
-        const float dd = (qn[q] + xn[row]) - 2.0f * s;
-        s = 0.f - (dd > 0.f ? dd : 0.f);
-      }
+      if constexpr (L2) s = wide_l2_neg_dist(qn[q], xn[row], s);    // ranked as 0 - dist
       if (live && j == 0) keys[i] = rarc_candkey(s, row);
     }
   }
   __syncthreads();
-  // 2. the k-th largest KEY (64 bits: score, then ~row = id ascending): radix select on the high word, then on the low word
-  //    among the keys that share it
+  // 2. the k best keys (64 bits: score, then ~row = id ascending) in exact order, 3. written out (canon_topk.h)
   const uint32_t kk = k < c ? k : c;
   uint32_t pow2 = 1;
   while (pow2 < kk) pow2 <<= 1;
-  for (uint32_t i = threadIdx.x; i < pow2; i += blockDim.x) s_top[i] = 0;
-  if (threadIdx.x == 0) s_n = 0;
-  __syncthreads();
-  if (kk > 0) {
-    const uint32_t hi = wide_kth_largest_u32([&](uint32_t i) { return (uint32_t)(keys[i] >> 32); }, c, kk, s_hist, s_pick);
-    // how many keys lie strictly above `hi` in the high word; the rest of the k come from the ties on it, by low word
-    __shared__ uint32_t s_above;
-    if (threadIdx.x == 0) s_above = 0;
-    __syncthreads();
-    uint32_t mine = 0;
-    for (uint32_t i = threadIdx.x; i < c; i += blockDim.x) mine += ((uint32_t)(keys[i] >> 32) > hi);
-    if (mine) atomicAdd(&s_above, mine);
-    __syncthreads();
-    const uint32_t need_lo = kk - s_above;   // >= 1
-    // (the low word is ~row: larger = smaller id; ties on the high word are few except for duplicate rows)
-    const uint32_t lo = wide_kth_largest_u32(
-        [&](uint32_t i) { return (uint32_t)(keys[i] >> 32) == hi ? (uint32_t)keys[i] : 0u; }, c, need_lo, s_hist, s_pick);
-    const uint64_t kth = ((uint64_t)hi << 32) | lo;
-    for (uint32_t i = threadIdx.x; i < c; i += blockDim.x)
-      if (keys[i] >= kth) {
-        const uint32_t pos = atomicAdd(&s_n, 1u);
-        if (pos < pow2) s_top[pos] = keys[i];
-      }
-    __syncthreads();
-    // 3. exact order: bitonic sort, descending (zeros — below every real key — pad to the power of two)
-    for (uint32_t kb = 2; kb <= pow2; kb <<= 1)
-      for (uint32_t jb = kb >> 1; jb > 0; jb >>= 1) {
-        for (uint32_t i = threadIdx.x; i < pow2; i += blockDim.x) {
-          const uint32_t ixj = i ^ jb;
-          if (ixj > i) {
-            const uint64_t a = s_top[i], b = s_top[ixj];
-            const bool desc = (i & kb) == 0;
-            if (desc ? a < b : a > b) { s_top[i] = b; s_top[ixj] = a; }
-          }
-        }
-        __syncthreads();
-      }
-  }
-  for (uint32_t i = threadIdx.x; i < k; i += blockDim.x) {
-    const bool have = i < kk;
-    const uint64_t key = have ? s_top[i] : 0;
-    out_ids[(size_t)q * k + i] = have ? id_base + (int64_t)rarc_candrow(key) : -1;
-    out_scores[(size_t)q * k + i] = L2 ? (have ? 0.f - rarc_candscore(key) : INFINITY) : (have ? rarc_candscore(key) : -INFINITY);
-  }
+  wide_topk_keys(keys, c, kk, pow2, s_top, s_hist, s_pick, s_cnt, true);
+  wide_write_topk<L2>(s_top, kk, k, id_base, out_ids + (size_t)q * k, out_scores + (size_t)q * k);
 }
 
 extern "C" size_t rarc_wide_workspace_bytes(int d_pad, int cand_cap) {

@@ -52,6 +52,30 @@ def _mmr_select(scored, embeddings, query_embedding, k, lambda_mult=0.5):
     return [scored[i][0] for i in chosen]
 
 
+def metadata_matches(metadata: dict, flt) -> bool:
+    """LangChain FAISS's filter semantics: a callable decides on the metadata dict; a dict must match on EVERY key — a list
+    or tuple value by membership, anything else by ==; a document without the key does not match."""
+    if callable(flt):
+        return bool(flt(metadata))
+    if not isinstance(flt, dict):
+        raise ValueError(f"filter must be a dict, a callable or a RowSet, got {type(flt).__name__}")
+    for key, want in flt.items():
+        if key not in metadata:
+            return False
+        have = metadata[key]
+        if isinstance(want, (list, tuple)):
+            if have not in want:
+                return False
+        elif have != want:
+            return False
+    return True
+
+
+def matching_rows(metadatas, flt) -> np.ndarray:
+    """Row numbers (ascending) of the metadata dicts a dict / callable filter lets through (None = {})."""
+    return np.fromiter((r for r, md in enumerate(metadatas) if metadata_matches({} if md is None else md, flt)), dtype=np.int64)
+
+
 def _shard_files(folder: str, index_name: str) -> List[str]:
     """Every shard file of `index_name` in the folder, whatever layout wrote it."""
     import re
@@ -528,6 +552,10 @@ class HipFlatVectorStore(VectorStore):
         return [d for d, _ in self.similarity_search_with_score(query, k, **kwargs)]
 
     def similarity_search_with_score(self, query: str, k: int = 4, **kwargs: Any) -> List[Tuple[Document, float]]:
+        if self._checked_filter(kwargs.get("filter")) is not None:
+            if self.ntotal == 0:
+                return []
+            return self._filtered_answers(np.array([self.embedding.embed_query(query)]).astype(np.float32), k, kwargs["filter"], True)[0]
         if self.ntotal == 0:
             return []
         if self._coalescer is not None and self._batch_embedder() is not None:
@@ -544,14 +572,15 @@ class HipFlatVectorStore(VectorStore):
     async def asimilarity_search_with_score(self, *args: Any, **kwargs: Any) -> List[Tuple[Document, float]]:
         query = args[0] if args else kwargs.get("query")
         k = args[1] if len(args) > 1 else kwargs.get("k", 4)
-        if self._coalescer is None or not isinstance(query, str) or self._batch_embedder() is None or len(args) > 2:
+        if (self._coalescer is None or not isinstance(query, str) or self._batch_embedder() is None or len(args) > 2
+                or kwargs.get("filter") is not None):       # (the front carries (query, k): a filtered call takes the sync path)
             return await super().asimilarity_search_with_score(*args, **kwargs)
         if self.ntotal == 0:
             return []
         return await self._async_front().submit(query, min(int(k), self.ntotal))
 
     async def asimilarity_search(self, query: str, k: int = 4, **kwargs: Any) -> List[Document]:
-        if self._coalescer is None or self._batch_embedder() is None:
+        if self._coalescer is None or self._batch_embedder() is None or kwargs.get("filter") is not None:
             return await super().asimilarity_search(query, k, **kwargs)
         return [d for d, _ in await self.asimilarity_search_with_score(query, k)]
 
@@ -565,6 +594,10 @@ class HipFlatVectorStore(VectorStore):
         return [d for d, _ in self.similarity_search_by_vector_with_score(embedding, k, **kwargs)]
 
     def similarity_search_by_vector_with_score(self, embedding, k: int = 4, **kwargs: Any):
+        if self._checked_filter(kwargs.get("filter")) is not None:
+            if self.ntotal == 0:
+                return []
+            return self._filtered_answers(np.array([embedding]).astype(np.float32), k, kwargs["filter"], True)[0]
         if self.ntotal == 0:
             return []
         k = min(k, self.ntotal)
@@ -574,6 +607,50 @@ class HipFlatVectorStore(VectorStore):
         with self._guard.shared():
             scores, rows = self.index.search(qv, k)
             return self._to_documents(scores[0], rows[0])
+
+    # -- filter= : a search over the documents a metadata predicate lets through -------------------------------------------
+    def _checked_filter(self, flt):
+        """`filter=None` is the unfiltered path; anything else must be answerable HERE, or is refused before any launch."""
+        if flt is not None and self.storage == "f8":
+            from ....hip.binding import RarcUnsupported
+
+            raise RarcUnsupported("filter= scores the allowed rows from fp16 / fp32 rows: use storage 'f16' or 'f32' (an 'f8' store "
+                                  "answers unfiltered searches)")
+        return flt
+
+    def row_filter(self, filter):          # noqa: A002 - LangChain's keyword
+        """Evaluate a dict / callable filter ONCE over every document's metadata and return the prepared handle (a RowSet):
+        pass it as `filter=` to any number of searches.  A python predicate over a million metadata dicts costs far more than
+        the search it restricts; the handle is good until the next add_texts / delete (a search with a stale one raises)."""
+        with self._guard.shared():
+            return self._resolve_filter(self._checked_filter(filter))
+
+    def _resolve_filter(self, flt):
+        """dict / callable -> RowSet over today's rows (caller holds the guard); a RowSet is used as is."""
+        from ....hip.engine import RowSet
+
+        if isinstance(flt, RowSet):
+            return flt
+        if self.index is None or not hasattr(self.index, "rowset"):
+            raise NotImplementedError("this store's engine has no filtered search")
+        seq = self._docs_by_row()
+        if isinstance(seq, ColumnarDocstore):
+            metadatas = seq.metadatas if seq.metadatas is not None else ({} for _ in range(len(seq)))
+        else:
+            metadatas = (d.metadata for d in seq)
+        return self.index.rowset(matching_rows(metadatas, flt))
+
+    def _filtered_answers(self, q, k: int, flt, with_scores: bool):
+        """Per query [(Document, score)] / [Document] of a filtered search.  Resolution and search under ONE shared hold of
+        the guard: a concurrent delete cannot renumber rows between them.  k is clamped to the number of matching rows, as it
+        is clamped to ntotal without a filter: fewer than k matches return what there is."""
+        with self._guard.shared():
+            rs = self._resolve_filter(flt)
+            kk = min(int(k), rs.m)
+            if kk < 1:
+                return [[] for _ in range(len(q))]
+            scores, rows = self.index.search_filtered(q, kk, rs)
+            return self._map_batch(scores, rows, with_scores)
 
     def _to_documents(self, scores, rows) -> List[Tuple[Document, float]]:
         """[(Document, float(score))] of one query's answer, row -1 skipped (VectorStore_Faiss.py:265-272)."""
@@ -667,11 +744,20 @@ class HipFlatVectorStore(VectorStore):
             self.timing[key] = self.timing.get(key, 0.0) + (now - t0)
         return now
 
-    def batch_search_by_vector(self, embeddings, k: int = 4):
-        """Many query vectors, one scan per 256.  Returns (scores fp32 [nq][k], row indices int64 [nq][k])."""
+    def batch_search_by_vector(self, embeddings, k: int = 4, filter=None):      # noqa: A002
+        """Many query vectors, one scan per 256.  Returns (scores fp32 [nq][k], row indices int64 [nq][k]); with `filter`
+        (one for the whole batch) k is clamped to the matching rows."""
+        self._checked_filter(filter)
         if self.ntotal == 0:
             nq = len(embeddings)
             return np.zeros((nq, 0), np.float32), np.zeros((nq, 0), np.int64)
+        if filter is not None:
+            with self._guard.shared():
+                rs = self._resolve_filter(filter)
+                kk = min(int(k), rs.m)
+                if kk < 1:
+                    return np.zeros((len(embeddings), 0), np.float32), np.zeros((len(embeddings), 0), np.int64)
+                return self.index.search_filtered(embeddings, kk, rs)
         q = embeddings if hasattr(embeddings, "is_cuda") else np.asarray(embeddings, dtype=np.float32)
         nq, kk, at = len(q), min(int(k), self.ntotal), 0
         scores, rows = np.empty((nq, kk), np.float32), np.empty((nq, kk), np.int64)
@@ -680,15 +766,18 @@ class HipFlatVectorStore(VectorStore):
             at += len(sc)
         return scores, rows
 
-    def _batch_answers(self, queries: Sequence[str], k: int, with_scores: bool):
+    def _batch_answers(self, queries: Sequence[str], k: int, with_scores: bool, flt=None):
         import time
 
         queries = list(queries)
+        self._checked_filter(flt)
         if self.ntotal == 0 or not queries:
             return [[] for _ in queries]
         t0 = time.perf_counter()
         q = self._embed_batch(queries)
         t0 = self._tick("embed_s", t0)
+        if flt is not None:
+            return self._filtered_answers(q, k, flt, with_scores)
         out: list = []
         with self._guard.shared():
             for scores, rows in self._search_chunks(q, k):
@@ -700,11 +789,11 @@ class HipFlatVectorStore(VectorStore):
     def batch_similarity_search_with_score(self, queries: Sequence[str], k: int = 4, **kwargs: Any):
         """similarity_search_with_score for a list of queries: one encoder call (when the provider can batch), one scan per
         256 queries, each scan running while the answer before it becomes Documents.  Element i equals
-        similarity_search_with_score(queries[i], k)."""
-        return self._batch_answers(queries, k, True)
+        similarity_search_with_score(queries[i], k).  `filter=`: one filter for the whole batch."""
+        return self._batch_answers(queries, k, True, kwargs.get("filter"))
 
     def batch_similarity_search(self, queries: Sequence[str], k: int = 4, **kwargs: Any) -> List[List[Document]]:
-        return self._batch_answers(queries, k, False)
+        return self._batch_answers(queries, k, False, kwargs.get("filter"))
 
     @property
     def coalesced_launches(self) -> Tuple[int, int]:
@@ -714,6 +803,7 @@ class HipFlatVectorStore(VectorStore):
 
     def max_marginal_relevance_search(self, query: str, k: int = 4, fetch_k: int = 20, lambda_mult: float = 0.5,
                                       **kwargs: Any) -> List[Document]:
+        self._refuse_mmr_filter(kwargs)
         if self.ntotal == 0:
             return []
         return self.max_marginal_relevance_search_by_vector(self.embedding.embed_query(query), k, fetch_k,
@@ -728,6 +818,7 @@ class HipFlatVectorStore(VectorStore):
         format (a relative 5e-4 for fp16), so the selection can differ from the reference's only where
         two candidates' MMR values are within that rounding."""
         reembed = kwargs.pop("reembed", True)
+        self._refuse_mmr_filter(kwargs)
         if self.ntotal == 0:
             return []
         qv32 = np.array([embedding]).astype(np.float32)
@@ -752,6 +843,15 @@ class HipFlatVectorStore(VectorStore):
             qv = qv / np.linalg.norm(qv)
             cand = cand / np.linalg.norm(cand, axis=1, keepdims=True)
         return _mmr_select(scored, cand.tolist(), qv.tolist(), k, lambda_mult)
+
+    @staticmethod
+    def _refuse_mmr_filter(kwargs) -> None:
+        if kwargs.get("filter") is not None:
+            from ....hip.binding import RarcUnsupported
+
+            raise RarcUnsupported("filter= is answered by the similarity searches (similarity_search*, batch_similarity_search*, "
+                                  "the retriever's 'similarity' modes), not by max_marginal_relevance_search: its fetch_k "
+                                  "candidates are taken from the whole index")
 
     def _mmr_on_device(self, rows: List[int], embedding, k: int, lambda_mult: float) -> List[int]:
         """Selection order (indices into `rows`) of the MMR loop, computed on the device from the resident rows."""

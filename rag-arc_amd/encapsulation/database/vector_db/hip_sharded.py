@@ -178,6 +178,17 @@ class HipShardedFlatVectorStore(HipFlatVectorStore):
         super().__init__(embedding, *args, **kwargs)
         self._group, self._merge_fn = group, merge_fn
 
+    def _checked_filter(self, flt):
+        if flt is not None:
+            from ....hip.binding import RarcUnsupported
+
+            raise RarcUnsupported("filter= is answered by the one-GPU store (HipFlatVectorStore): the sharded store has no "
+                                  "filtered search (every rank would need the filter's rows of its own shard)")
+        return flt
+
+    def row_filter(self, filter):          # noqa: A002
+        return self._checked_filter(filter if filter is not None else {})
+
     def _make_engine(self, dim: int):
         return _ShardedIndex(super()._make_engine(dim), group=self._group, merge_fn=self._merge_fn)
 

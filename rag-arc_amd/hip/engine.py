@@ -178,6 +178,45 @@ class DeviceArena:
             pass
 
 
+class RowSet:
+    """A prepared filter over the rows of one index (FlatIndexF16.rowset): the allowed row numbers, sorted and distinct, on the
+    device (`rows`, int64 [m] — what rarc_search_rows walks), the same set as a bitmask (`bits`, int32 words, bit r & 31 of
+    word r >> 5 — what rarc_strike_rows tests), `m`, and the version of the rows it was built for: an add extends nothing and a
+    delete renumbers rows, so search_filtered refuses a RowSet of an older version."""
+
+    __slots__ = ("rows", "bits", "m", "ntotal", "version", "_owner")
+
+    def __init__(self, rows, bits, m: int, ntotal: int, version: int, owner):
+        self.rows, self.bits, self.m, self.ntotal, self.version = rows, bits, int(m), int(ntotal), int(version)
+        self._owner = weakref.ref(owner)
+
+    def __len__(self) -> int:
+        return self.m
+
+    @staticmethod
+    def sorted_rows(rows_or_mask, ntotal: int) -> np.ndarray:
+        """The allowed row numbers as a sorted, distinct int64 array: from row numbers (any order, duplicates allowed) or
+        from a boolean mask of length ntotal.  ValueError for anything outside [0, ntotal).  Host-side, no device needed."""
+        a = rows_or_mask
+        if hasattr(a, "detach"):            # a torch tensor
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        if a.dtype == np.bool_:
+            if a.ndim != 1 or a.shape[0] != int(ntotal):
+                raise ValueError(f"a boolean row mask must have one entry per stored row ({int(ntotal)}), got shape {a.shape}")
+            return np.flatnonzero(a).astype(np.int64)
+        if a.size == 0:
+            return np.zeros(0, dtype=np.int64)
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"row numbers must be integers (or a boolean mask), got dtype {a.dtype}")
+        if a.dtype.kind == "u" and a.size and int(a.max()) >= int(ntotal):
+            raise ValueError(f"row numbers must lie in [0, {int(ntotal)})")
+        rows = np.unique(a.astype(np.int64).reshape(-1))
+        if rows[0] < 0 or rows[-1] >= int(ntotal):
+            raise ValueError(f"row numbers must lie in [0, {int(ntotal)}): got {int(rows[0])} .. {int(rows[-1])}")
+        return rows
+
+
 class FlatIndexF16:
     """Exact top-k inner-product search over fp16 (or, with storage="f8", fp8 e4m3fn + per-row scale)
     rows resident in HBM.
@@ -1354,6 +1393,150 @@ class FlatIndexF16:
         self.last_repaired = flagged
         if flagged:
             self._repair_rows(q, k, out_ids, out_sc, flagged, words=[words[i] for i in flagged])
+
+    # ------------------------------------------------------------------ filtered search (csrc/subset.hip)
+    # "auto" (measured at 1M x 768: profiles/filtered_1m_bench.json): over-fetch needs k' = ceil(1.5 k ntotal / m)
+    # + 32 results of an ordinary search — 1.5 x what a uniformly spread filter needs, so that a fallback is rare — and no path
+    # offers more than 8192.  The row-list search costs 2.5 ns per listed row plus 0.078 ns per row and query (a ratio of 32);
+    # an over-fetched search costs about what the unfiltered one does: the list wins while m * (32 + nq) stays under
+    # FILTER_SUBSET_WORK x ntotal (the measured cells put the constant between 3.3 and 16.5).
+    FILTER_OVERFETCH_MAX_K = B.WIDE_MAX_K
+    FILTER_SUBSET_WORK = 8.0
+
+    def rowset(self, rows_or_mask) -> RowSet:
+        """Prepare a filter: row numbers (numpy / torch / list, any order, duplicates allowed) or a boolean mask of length
+        ntotal -> RowSet.  ValueError for a row outside [0, ntotal)."""
+        self._refuse_filtered()
+        t = self.torch
+        with self._lock, t.cuda.device(self.device):
+            n = int(self.ntotal)
+            rows = RowSet.sorted_rows(rows_or_mask, n)
+            mask = np.zeros(((n + 31) // 32) * 32, dtype=np.uint8)
+            mask[rows] = 1
+            words = np.packbits(mask.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
+            bits = t.from_numpy(words.view(np.int32).copy()).to(self.device) if words.size else \
+                t.zeros(1, dtype=t.int32, device=self.device)
+            return RowSet(t.from_numpy(rows).to(self.device), bits, rows.size, n, self._rows_version(), self)
+
+    def _refuse_filtered(self) -> None:
+        if self.storage == "f8":
+            raise B.RarcUnsupported("a filtered search scores the allowed rows canonically from fp16 / fp32 rows (csrc/subset.hip): "
+                                    "store the rows as 'f16' or 'f32' (fp8 rows answer unfiltered searches)")
+        if self.shadow:
+            raise B.RarcUnsupported("a filtered search does not read the int8 shadow image: use storage 'f16' or 'f32' without "
+                                    "shadow=True")
+        if self._parent is not None:
+            raise B.RarcUnsupported("a twin() search context answers unfiltered searches: run search_filtered on the index it "
+                                    "was taken from")
+
+    @property
+    def filtered_stats(self) -> dict:
+        """Counters of search_filtered: 256-query batches answered by each strategy, and queries that over-fetch could not
+        answer and the row-list search answered instead."""
+        return self.__dict__.setdefault("_filtered_stats", {"subset_batches": 0, "overfetch_batches": 0, "fallback_queries": 0})
+
+    def _overfetch_k(self, k: int, m: int) -> int:
+        return -(-3 * int(k) * int(self.ntotal) // (2 * max(int(m), 1))) + 32
+
+    def filter_strategy(self, nq: int, k: int, m: int) -> str:
+        """What strategy="auto" takes for nq queries, k results and m allowed rows."""
+        if m == 0 or self.ntotal == 0:
+            return "subset"
+        if self._overfetch_k(k, m) > self.FILTER_OVERFETCH_MAX_K:
+            return "subset"
+        return "subset" if float(m) * (32.0 + float(nq)) <= self.FILTER_SUBSET_WORK * float(self.ntotal) else "overfetch"
+
+    def search_filtered(self, queries, k: int, rowset: RowSet, strategy: str = "auto") -> Tuple[np.ndarray, np.ndarray]:
+        """search() restricted to the rows of `rowset`: the unfiltered ranking with every other row struck out, cut at k —
+        (scores fp32 [nq][k], ids int64 [nq][k]); (-inf, -1) beyond min(k, m) (metric "l2": (+inf, -1)).  Exact whatever the
+        strategy: "subset" scores the listed rows only (rarc_search_rows), "overfetch" runs the ordinary search for
+        k' > k results, strikes the rows outside the set (rarc_strike_rows) and hands the queries that kept fewer than
+        min(k, m) to "subset"; "auto" chooses (filter_strategy)."""
+        ids, scores = self.search_filtered_device(queries, k, rowset, strategy)
+        return self.to_host(ids, scores)
+
+    def search_filtered_device(self, queries, k: int, rowset: RowSet, strategy: str = "auto"):
+        """search_filtered with the answer left on the device: (ids int64, scores fp32)."""
+        t = self.torch
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        if strategy not in ("auto", "subset", "overfetch"):
+            raise ValueError(f"unknown strategy: {strategy} ('auto', 'subset' or 'overfetch')")
+        self._refuse_filtered()
+        if k > B.WIDE_MAX_K:
+            raise B.RarcUnsupported(f"k={k} exceeds the limit of {B.WIDE_MAX_K} results per query")
+        if not isinstance(rowset, RowSet) or rowset._owner() is not self:
+            raise ValueError("search_filtered takes a RowSet made by this index's rowset()")
+        if rowset.version != self._rows_version():
+            raise B.RarcError("the index has changed since this RowSet was made (an add extends no filter, a delete renumbers "
+                              "rows): make a new one with rowset()")
+        with t.cuda.device(self.device):
+            q = t.as_tensor(queries, dtype=t.float32).to(self.device).contiguous()
+            if q.ndim == 1:
+                q = q[None, :]
+            if q.ndim != 2 or q.shape[1] != self.dim:
+                raise ValueError(f"expected [nq][{self.dim}] queries, got {tuple(q.shape)}")
+            nq, m = int(q.shape[0]), rowset.m
+            if strategy == "auto":
+                strategy = self.filter_strategy(nq, k, m)
+            pad = float("inf" if self.metric == "l2" else "-inf")
+            out_ids = t.full((nq, k), -1, dtype=t.int64, device=self.device)
+            out_sc = t.full((nq, k), pad, dtype=t.float32, device=self.device)
+            if self.ntotal == 0 or nq == 0:           # the empty index answers padding; no kernel has anything to read
+                return out_ids, out_sc
+            stats = self.filtered_stats
+            n_batches = -(-nq // B.MAX_QUERIES)
+            if strategy == "subset":
+                with self._lock:
+                    self._search_rows(q, k, rowset, out_ids, out_sc)
+                stats["subset_batches"] += n_batches
+                return out_ids, out_sc
+            # over-fetch: ONE ordinary search for k' results (never a loop on k'), the strike, then the row-list search for
+            # the queries whose k' results held too few allowed rows
+            kp = max(int(k), min(self._overfetch_k(k, m), self.FILTER_OVERFETCH_MAX_K, int(self.ntotal)))
+            ids, sc = self.search_device(q, kp)
+            with self._lock:
+                count = t.empty(nq, dtype=t.int32, device=self.device)
+                B.check(self.lib.rarc_strike_rows(ids.data_ptr(), sc.data_ptr(), nq, kp, rowset.bits.data_ptr(), rowset.ntotal,
+                                                  self.id_base, k, 1 if self.metric == "l2" else 0, out_ids.data_ptr(),
+                                                  out_sc.data_ptr(), count.data_ptr(), self._stream()), "rarc_strike_rows")
+                stats["overfetch_batches"] += n_batches
+                short = t.nonzero(count < min(int(k), m)).reshape(-1)      # (one read-back per call)
+                if short.numel():
+                    sub_ids = t.empty((short.numel(), k), dtype=t.int64, device=self.device)
+                    sub_sc = t.empty((short.numel(), k), dtype=t.float32, device=self.device)
+                    self._search_rows(q[short].contiguous(), k, rowset, sub_ids, sub_sc)
+                    out_ids[short], out_sc[short] = sub_ids, sub_sc
+                    stats["fallback_queries"] += int(short.numel())
+            return out_ids, out_sc
+
+    def _search_rows(self, q, k: int, rowset: RowSet, out_ids, out_sc) -> None:
+        """rarc_search_rows over the row list, 256 queries per call (caller holds the lock).  The queries go through
+        rarc_prep_queries as for any search (normalised for metric "cosine"); nothing here reads their fp16 copy, so
+        metric "ip" / "l2" take queries and rows of any finite scale."""
+        t = self.torch
+        self._ensure_qbuf()
+        norm = 1 if self.normalize else 0
+        mn = max(self.max_norm, 1.0) if norm else self.max_norm
+        stream = self._stream()
+        fmt = 2 if self.storage == "f32" else 0
+        l2 = self.metric == "l2"
+        status = t.empty(B.MAX_QUERIES, dtype=t.int32, device=self.device)
+        for s0 in range(0, q.shape[0], B.MAX_QUERIES):
+            qc = q[s0: s0 + B.MAX_QUERIES]
+            nq = int(qc.shape[0])
+            nbytes = int(self.lib.rarc_search_rows_workspace_bytes(nq, k))
+            if getattr(self, "_rows_ws", None) is None or self._rows_ws.numel() < nbytes:
+                self._rows_ws = None
+                self._rows_ws = t.empty(nbytes, dtype=t.uint8, device=self.device)
+            B.check(self.lib.rarc_prep_queries(qc.data_ptr(), qc.shape[1], nq, self.dim, self.d_pad, norm, mn, 0,
+                                               self._qbuf["qblock"].data_ptr(), stream), "rarc_prep_queries")
+            oi, osc = out_ids[s0: s0 + nq], out_sc[s0: s0 + nq]
+            B.check(self.lib.rarc_search_rows(self._rows.data_ptr(), fmt, self.ntotal, self.d_pad, self._qbuf["qblock"].data_ptr(),
+                                              nq, rowset.rows.data_ptr() if rowset.m else 0, rowset.m, k, self.id_base,
+                                              self._xn.data_ptr() if l2 else 0, 1 if l2 else 0, oi.data_ptr(), osc.data_ptr(),
+                                              status.data_ptr(), self._rows_ws.data_ptr(), self._rows_ws.numel(), stream),
+                    "rarc_search_rows")
 
     def neighbors_above(self, queries, threshold: float, k_cap: int = 64):
         """Range query by score: for every query, the stored rows whose canonical score is >= threshold
