@@ -677,6 +677,11 @@ int rarc_search_wide_l2(const void* d_rows, const uint16_t* d_image16, int fmt, 
  * threshold thr (+inf for the padding queries), and after rarc_search_wide_l2 epsd = eps_k + delta and the canonical |q|^2
  * (undefined after rarc_search_wide).  Reads the workspace only; not used by any search. */
 int rarc_debug_wide_bounds(const void* d_ws, size_t ws_bytes, int d_pad, int cand_cap, float* d_out, void* stream);
+/* Test hook for the int8 scale of a prepared query (csrc/rarc_common.h: rarc_query_scale8, the function rarc_prep_queries'
+ * kernel calls): for mx = max |element| of the prepared query, *sq = the multiplier of q8 = rint(v * sq) and *qi = 1 / sq, the
+ * fp32 number the scan dequantises with.  Both are finite and positive for every mx (zero, subnormal, infinite and NaN
+ * included) and mx * sq <= 127.4.  Host code only: touches no device, runs on a machine without one. */
+int rarc_debug_query_scale8(float mx, float* sq, float* qi);
 
 /*
  * Exact top-k over a LIST of rows of one index — the search behind a metadata filter (a LangChain-style `filter=` on the

@@ -259,9 +259,8 @@ __global__ __launch_bounds__(256) void rarc_prep_queries_kernel(const float* in,
   // the fp32 number qi = 1/s_q, so the quantised query is DEFINED as q8 * qi and the residual below
   // is taken against exactly that
   const float mx = __uint_as_float(s_amax);
-  float sq = (mx > 0.f && mx < INFINITY) ? 127.f / mx : 1.f;
-  while ((double)mx * (double)sq > 127.4) sq *= 0.9999f;
-  const float qi = 1.0f / sq;
+  float sq, qi;
+  rarc_query_scale8(mx, &sq, &qi);
   double rn = 0.0, hn = 0.0;
   for (int m = tid; m < d_pad; m += 256) {
     const float v = row[m];
@@ -505,6 +504,13 @@ extern "C" int rarc_prep_queries(const float* d_in, int64_t ld_in, int nq, int d
                      qb.q8, qb.eps16, qb.eps8, qb.qinv, qb.hq, qb.floor, rarc_launch_extras().status_zero,
                      rarc_launch_extras().flag_host);
   RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+// Host-only view of the scale the kernel above takes for a query whose largest prepared magnitude is mx: touches no device
+extern "C" int rarc_debug_query_scale8(float mx, float* sq, float* qi) {
+  RARC_REQUIRE(sq && qi, RARC_E_INVALID, "rarc_debug_query_scale8: null pointer");
+  rarc_query_scale8(mx, sq, qi);
   return RARC_OK;
 }
 

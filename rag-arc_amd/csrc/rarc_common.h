@@ -367,6 +367,20 @@ static inline __host__ __device__ float rarc_tmeta_pack(uint16_t s_half_bits, ui
   return __builtin_bit_cast(float, w);
 }
 
+// ---- int8 scale of a prepared query (rarc_prep_queries_kernel; rarc_debug_query_scale8 is the host's view of it) ----------
+// mx = max |v| over the prepared query.  q8 = rint(v * sq) clamped to +-127, and the scan dequantises with the fp32 number
+// qi = 1 / sq.  Any finite positive sq keeps the pruning proof: eps8 is built from the residual against q8 * qi as written.
+// sq = 127 / mx wherever that quotient is finite: it is correctly rounded and normal (a subnormal quotient would need
+// mx > 127 / FLT_MIN, beyond FLT_MAX), so mx * sq <= 127 (1 + 2^-24) and nothing is left to correct — no loop.  Below
+// mx = 127 / FLT_MAX (3.73e-37) the quotient overflows: sq = 1 there, the query quantises to zeros and eps8 becomes
+// ||q||·max||d||, far below the 1e-30 the bound carries anyway.  mx == 0 and a non-finite mx take sq = 1 as well.
+__host__ __device__ static inline void rarc_query_scale8(float mx, float* sq_out, float* qi_out) {
+  float sq = (mx > 0.f && mx < __builtin_inff()) ? 127.f / mx : 1.f;
+  if (!(sq < __builtin_inff())) sq = 1.f;
+  *sq_out = sq;
+  *qi_out = 1.0f / sq;
+}
+
 // ---- error plumbing (host) ------------------------------------------------------------------
 void rarc_set_error(const char* fmt, ...);
 #define RARC_HIP_CHECK(expr)                                                              \

@@ -202,6 +202,7 @@ SIGNATURES = {
     "rarc_search_wide_l2": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_float, c_float, c_void_p, c_void_p, c_int, c_int,
                                     c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "rarc_debug_wide_bounds": (c_int, [c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p]),
+    "rarc_debug_query_scale8": (c_int, [c_float, ctypes.POINTER(c_float), ctypes.POINTER(c_float)]),
     "rarc_search_rows_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rarc_search_rows": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -613,13 +613,21 @@ class FlatIndexF16:
                                                  norm2.data_ptr(), n, self.dim,
                                                  1 if self.normalize else 0, self._stream()),
                         "rarc_ingest_f16")
-            self.max_norm = max(self.max_norm, float(norm2.max().sqrt().item()))
+            block_norm = float(norm2.max().sqrt().item())
+            if block_norm < self.FP32_SQUARES_EXACT and not self.normalize and self.storage != "f16":
+                # the kernels' fp32 sums of squares (fp8: scale^2) underflow for rows this small, and max_norm has to stay an
+                # upper bound of every stored row's norm: from the vectors in float64 (an e4m3 value is within 2^-4 of its
+                # element, relatively; fp16 rows this small are stored as zeros and need nothing)
+                block_norm = max(block_norm, float(x.double().norm(dim=1).max().item()) * (1.07 if self.storage == "f8" else 1.0))
+            self.max_norm = max(self.max_norm, block_norm)
             old = self.ntotal
             self.ntotal += n
             self._version += 1
             self._requant(old)
 
     FP16_IMAGE_LIMIT = 65520.0     # the smallest magnitude that rounds to infinity as an fp16
+    FP32_SQUARES_EXACT = 1e-15     # a norm below this may come from squares under FLT_MIN (elements under 1.1e-19): the fp32 sum
+    #                                of squares then loses them, down to 0 for elements under 2^-75
 
     def _refuse_rows_without_image(self, x) -> None:
         """fp32 storage keeps the rows as they come, but every scan reads their fp16 IMAGE, and rho — the distance between the
@@ -1346,7 +1354,11 @@ class FlatIndexF16:
         qn = float(q.norm(dim=1).max().item())
         if not qn < self.FP16_IMAGE_LIMIT:      # (an element is at most the norm: below the limit no query has one beyond it)
             self._refuse_queries_without_fp16(q)
-        bound = qn * max(self.max_norm, 1e-30) * 1.001
+        if qn < self.FP32_SQUARES_EXACT:        # elements whose squares leave the fp32 range: the norm again in float64
+            qn = float(q.double().norm(dim=1).max().item())
+        # (never an empty window: an all-zero batch, or a bound below the fp32 range, is answered — every score is +-0 or
+        #  next to it — and 1e-30 is the absolute term every error bound of the query block carries anyway)
+        bound = max(qn * max(self.max_norm, 1e-30) * 1.001, 1e-30)
         return -bound, bound
 
     def _search_chunk(self, q, k, out_ids, out_sc, repair, status=None, flag_host: int = 0, gate: int = 0, bins=None) -> None:

@@ -89,7 +89,7 @@ def test_bound_holds_and_is_not_vacuous_on_gaussian_data():
 
 CASES = ["outlier_dims", "row_magnitudes", "tile_magnitudes", "sparse", "tiny_huge", "aligned"]
 NEW_CASES = ["norm_spread_in_tile", "one_hot", "tiny_elements", "image_of_zeros", "half_ulp_off_the_image", "zero_rows_zero_query",
-             "query_scales"]
+             "query_scales", "tiny_queries", "subnormal_queries"]
 
 
 def _case_data(case, n=4000, d=384, nq=32):
@@ -154,6 +154,18 @@ def _case_data(case, n=4000, d=384, nq=32):
     elif case == "query_scales":
         Q[::2] *= 1e4
         Q[1::2] *= 1e-6
+        metric = "ip"
+    elif case == "tiny_queries":
+        # max|q| just above and just below 127 / FLT_MAX (3.73e-37), where the int8 scale 127 / max|q| is next to FLT_MAX (its
+        # inverse a subnormal) or overflows (rarc_query_scale8 then takes 1 and the query quantises to zeros)
+        edge = 127.0 / float(np.finfo(np.float32).max)
+        to = np.where(np.arange(nq) % 2 == 0, edge * 1.01, edge * 0.99)
+        Q = (Q.astype(np.float64) * (to / np.abs(Q).max(axis=1))[:, None]).astype(np.float32)
+        assert (np.abs(Q).max(axis=1)[::2] > edge).all() and (np.abs(Q).max(axis=1)[1::2] < edge).all()
+        metric = "ip"
+    elif case == "subnormal_queries":               # every element an fp32 subnormal (or zero)
+        Q = (Q.astype(np.float64) * 1e-42).astype(np.float32)
+        assert Q.any() and np.abs(Q).max() < np.finfo(np.float32).tiny
         metric = "ip"
     else:
         raise KeyError(case)

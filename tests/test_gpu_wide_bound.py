@@ -86,6 +86,21 @@ def _case(oracle, name):
         c["k"] = 1025 if d == 256 else 10
         X = rng.standard_normal((n, d)).astype(np.float32)
         Q = rng.standard_normal((8, d)).astype(np.float32)
+    elif name in ("tiny_queries", "subnormal_queries"):
+        # metric "ip" at the small end of the fp32 range, the shape of gauss_256: max|q| just above / just below 127 / FLT_MAX
+        # (where the query block's int8 scale is next to FLT_MAX, or overflows and falls back to 1), and queries whose every
+        # element is an fp32 subnormal.  q16 is all zeros: the whole canonical score is error, and eps has to cover it.
+        c["metric"] = "ip"
+        d, n = 256, FIRST + 300
+        X = rng.standard_normal((n, d)).astype(np.float32)
+        Q = rng.standard_normal((8, d))
+        if name == "tiny_queries":
+            edge = 127.0 / float(np.finfo(np.float32).max)
+            Q = (Q * (np.where(np.arange(8) % 2 == 0, edge * 1.01, edge * 0.99) / np.abs(Q).max(axis=1))[:, None]).astype(np.float32)
+            assert (np.abs(Q).max(axis=1)[::2] > edge).all() and (np.abs(Q).max(axis=1)[1::2] < edge).all()
+        else:
+            Q = (Q * 1e-42).astype(np.float32)
+            assert Q.any() and np.abs(Q).max() < np.finfo(np.float32).tiny
     elif name == "f32_rows_off_their_image":
         # fp32 storage, every row element on an fp16 midpoint: ||row - image|| is the whole 2^-11 ||row|| that rho allows, and
         # the queries run along row - image of the heaviest rows
@@ -125,9 +140,10 @@ def _case(oracle, name):
 
 
 CASES = ["midpoints_ip", "midpoints_cosine", "dominant_4096", "gauss_256", "gauss_1088", "gauss_4096", "f32_rows_off_their_image",
-         "ip_scaled_queries", "l2_spread_f16", "l2_spread_f32"]
+         "ip_scaled_queries", "l2_spread_f16", "l2_spread_f32", "tiny_queries", "subnormal_queries"]
 LATER_CHUNKS = {"midpoints_ip": "fused128", "midpoints_cosine": "fused128", "gauss_256": "fused128",
-                "f32_rows_off_their_image": "fused128", "ip_scaled_queries": "fused128", "l2_spread_f16": "stored"}
+                "f32_rows_off_their_image": "fused128", "ip_scaled_queries": "fused128", "l2_spread_f16": "stored",
+                "tiny_queries": "fused128", "subnormal_queries": "fused128"}
 
 
 def _search_and_bounds(idx, Q, k):
