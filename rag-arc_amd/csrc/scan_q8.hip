@@ -17,7 +17,7 @@
 //   * Q8 (256 × D int8) lives in REGISTERS: wave w owns queries [32w, 32w+32) as the MFMA B operand
 //     (D/32 fragments × 4 VGPRs = 96 VGPRs at D = 768).
 //   * a tile = 32 corpus rows = 64·D contiguous bytes.  Each thread fetches D/128 16-byte chunks with
-//     plain global_load_dwordx4 (a wave reads 1 KiB contiguous), two tiles ahead, converts them to
+//     non-temporal global_load_dwordx4 (a wave reads 1 KiB contiguous), two tiles ahead, converts them to
 //     int8 with the tile's scale (4 v_pk_fma_f16 + 2 v_perm_b32 per chunk) and writes 8 bytes to the
 //     LDS int8 tile (row stride D+16: the 16-lane groups of the A-fragment ds_read_b128 then hit 16
 //     distinct bank groups).  Two LDS tiles: convert(t+1) overlaps MFMA(t); one barrier per tile.
@@ -82,6 +82,23 @@ template <bool B>
 struct Q8Flag { static constexpr bool value = B; };
 constexpr int Q8_DEEP_D = 384;  // rows up to this many dimensions run with four fetch groups in flight (see NG)
 
+// Cache policy of the row stream.  Every row byte is read once per scan, so the 16-byte row chunk loads of `fetch` are non-temporal
+// (global_load_dwordx4 ... nt): they bypass the CU's L1 and leave it to what IS re-read — tile metadata (eight waves),
+// thresholds and histogram words.  Only the chunk loads (the tile-0 redirect's among them: it goes through the same `fetch`);
+// everything else in a fetch group keeps the default policy.  In measurement builds ABL bit 262144 restores plain loads.
+// Measured, 100M rows, ms per scan plain -> non-temporal (profiles/q8nt_q8_nt_ab.txt): fp16 x 768 26.97-27.00 -> 26.31-26.34,
+// fp8 x 1024 28.72 -> 28.29, int8 shadow x 768 20.35 -> 20.03; the fetch + convert + barrier skeleton 6.39 -> 7.15 TB/s on fp16
+// rows.  No format is slower, so there is no per-format switch.
+// What did and did not stay as it was in the machine code (profiles/q8nt_codeobj_table.txt): the vector-memory instructions and
+// their order are those of the plain-load build in all 16 instantiations, no scratch; tests/test_codeobj_q8_stream.py asserts
+// that `nt` sits on exactly the row chunk loads and that nothing spills — it checks no wait.  The counted waits are NOT all the
+// same: the vector-typed load moved register allocation, and the waits at group B's loop header are one step tighter in
+// <768,0> (vmcnt(2), vmcnt(1) -> vmcnt(1), vmcnt(0)), <512,0>, <640,0> and <256,1> (which also uses 172 VGPRs instead of 178).
+// That header wait is for the fetch group issued before the matrix phase, a tile period earlier; but a vmcnt(0) there also
+// waits for any survivor flush (stores, histogram atomics) still queued behind it, once per iteration pair.  The headline
+// (N(0,1) rows, rare flushes) was measured on this code; clustered or survivor-heavy corpora were not.
+typedef uint32_t q8_u32x4 __attribute__((ext_vector_type(4)));
+
 // Row stride of the int8 tile.  32x32x32 form (fp16 rows): D + 16 — the 16-lane groups of the A-fragment ds_read_b128 hit
 // 16 distinct bank groups.  16x16x64 form (fp8 / shadow rows, round 3): lane l reads row l & 15, 16-byte k quarter l >> 4;
 // with D + 16 the hardware's ds_read_b128 lane groups ({0-3, 12-15, 20-27}, ...) put two lanes on one bank group in EVERY
@@ -129,6 +146,7 @@ __device__ __forceinline__ int q8_all16(const q8_i32x16& a) {
 // 256 = no ping-pong between the wave groups, 512 = barrier at the end of the iteration where EB would put it behind the matrix phase, 1024 = s_memtime timeline of workgroup 0 into p.dbg,
 // 131072 = fp8 / shadow form: only the first two k steps' A fragments are read from LDS (the MFMAs reuse them: what the other 7/8 of the ds_read_b128 cost),
 // 65536 = waves 4-7 issue no MFMAs (fp8 / shadow form: half the matrix work per CU, everything else unchanged — round 5's overlap question),
+// 262144 = plain row chunk loads (the policy before the non-temporal row stream; results are right),
 // 16384 = every survivor updates the histogram, 4096 = survivors walked per lane (no LDS transposition), 8192 = parked scores walked at once (no batching), 2048 = fast path carries the position of the best score along (the earlier form; 0.5 % slower at 100M rows)
 //
 // Vector-memory discipline.  The prefetched tile registers are consumed with counted waits
@@ -152,6 +170,7 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
   constexpr int CPT = 32 * CPR / Q8_THREADS;  // chunks per thread per tile
   constexpr int MSTRIDE = FMT == 1 ? RARC_QMETA_F8_STRIDE : RARC_QMETA_STRIDE;  // floats of metadata per tile
   constexpr int TCH = 32 * CPR;       // chunks per tile
+  constexpr bool NT_ROWS = !(ABL & 262144);  // (the row stream's cache policy, above)
 
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -272,7 +291,12 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
     __builtin_amdgcn_sched_barrier(0);
     const uint4* src = p.corpus + (size_t)tile * TCH + tid;
 #pragma unroll
-    for (int j = 0; j < CPT; ++j) f.c[j] = src[j * Q8_THREADS];
+    for (int j = 0; j < CPT; ++j) {
+      if constexpr (NT_ROWS)   // (uint4 is a struct: the builtin wants a vector type)
+        f.c[j] = __builtin_bit_cast(uint4, __builtin_nontemporal_load((const q8_u32x4*)(src + j * Q8_THREADS)));
+      else
+        f.c[j] = src[j * Q8_THREADS];
+    }
   };
   uint32_t opaque_zero = 0;
   asm volatile("" : "+v"(opaque_zero));  // a zero the compiler cannot fold (FMT 2, see convert_chunk)
@@ -763,8 +787,11 @@ static int launch_scan_q8(const ScanQ8Params& p, int grid, hipStream_t s) {
   }
 #ifdef RARC_Q8_ABLATIONS
   // (measurement builds only: RARC_Q8_ABL selects an ablated instantiation of the two headline shapes — results are wrong)
-  if constexpr (ABL == 0 && ((D == 1024 && FMT == 1) || (D == 768 && FMT == 0))) {
+  if constexpr (ABL == 0 && ((D == 1024 && FMT == 1) || (D == 768 && FMT == 0) || (D == 768 && FMT == 2))) {
     static const int abl = getenv("RARC_Q8_ABL") ? atoi(getenv("RARC_Q8_ABL")) : 0;
+    // the row stream's cache policy, A/B in one binary (tools/q8_abl.sh): plain row loads under the full kernel and under the skeleton
+    if (abl == 262144) return launch_scan_q8<D, FMT, 262144>(p, grid, s);
+    if (abl == 262149) return launch_scan_q8<D, FMT, 262149>(p, grid, s);
     if (abl == 1) return launch_scan_q8<D, FMT, 1>(p, grid, s);
     if (abl == 4) return launch_scan_q8<D, FMT, 4>(p, grid, s);
     if (abl == 5) return launch_scan_q8<D, FMT, 5>(p, grid, s);

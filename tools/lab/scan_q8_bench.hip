@@ -1,18 +1,20 @@
 // tools/lab/scan_q8_bench.hip — ablation timing of the int8-prefilter scan kernel (development tool).
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off tools/lab/scan_q8_bench.hip -o tools/scan_q8_bench
+// ABL 262144 = plain row loads; 5 = the fetch + convert + barrier skeleton (no MFMAs, no pruning); 262149 = both
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-#include "../rag-arc_amd/csrc/scan_f16.hip"
-#include "../rag-arc_amd/csrc/scan_q8.hip"
-#include "../rag-arc_amd/csrc/quant.hip"
-#include "../rag-arc_amd/csrc/prep.hip"
-#include "../rag-arc_amd/csrc/finalize.hip"
+#include "../../rag-arc_amd/csrc/scan_f16.hip"
+#include "../../rag-arc_amd/csrc/scan_q8.hip"
+#include "../../rag-arc_amd/csrc/quant.hip"
+#include "../../rag-arc_amd/csrc/prep.hip"
+#include "../../rag-arc_amd/csrc/finalize.hip"
 void rarc_set_error(const char* fmt, ...) { (void)fmt; }
 void rarc_roctx_push(const char*) {}
 void rarc_roctx_pop() {}
 bool rarc_prof_next(hipEvent_t*, hipEvent_t*) { return false; }
+RarcLaunchExtras& rarc_launch_extras() { static thread_local RarcLaunchExtras x{}; return x; }
 
 #ifndef BD
 #define BD 768
@@ -66,8 +68,10 @@ int main(int argc, char** argv) {
   { unsigned long long* d; hipMalloc(&d, 65536); hipMemset(d, 0, 65536); p.dbg = d; }
   int grid = 256;
   const double gb = (double)N * D * 2 / 1e9;
-#define RUN(A) { float us = run<A>(p, grid, 6, corpus, N, qb, KP, ws); printf("ABL=%2d  %8.1f us  %6.2f TB/s\n", A, us, gb / us * 1e3); }
+#define RUN(A) { float us = run<A>(p, grid, 6, corpus, N, qb, KP, ws); printf("ABL=%6d  %8.1f us  %6.2f TB/s\n", A, us, gb / us * 1e3); }
   RUN(0) RUN(0) RUN(256) RUN(1) RUN(257)
+  // the row stream's cache policy: non-temporal (0, 5) against plain (262144, 262149) row loads, alternated, two rounds
+  for (int round = 0; round < 2; ++round) { RUN(0) RUN(262144) RUN(5) RUN(262149) }
   for (int v = 0; v < 1; ++v) { if (v == 0) run<1024>(p, grid, 1, corpus, N, qb, KP, ws); else run<1025>(p, grid, 1, corpus, N, qb, KP, ws);
     std::vector<unsigned long long> h(8192); hipMemcpy(h.data(), p.dbg, 65536, hipMemcpyDeviceToHost);
     printf("\ntimeline wg0 (%s), shader cycles relative to wave0 stamp0 of the iteration:  start  mfma+conv  pruned  fetched  barrier_out | next_start\n", v ? "no prune" : "full");
@@ -81,7 +85,7 @@ int main(int argc, char** argv) {
     for (int rep = 0; rep < 6; ++rep) {
       if (rep >= 3) { run<0>(p, grid, 1, corpus, N, qb, KP, ws); printf("(after a scan) "); }
       hipEventRecord(f0, 0);
-      rarc_finalize_q8_launch(corpus, nullptr, 0, D, qb.q32, qb.eps8, 256, K, 0, ws, CAP, grid, oi, os, st, 0, false, qmeta, qb.hq);
+      rarc_finalize_q8_launch(corpus, nullptr, 0, D, qb.q32, qb.eps8, 256, K, 0, ws, CAP, grid, oi, os, st, 0, false, qmeta, qb.hq, qb.eps16);
       hipEventRecord(f1, 0); hipEventSynchronize(f1); float ms; hipEventElapsedTime(&ms, f0, f1);
       unsigned long long h[16 + 1024]; hipMemcpy(h, fd, sizeof(h), hipMemcpyDeviceToHost);
       { double s1 = 0, s2 = 0; unsigned long long m1 = 0, m2 = 0, tmax = 0; int qmax = 0;
