@@ -715,6 +715,36 @@ int rarc_strike_rows(const int64_t* d_ids, const float* d_scores, int nq, int kp
                      int64_t id_base, int k, int l2, int64_t* d_out_ids, float* d_out_scores, uint32_t* d_count, void* stream);
 
 /*
+ * The same two with the filter chosen PER QUERY: the queries of concurrent callers, each with a filter of its own, in one call
+ * (FlatIndexF16.search_filtered_many).  Each query's answer is what rarc_search_rows / rarc_strike_rows give for its own list /
+ * mask, bit for bit.
+ *
+ * rarc_search_rows_grouped — the queries arrive sorted by group (queries that share one list), cut into TILES:
+ *   d_lists   the groups' lists, one behind the other (int64; each group's part strictly ascending, each entry in [0, n_rows):
+ *             the caller's contract as above).  May be NULL when m_max == 0
+ *   d_tiles   int64 [n_tiles][4] on the device = (first query, queries in the tile, offset of the group's list in d_lists, the
+ *             list's length m_g).  A tile holds queries of ONE group, at most QT of them: QT = 1 for nq == 1, 4 for
+ *             d_pad > 2048, else 8.  Every query of [0, nq) lies in exactly one tile; 1 <= n_tiles <= nq.  A group of more
+ *             than QT queries is several tiles over the same list; m_g == 0 answers padding
+ *   m_max     the largest m_g of the table (it decides how many slab rounds are launched)
+ * Everything else — limits, metric "l2", d_status, the workspace (rarc_search_rows_grouped_workspace_bytes(nq, k) ==
+ * rarc_search_rows_workspace_bytes(nq, k)) — as rarc_search_rows.  Launches per slab round: one score kernel over every
+ * tile, one select for the queries whose list goes on; then one select for every answer.
+ *
+ * rarc_strike_rows_grouped — rarc_strike_rows with d_bits_off int64 [nq]: query q is struck against the mask that starts at word
+ * d_bits_off[q] of d_bits (all masks of the call in one buffer, each uint32 [ceil(n_rows / 32)]); a negative entry keeps every
+ * row (an unfiltered query in the same call).  One launch.
+ */
+size_t rarc_search_rows_grouped_workspace_bytes(int nq, int k);
+int rarc_search_rows_grouped(const void* d_rows, int fmt, int64_t n_rows, int d_pad, const void* d_qblock, int nq,
+                             const int64_t* d_lists, const int64_t* d_tiles, int n_tiles, int64_t m_max, int k, int64_t id_base,
+                             const float* d_xn, int l2, int64_t* d_out_ids, float* d_out_scores, uint32_t* d_status, void* d_ws,
+                             size_t ws_bytes, void* stream);
+int rarc_strike_rows_grouped(const int64_t* d_ids, const float* d_scores, int nq, int kprime, const uint32_t* d_bits,
+                             const int64_t* d_bits_off, int64_t n_rows, int64_t id_base, int k, int l2, int64_t* d_out_ids,
+                             float* d_out_scores, uint32_t* d_count, void* stream);
+
+/*
  * All pairs (i < j) of n embeddings whose cosine reaches a threshold — the entity de-duplication of the reference's graph
  * store (encapsulation/database/graph_db/Base_Neo4j.py:538-583: sklearn.metrics.pairwise.cosine_similarity over every entity
  * embedding, then a python loop over i < j keeping similarity >= 0.95); SURVEY 8(f) rank 4.  The n x n matrix is never

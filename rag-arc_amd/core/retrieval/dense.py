@@ -56,20 +56,37 @@ class VectorStoreRetriever(BaseRetriever):
     def batch_invoke(self, inputs: List[str], **kwargs: Any) -> List[List[Document]]:
         """invoke() for a list of queries in ONE pass of the store (one encoder call, one scan per 256 queries) when the
         store can batch (`batch_similarity_search`: HipFlatVectorStore and its sharded form) and the search type is
-        "similarity"; otherwise query by query.  Element i equals invoke(inputs[i], **kwargs)."""
-        params: Dict[str, Any] = {**self.search_kwargs, **kwargs}
+        "similarity"; otherwise query by query.  Element i equals invoke(inputs[i], **kwargs).
+        `filters=` (a sequence, one entry per query: dict / callable / prepared handle / None) gives every query a filter of its
+        own — the tenants of a mixed batch share the store's pass; element i then equals invoke(inputs[i], filter=filters[i])."""
+        inputs = list(inputs)
+        filters = kwargs.pop("filters", self.search_kwargs.get("filters"))
+        params: Dict[str, Any] = {**{key: v for key, v in self.search_kwargs.items() if key != "filters"}, **kwargs}
         k = params.get("k", getattr(self, "k", 5))
         params["k"] = k
+        if filters is not None:
+            filters = list(filters)
+            if params.get("filter") is not None:
+                raise ValueError("pass filter= (one filter for the whole batch) or filters= (one per query), not both")
+            if len(filters) != len(inputs):
+                raise ValueError(f"filters= takes one entry per query: {len(inputs)} queries, {len(filters)} filters")
+
+        def one_by_one():
+            if filters is None:
+                return [self.invoke(q, **kwargs) for q in inputs]
+            return [self.invoke(q, **{**kwargs, "filter": f}) for q, f in zip(inputs, filters)]
+
         batched = getattr(self.vectorstore, "batch_similarity_search", None)
         if self.search_type != "similarity" or batched is None:
-            return [self.invoke(q, **kwargs) for q in inputs]
+            return one_by_one()
         try:
-            return [docs[:k] for docs in batched(list(inputs), **params)]
+            more = {} if filters is None else {"filters": filters}
+            return [docs[:k] for docs in batched(inputs, **params, **more)]
         except Exception as exc:
             # element i must equal invoke(inputs[i]): a query that cannot be answered raises from ITS invoke, the ones
             # before it are not lost to a caller that catches per query (MultiPathRetriever.batch_invoke does)
             logger.error("batched retrieval failed (%s): answering query by query", exc)
-            return [self.invoke(q, **kwargs) for q in inputs]
+            return one_by_one()
 
     # ------------------------------------------------------------------ async
     async def _aget_relevant_documents(self, query: str, **kwargs: Any) -> List[Document]:

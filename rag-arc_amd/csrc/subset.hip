@@ -251,3 +251,277 @@ extern "C" int rarc_strike_rows(const int64_t* d_ids, const float* d_scores, int
   RARC_HIP_CHECK(hipGetLastError());
   return RARC_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- grouped forms
+// One filter PER QUERY (FlatIndexF16.search_filtered_many; the store's `filters=` and its coalescing front): the queries of a
+// call arrive sorted by group, each group with a row list of its own, all lists concatenated in one buffer.
+//   rarc_search_rows_grouped   the tile table d_tiles (int64 [n_tiles][4] = first query, queries (<= QT), where the group's list
+//                              starts in d_lists, its length m_g) cuts the queries into tiles that never span two groups.  Per
+//                              slab round ONE subset_score_grouped_kernel over (row steps, tiles): a workgroup reads its tile's
+//                              entry, walks entries [round slab, (round + 1) slab) of its group's list — if the list reaches
+//                              that far — and writes keys behind what the query keeps.  A slab is longer than any k, so every
+//                              round but a group's last leaves more than k keys: a query keeps 0 keys before round 0 and k
+//                              before any other, and both follow from the table — nothing is uploaded per round.  The select
+//                              between rounds runs for the queries whose list goes on; ONE last select answers every query over
+//                              its own count (a group that ended earlier has kept its keys untouched until then).
+//   rarc_strike_rows_grouped   strike_rows_kernel with the mask chosen per query: d_bits_off[q] = the word of d_bits at which
+//                              query q's mask starts, negative = keep every row (an unfiltered caller in the same batch).
+// Same arithmetic as above (canon_topk.h), same keys: each query's answer is rarc_search_rows's for its list, bit for bit.
+namespace {
+static_assert(SUB_SLAB_MIN > SUB_KMAX, "a full slab must leave more than k keys: sub_round_kept counts on it");
+
+// what a query holds when round `round` of its list begins, and how many list entries that round adds
+__device__ __forceinline__ uint32_t sub_round_kept(uint32_t round, uint32_t k) { return round ? k : 0u; }
+__device__ __forceinline__ uint32_t sub_round_n(int64_t m, uint32_t round, uint32_t slab) {
+  const int64_t left = m - (int64_t)round * (int64_t)slab;
+  return left <= 0 ? 0u : (left < (int64_t)slab ? (uint32_t)left : slab);
+}
+
+// the walk of subset_score_kernel for QN staged queries (query t of the tile is query q0 + t of the call)
+template <bool F32ROWS, int QN>
+__device__ __forceinline__ void sub_walk(const float* s_q, uint4* s_stage, const void* __restrict__ rows, int d_pad, int q0, int cnt,
+                                         const int64_t* __restrict__ list, uint32_t n_list, uint64_t* __restrict__ keys,
+                                         uint32_t stride, uint32_t kept, const float* __restrict__ xn, const float* __restrict__ qn) {
+  const int j = threadIdx.x & 7;
+  uint4* stage = s_stage + (threadIdx.x & ~7);
+  for (uint32_t i0 = blockIdx.x * 32; i0 < n_list; i0 += gridDim.x * 32) {
+    const uint32_t i = i0 + (threadIdx.x >> 3);
+    const bool live = i < n_list;
+    const uint32_t row = (uint32_t)list[live ? i : n_list - 1];
+    float s[QN];
+    wide_canon_dot8n<F32ROWS, QN>(s_q, d_pad, rows, (size_t)row, d_pad, j, stage, s);
+    if (live && j == 0) {
+      const float xr = xn ? xn[row] : 0.f;
+#pragma unroll
+      for (int t = 0; t < QN; ++t)
+        if (t < cnt)
+          keys[(size_t)(q0 + t) * stride + kept + i] = rarc_candkey(xn ? wide_l2_neg_dist(qn[q0 + t], xr, s[t]) : s[t], row);
+    }
+  }
+}
+
+// keys[q][kept + i] = key of (query q, row list_g[round slab + i]) for the queries q of tile blockIdx.y and its group g.
+// Every exit and branch below depends on the tile's entry and blockIdx only: a workgroup takes it as a whole.
+template <bool F32ROWS, int QT>
+__global__ __launch_bounds__(256) void subset_score_grouped_kernel(const void* __restrict__ rows, int d_pad, const float* __restrict__ q32,
+                                                                   int nq, const int64_t* __restrict__ lists,
+                                                                   const int64_t* __restrict__ tiles, uint32_t round, uint32_t slab,
+                                                                   uint32_t k, uint64_t* __restrict__ keys, uint32_t stride,
+                                                                   const float* __restrict__ xn, const float* __restrict__ qn) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* s_q = (float*)smem;                                // [QT][d_pad]
+  __shared__ uint4 s_stage[256];
+  const int64_t* tile = tiles + 4 * (size_t)blockIdx.y;
+  const int64_t q0l = tile[0];
+  const uint32_t n_list = sub_round_n(tile[3], round, slab);
+  if (q0l < 0 || q0l >= nq || blockIdx.x * 32u >= n_list) return;       // this group's list ended in an earlier round
+  const int q0 = (int)q0l;
+  int cnt = (int)(tile[1] < QT ? tile[1] : QT);
+  cnt = cnt < nq - q0 ? cnt : nq - q0;
+  if (cnt < 1) return;
+  const int staged = cnt == 1 ? 1 : QT;                     // a tile of one query (256 tenants, one query each) is a gather
+  for (int i = threadIdx.x; i < staged * d_pad; i += 256) s_q[i] = i / d_pad < cnt ? q32[(size_t)q0 * d_pad + i] : 0.f;
+  __syncthreads();
+  const int64_t* list = lists + tile[2] + (int64_t)round * (int64_t)slab;
+  const uint32_t kept = sub_round_kept(round, k);
+  if (QT > 1 && cnt == 1) sub_walk<F32ROWS, 1>(s_q, s_stage, rows, d_pad, q0, 1, list, n_list, keys, stride, kept, xn, qn);
+  else sub_walk<F32ROWS, QT>(s_q, s_stage, rows, d_pad, q0, cnt, list, n_list, keys, stride, kept, xn, qn);
+}
+
+// subset_select_kernel with the count of every query worked out from its group's m.  last == 0: behind round `round`, for the
+// queries whose list has a further round (k + slab keys -> the k best to the front); last != 0: every query's answer.
+template <bool L2>
+__global__ __launch_bounds__(1024) void subset_select_grouped_kernel(uint64_t* keys_all, uint32_t stride, const int64_t* __restrict__ tiles,
+                                                                     int n_tiles, uint32_t round, uint32_t slab, uint32_t k, int last,
+                                                                     int64_t id_base, int64_t* out_ids, float* out_scores,
+                                                                     uint32_t* status) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint64_t* s_top = (uint64_t*)smem;                       // [pow2 >= min(k, c)]
+  __shared__ uint32_t s_hist[256];
+  __shared__ uint32_t s_pick[2];
+  __shared__ uint32_t s_cnt[2];
+  __shared__ long long s_m;
+  const uint32_t q = blockIdx.x;
+  if (threadIdx.x == 0) s_m = 0;
+  __syncthreads();
+  for (int i = threadIdx.x; i < n_tiles; i += blockDim.x) {          // the one tile that holds this query
+    const int64_t* tile = tiles + 4 * (size_t)i;
+    if ((int64_t)q >= tile[0] && (int64_t)q < tile[0] + tile[1]) s_m = tile[3];
+  }
+  __syncthreads();
+  const int64_t m = s_m;
+  const int64_t rounds = (m + slab - 1) / slab;
+  uint64_t* keys = keys_all + (size_t)q * stride;
+  uint32_t c;
+  if (!last) {
+    if ((int64_t)round + 1 >= rounds) return;              // (the whole workgroup: m is the same in every thread)
+    c = sub_round_kept(round, k) + slab;
+  } else {
+    c = rounds <= 0 ? 0u : sub_round_kept((uint32_t)(rounds - 1), k) + sub_round_n(m, (uint32_t)(rounds - 1), slab);
+  }
+  const uint32_t kk = k < c ? k : c;
+  uint32_t pow2 = 1;
+  while (pow2 < kk) pow2 <<= 1;
+  wide_topk_keys(keys, c, kk, pow2, s_top, s_hist, s_pick, s_cnt, last != 0);
+  if (!last) {
+    for (uint32_t i = threadIdx.x; i < kk; i += blockDim.x) keys[i] = s_top[i];
+    return;
+  }
+  wide_write_topk<L2>(s_top, kk, k, id_base, out_ids + (size_t)q * k, out_scores + (size_t)q * k);
+  if (q == 0)
+    for (uint32_t i = threadIdx.x; i < RARC_MAX_QUERIES; i += blockDim.x) status[i] = RARC_Q_OK;
+}
+
+// strike_rows_kernel, the mask of query q starting at word bits_off[q] of `bits` (negative: every row stays)
+__global__ __launch_bounds__(256) void strike_rows_grouped_kernel(const int64_t* __restrict__ ids, const float* __restrict__ scores,
+                                                                  int kp, const uint32_t* __restrict__ bits_all,
+                                                                  const int64_t* __restrict__ bits_off, int64_t n_rows, int64_t id_base,
+                                                                  int k, float pad, int64_t* __restrict__ out_ids,
+                                                                  float* __restrict__ out_scores, uint32_t* __restrict__ count) {
+  __shared__ uint32_t s_wave[4];
+  const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int64_t off = bits_off[q];
+  const uint32_t* bits = bits_all + (off < 0 ? 0 : off);
+  uint32_t base = 0;
+  for (int i0 = 0; i0 < kp && base < (uint32_t)k; i0 += 256) {      // (base is the same in every thread)
+    const int i = i0 + tid;
+    bool ok = false;
+    int64_t id = -1;
+    float s = pad;
+    if (i < kp) {
+      id = ids[(size_t)q * kp + i];
+      s = scores[(size_t)q * kp + i];
+      const int64_t r = id - id_base;
+      ok = id >= 0 && r >= 0 && r < n_rows && (off < 0 || ((bits[r >> 5] >> (r & 31)) & 1u));
+    }
+    const unsigned long long b = __builtin_amdgcn_ballot_w64(ok);
+    if (lane == 0) s_wave[w] = (uint32_t)__builtin_popcountll(b);
+    __syncthreads();
+    uint32_t pos = base + (uint32_t)__builtin_popcountll(b & ((1ull << lane) - 1ull));
+    for (int v = 0; v < w; ++v) pos += s_wave[v];
+    if (ok && pos < (uint32_t)k) {
+      out_ids[(size_t)q * k + pos] = id;
+      out_scores[(size_t)q * k + pos] = s;
+    }
+    base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    __syncthreads();
+  }
+  for (uint32_t i = base + tid; i < (uint32_t)k; i += 256) {
+    out_ids[(size_t)q * k + i] = -1;
+    out_scores[(size_t)q * k + i] = pad;
+  }
+  if (tid == 0) count[q] = base < (uint32_t)k ? base : (uint32_t)k;
+}
+
+template <bool F32ROWS, int QT>
+int sub_launch_score_grouped(const void* d_rows, int d_pad, const float* q32, int nq, const int64_t* lists, const int64_t* tiles,
+                             int n_tiles, uint32_t n_max, uint32_t round, uint32_t slab, uint32_t k, uint64_t* keys, uint32_t stride,
+                             const float* xn, const float* qn, hipStream_t s) {
+  const size_t lds = (size_t)QT * d_pad * 4;
+  static RarcPerDevice attr_done;
+  if (size_t& done = attr_done.cur(); !done) {
+    RARC_HIP_CHECK(hipFuncSetAttribute((const void*)subset_score_grouped_kernel<F32ROWS, QT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       65536));
+    done = 1;
+  }
+  // as sub_launch_score, the row steps those of the longest list still walking: a shorter one's spare workgroups leave at once
+  const uint32_t steps = (n_max + 31) / 32;
+  uint32_t gx = 2048 / (uint32_t)n_tiles;
+  gx = gx < 8 ? 8 : gx;
+  gx = gx > steps ? steps : gx;
+  hipLaunchKernelGGL((subset_score_grouped_kernel<F32ROWS, QT>), dim3(gx, n_tiles), dim3(256), lds, s, d_rows, d_pad, q32, nq, lists,
+                     tiles, round, slab, k, keys, stride, xn, qn);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+template <bool L2>
+int sub_launch_select_grouped(uint64_t* keys, uint32_t stride, const int64_t* tiles, int n_tiles, uint32_t round, uint32_t slab, int k,
+                              int last, int nq, int64_t id_base, int64_t* out_ids, float* out_scores, uint32_t* status, hipStream_t s) {
+  static RarcPerDevice attr_done;
+  if (size_t& done = attr_done.cur(); !done) {
+    RARC_HIP_CHECK(hipFuncSetAttribute((const void*)subset_select_grouped_kernel<L2>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+    done = 1;
+  }
+  uint32_t pow2 = 1;
+  while (pow2 < (uint32_t)k) pow2 <<= 1;
+  hipLaunchKernelGGL(subset_select_grouped_kernel<L2>, dim3(nq), dim3(1024), (size_t)pow2 * 8, s, keys, stride, tiles, n_tiles, round,
+                     slab, (uint32_t)k, last, id_base, out_ids, out_scores, status);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+}  // namespace
+
+extern "C" size_t rarc_search_rows_grouped_workspace_bytes(int nq, int k) { return rarc_search_rows_workspace_bytes(nq, k); }
+
+extern "C" int rarc_search_rows_grouped(const void* d_rows, int fmt, int64_t n_rows, int d_pad, const void* d_qblock, int nq,
+                                        const int64_t* d_lists, const int64_t* d_tiles, int n_tiles, int64_t m_max, int k,
+                                        int64_t id_base, const float* d_xn, int l2, int64_t* d_out_ids, float* d_out_scores,
+                                        uint32_t* d_status, void* d_ws, size_t ws_bytes, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_rows && d_qblock && d_tiles && d_out_ids && d_out_scores && d_status && d_ws && (d_lists || m_max == 0), RARC_E_INVALID,
+               "rarc_search_rows_grouped: null pointer");
+  RARC_REQUIRE(fmt == 0 || fmt == 2, RARC_E_INVALID, "rarc_search_rows_grouped: fmt 0 (fp16 rows) or 2 (fp32 rows), got %d", fmt);
+  RARC_REQUIRE(!l2 || d_xn, RARC_E_INVALID,
+               "rarc_search_rows_grouped: null pointer (d_xn: metric l2 needs the rows' squared norms, rarc_row_sqnorms)");
+  RARC_REQUIRE(d_pad > 0 && d_pad % RARC_DIM_ALIGN == 0 && d_pad <= 4096, RARC_E_UNSUPPORTED,
+               "rarc_search_rows_grouped: padded dim %d unsupported (multiple of %d, <= 4096)", d_pad, RARC_DIM_ALIGN);
+  RARC_REQUIRE(nq >= 1 && nq <= RARC_MAX_QUERIES && k >= 1 && k <= SUB_KMAX, RARC_E_INVALID,
+               "rarc_search_rows_grouped: need 1 <= nq <= %d, 1 <= k <= %d (nq=%d k=%d)", RARC_MAX_QUERIES, SUB_KMAX, nq, k);
+  RARC_REQUIRE(n_tiles >= 1 && n_tiles <= nq, RARC_E_INVALID,
+               "rarc_search_rows_grouped: need 1 <= n_tiles <= nq: every query in one tile (n_tiles=%d nq=%d)", n_tiles, nq);
+  RARC_REQUIRE(n_rows >= 0 && n_rows < (int64_t)0xffffff00ll && m_max >= 0 && m_max <= n_rows, RARC_E_INVALID,
+               "rarc_search_rows_grouped: need 0 <= m_max <= n_rows < 2^32 - 256 (m_max=%lld n_rows=%lld)", (long long)m_max,
+               (long long)n_rows);
+  char* wsb = (char*)(((uintptr_t)d_ws + 255) & ~(uintptr_t)255);
+  RARC_REQUIRE(wsb + sub_ws_bytes(nq, k) <= (char*)d_ws + ws_bytes, RARC_E_WORKSPACE,
+               "rarc_search_rows_grouped: workspace of %zu bytes, %zu needed", ws_bytes, sub_ws_bytes(nq, k) + 256);
+  hipStream_t s = (hipStream_t)stream;
+  float* qn = (float*)wsb;                                  // [256]
+  uint64_t* keys = (uint64_t*)(wsb + 1024);                 // [nq][k + slab]
+  const int slab = sub_slab_rows(nq, k);
+  const uint32_t stride = (uint32_t)(k + slab);
+  const RarcQb qb = rarc_qb_carve(d_qblock, d_pad);
+  const float* xn = l2 ? d_xn : nullptr;
+  if (l2 && m_max > 0) {
+    hipLaunchKernelGGL(subset_qn_kernel, dim3((nq + 31) / 32), dim3(256), 0, s, qb.q32, d_pad, nq, qn);
+    RARC_HIP_CHECK(hipGetLastError());
+  }
+  const bool wide_rows = d_pad > 2048;
+  int rc;
+  uint32_t round = 0;
+  for (int64_t at = 0; at < m_max; at += slab, ++round) {
+    const uint32_t n = (uint32_t)(m_max - at < slab ? m_max - at : slab);
+#define SUB_SCORE(F32, QT) \
+  sub_launch_score_grouped<F32, QT>(d_rows, d_pad, qb.q32, nq, d_lists, d_tiles, n_tiles, n, round, (uint32_t)slab, (uint32_t)k, keys, stride, xn, qn, s)
+    if (fmt == 2) rc = nq == 1 ? SUB_SCORE(true, 1) : (wide_rows ? SUB_SCORE(true, 4) : SUB_SCORE(true, 8));
+    else rc = nq == 1 ? SUB_SCORE(false, 1) : (wide_rows ? SUB_SCORE(false, 4) : SUB_SCORE(false, 8));
+#undef SUB_SCORE
+    if (rc != RARC_OK) return rc;
+    if (at + slab < m_max) {                              // some list goes on: its queries keep their k best
+      rc = l2 ? sub_launch_select_grouped<true>(keys, stride, d_tiles, n_tiles, round, (uint32_t)slab, k, 0, nq, id_base, d_out_ids,
+                                                d_out_scores, d_status, s)
+              : sub_launch_select_grouped<false>(keys, stride, d_tiles, n_tiles, round, (uint32_t)slab, k, 0, nq, id_base, d_out_ids,
+                                                 d_out_scores, d_status, s);
+      if (rc != RARC_OK) return rc;
+    }
+  }
+  return l2 ? sub_launch_select_grouped<true>(keys, stride, d_tiles, n_tiles, 0, (uint32_t)slab, k, 1, nq, id_base, d_out_ids, d_out_scores,
+                                              d_status, s)
+            : sub_launch_select_grouped<false>(keys, stride, d_tiles, n_tiles, 0, (uint32_t)slab, k, 1, nq, id_base, d_out_ids, d_out_scores,
+                                               d_status, s);
+}
+
+extern "C" int rarc_strike_rows_grouped(const int64_t* d_ids, const float* d_scores, int nq, int kprime, const uint32_t* d_bits,
+                                        const int64_t* d_bits_off, int64_t n_rows, int64_t id_base, int k, int l2, int64_t* d_out_ids,
+                                        float* d_out_scores, uint32_t* d_count, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_ids && d_scores && d_bits && d_bits_off && d_out_ids && d_out_scores && d_count, RARC_E_INVALID,
+               "rarc_strike_rows_grouped: null pointer");
+  RARC_REQUIRE(nq >= 1 && k >= 1 && kprime >= 1 && n_rows >= 0, RARC_E_INVALID,
+               "rarc_strike_rows_grouped: need nq >= 1, k >= 1, kprime >= 1 (nq=%d k=%d kprime=%d)", nq, k, kprime);
+  hipLaunchKernelGGL(strike_rows_grouped_kernel, dim3(nq), dim3(256), 0, (hipStream_t)stream, d_ids, d_scores, kprime, d_bits,
+                     d_bits_off, n_rows, id_base, k, l2 ? INFINITY : -INFINITY, d_out_ids, d_out_scores, d_count);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}

@@ -122,15 +122,16 @@ class _QueryCoalescer:
     BURST_SHARE = 0.75       # ... and in any case after this share of the last launch's duration
 
     class _Item:
-        __slots__ = ("payload", "k", "result", "error", "done")
+        __slots__ = ("payload", "k", "flt", "result", "error", "done")
 
-        def __init__(self, payload, k):
-            self.payload, self.k, self.result, self.error, self.done = payload, k, None, None, False
+        def __init__(self, payload, k, flt=None):
+            self.payload, self.k, self.flt, self.result, self.error, self.done = payload, k, flt, None, None, False
 
-    def submit(self, payload, k: int):
-        """payload: a query text or a query vector; returns that query's [(Document, score)], at most k of them (the
-        leader of a batch turns the whole answer into Documents in one native call: a waiter wakes up to a finished list)."""
-        item = self._Item(payload, int(k))
+    def submit(self, payload, k: int, flt=None):
+        """payload: a query text or a query vector, flt: that caller's filter (None = unfiltered); returns that query's
+        [(Document, score)], at most k of them (the leader of a batch turns the whole answer into Documents in one native
+        call: a waiter wakes up to a finished list)."""
+        item = self._Item(payload, int(k), flt)
         while True:
             with self.cv:
                 if item not in self.queue and not item.done:
@@ -159,7 +160,7 @@ class _QueryCoalescer:
                 del self.queue[: self.max_batch]
             t_launch = time.perf_counter()
             try:
-                results = self.run_batch([it.payload for it in batch], max(it.k for it in batch))
+                results = self.run_batch([it.payload for it in batch], max(it.k for it in batch), [it.flt for it in batch])
                 for it, pairs in zip(batch, results):
                     it.result = pairs[: it.k]
             except BaseException as exc:  # noqa: BLE001 - every waiter of the batch must learn of it
@@ -171,7 +172,7 @@ class _QueryCoalescer:
                     # it would have without the coalescer: the batch is answered again, one query per launch
                     for it in batch:
                         try:
-                            it.result = self.run_batch([it.payload], it.k)[0][: it.k]
+                            it.result = self.run_batch([it.payload], it.k, [it.flt])[0][: it.k]
                         except BaseException as exc_one:  # noqa: BLE001
                             it.error = exc_one
             finally:
@@ -271,7 +272,7 @@ class _RowsGuard:
 
 
 class _AsyncFront:
-    """The coalescer for coroutines: callers enqueue (payload, k, future) and await; one worker thread, started when there is
+    """The coalescer for coroutines: callers enqueue ((payload, filter), k, future) and await; one worker thread, started when there is
     work and gone after a second without any, answers up to `max_batch` of them per scan."""
 
     IDLE_S = 1.0
@@ -288,13 +289,13 @@ class _AsyncFront:
         self.last_batch = 1      # callers served by the previous launch, and how long it took
         self.last_scan_s = 0.0
 
-    async def submit(self, payload, k: int):
+    async def submit(self, payload, k: int, flt=None):
         import asyncio
 
         loop = asyncio.get_running_loop()
         fut = loop.create_future()
         with self.cv:
-            self.queue.append((payload, int(k), fut, loop))
+            self.queue.append(((payload, flt), int(k), fut, loop))
             if self.worker is None or not self.worker.is_alive():
                 self.worker = threading.Thread(target=self._work, name="rarc-async-front", daemon=True)
                 self.worker.start()
@@ -352,12 +353,14 @@ class _AsyncFront:
             t_launch = time.perf_counter()
             outcomes = []
             try:
-                results = self.run_batch([p for p, _, _, _ in batch], max(k for _, k, _, _ in batch))
+                results = self.run_batch([p for (p, _), _, _, _ in batch], max(k for _, k, _, _ in batch),
+                                         [f for (_, f), _, _, _ in batch])
                 outcomes = [(pairs[:k], None) for (_, k, _, _), pairs in zip(batch, results)]
-            except Exception:  # noqa: BLE001 - one caller's bad query fails that caller only: again, one by one
-                for p, k, _, _ in batch:
+            except Exception:  # noqa: BLE001 - one caller's bad query (or bad / stale filter) fails that caller only: one by one
+                outcomes = []
+                for (p, f), k, _, _ in batch:
                     try:
-                        outcomes.append((self.run_batch([p], k)[0][:k], None))
+                        outcomes.append((self.run_batch([p], k, [f])[0][:k], None))
                     except Exception as exc_one:  # noqa: BLE001
                         outcomes.append((None, exc_one))
             self.launches += 1
@@ -552,15 +555,13 @@ class HipFlatVectorStore(VectorStore):
         return [d for d, _ in self.similarity_search_with_score(query, k, **kwargs)]
 
     def similarity_search_with_score(self, query: str, k: int = 4, **kwargs: Any) -> List[Tuple[Document, float]]:
-        if self._checked_filter(kwargs.get("filter")) is not None:
-            if self.ntotal == 0:
-                return []
-            return self._filtered_answers(np.array([self.embedding.embed_query(query)]).astype(np.float32), k, kwargs["filter"], True)[0]
+        flt = self._checked_filter(kwargs.get("filter"))
         if self.ntotal == 0:
             return []
         if self._coalescer is not None and self._batch_embedder() is not None:
-            # text goes into the queue: the leader embeds the whole batch in one encoder call, then scans once
-            return self._coalescer.submit(query, min(k, self.ntotal))
+            # text goes into the queue: the leader embeds the whole batch in one encoder call, then scans once (a filtered
+            # caller too: the batch's filters go to search_filtered_many, one grouped search for all of them)
+            return self._coalescer.submit(query, min(k, self.ntotal), flt)
         return self.similarity_search_by_vector_with_score(self.embedding.embed_query(query), k, **kwargs)
 
     # -- async twins without a thread per call ------------------------------------------------------------------------
@@ -572,17 +573,17 @@ class HipFlatVectorStore(VectorStore):
     async def asimilarity_search_with_score(self, *args: Any, **kwargs: Any) -> List[Tuple[Document, float]]:
         query = args[0] if args else kwargs.get("query")
         k = args[1] if len(args) > 1 else kwargs.get("k", 4)
-        if (self._coalescer is None or not isinstance(query, str) or self._batch_embedder() is None or len(args) > 2
-                or kwargs.get("filter") is not None):       # (the front carries (query, k): a filtered call takes the sync path)
+        if self._coalescer is None or not isinstance(query, str) or self._batch_embedder() is None or len(args) > 2:
             return await super().asimilarity_search_with_score(*args, **kwargs)
+        flt = self._checked_filter(kwargs.get("filter"))       # (the front carries the caller's filter with its query)
         if self.ntotal == 0:
             return []
-        return await self._async_front().submit(query, min(int(k), self.ntotal))
+        return await self._async_front().submit(query, min(int(k), self.ntotal), flt)
 
     async def asimilarity_search(self, query: str, k: int = 4, **kwargs: Any) -> List[Document]:
-        if self._coalescer is None or self._batch_embedder() is None or kwargs.get("filter") is not None:
+        if self._coalescer is None or self._batch_embedder() is None:
             return await super().asimilarity_search(query, k, **kwargs)
-        return [d for d, _ in await self.asimilarity_search_with_score(query, k)]
+        return [d for d, _ in await self.asimilarity_search_with_score(query, k, filter=kwargs.get("filter"))]
 
     def _async_front(self) -> "_AsyncFront":
         front = self.__dict__.get("_afront")
@@ -594,15 +595,14 @@ class HipFlatVectorStore(VectorStore):
         return [d for d, _ in self.similarity_search_by_vector_with_score(embedding, k, **kwargs)]
 
     def similarity_search_by_vector_with_score(self, embedding, k: int = 4, **kwargs: Any):
-        if self._checked_filter(kwargs.get("filter")) is not None:
-            if self.ntotal == 0:
-                return []
-            return self._filtered_answers(np.array([embedding]).astype(np.float32), k, kwargs["filter"], True)[0]
+        flt = self._checked_filter(kwargs.get("filter"))
         if self.ntotal == 0:
             return []
-        k = min(k, self.ntotal)
         if self._coalescer is not None:
-            return self._coalescer.submit(np.asarray(embedding, dtype=np.float32), k)
+            return self._coalescer.submit(np.asarray(embedding, dtype=np.float32), min(k, self.ntotal), flt)
+        if flt is not None:
+            return self._filtered_answers(np.array([embedding]).astype(np.float32), k, flt, True)[0]
+        k = min(k, self.ntotal)
         qv = np.array([embedding]).astype(np.float32)
         with self._guard.shared():
             scores, rows = self.index.search(qv, k)
@@ -652,6 +652,66 @@ class HipFlatVectorStore(VectorStore):
             scores, rows = self.index.search_filtered(q, kk, rs)
             return self._map_batch(scores, rows, with_scores)
 
+    def _checked_filters(self, flt, filters, nq: int):
+        """`filters=` (one entry per query: dict / callable / RowSet / None) next to `filter=` (one for the batch): both is a
+        ValueError, so is a length other than the number of queries; every entry passes _checked_filter (the stores that
+        refuse `filter=` refuse this too, before any launch).  Returns the list, or None when `filters=` was not given or holds only None."""
+        if filters is None:
+            return None
+        if flt is not None:
+            raise ValueError("pass filter= (one filter for the whole batch) or filters= (one per query), not both")
+        filters = list(filters)
+        if len(filters) != int(nq):
+            raise ValueError(f"filters= takes one entry per query: {int(nq)} queries, {len(filters)} filters")
+        filters = [self._checked_filter(f) for f in filters]
+        return filters if any(f is not None for f in filters) else None        # (nothing but None: the unfiltered batch)
+
+    def _resolve_filters(self, filters) -> list:
+        """One RowSet (or None) per entry (caller holds the guard): equal dicts and identical callables / RowSets are resolved
+        ONCE — a python predicate over every metadata dict costs far more than the search."""
+        from ....hip.engine import RowSet
+
+        by_id: dict = {}
+        dicts: list = []                # (dict, RowSet): dicts are not hashable; a batch holds few distinct ones
+        out = []
+        for f in filters:
+            if f is None or isinstance(f, RowSet):
+                out.append(f)
+                continue
+            if id(f) not in by_id:
+                rs = next((r for d, r in dicts if d == f), None) if isinstance(f, dict) else None
+                if rs is None:
+                    rs = self._resolve_filter(f)
+                    if isinstance(f, dict):
+                        dicts.append((f, rs))
+                by_id[id(f)] = rs
+            out.append(by_id[id(f)])
+        return out
+
+    def _filtered_many(self, q, k: int, filters):
+        """(scores, rows, per-query k) of a search with one filter per query (caller holds the guard): ONE
+        search_filtered_many at the largest k any query can use; query i's answer is its first kks[i] = min(k, its matching
+        rows) entries — ntotal for an unfiltered one."""
+        if self.index is None or not hasattr(self.index, "search_filtered_many"):
+            raise NotImplementedError("this store's engine has no search with one filter per query")
+        rsets = self._resolve_filters(filters)
+        kks = [min(int(k), self.ntotal if rs is None else rs.m) for rs in rsets]
+        kk = max(kks) if kks else 0
+        if kk < 1:
+            return np.zeros((len(rsets), 0), np.float32), np.zeros((len(rsets), 0), np.int64), kks
+        scores, rows = self.index.search_filtered_many(q, kk, rsets)
+        return scores, rows, kks
+
+    def _filtered_many_answers(self, q, k: int, filters, with_scores: bool):
+        """Per query [(Document, score)] / [Document] for one filter per query: resolution and search under ONE shared hold
+        of the guard, as _filtered_answers; a query with fewer than k matches returns what there is (the padding rows of an
+        answer map to nothing)."""
+        with self._guard.shared():
+            scores, rows, kks = self._filtered_many(q, k, filters)
+            if rows.shape[1] == 0:
+                return [[] for _ in kks]
+            return [a[:kk] for a, kk in zip(self._map_batch(scores, rows, with_scores), kks)]
+
     def _to_documents(self, scores, rows) -> List[Tuple[Document, float]]:
         """[(Document, float(score))] of one query's answer, row -1 skipped (VectorStore_Faiss.py:265-272)."""
         return self._map_batch(np.asarray(scores)[None, :], np.asarray(rows)[None, :], True)[0]
@@ -676,8 +736,10 @@ class HipFlatVectorStore(VectorStore):
         (`embed_queries`); None otherwise (each caller then embeds its own query before queueing)."""
         return getattr(self.embedding, "embed_queries_device", None) or getattr(self.embedding, "embed_queries", None)
 
-    def _run_query_batch(self, payloads: Sequence, k: int):
-        """One scan for a batch of queries given as texts and / or vectors; returns [(Document, score)] x k per query."""
+    def _run_query_batch(self, payloads: Sequence, k: int, filters: Optional[Sequence] = None):
+        """One scan for a batch of queries given as texts and / or vectors; returns [(Document, score)] x k per query.
+        filters: the callers' filters, one per query (None = unfiltered) — a batch that carries any is ONE grouped filtered
+        search (search_filtered_many), each caller's answer cut at its own matching rows."""
         texts = [i for i, p in enumerate(payloads) if isinstance(p, str)]
         if texts and len(texts) == len(payloads) and hasattr(self.embedding, "embed_queries_device"):
             q = self.embedding.embed_queries_device([payloads[i] for i in texts])        # stays in HBM
@@ -689,6 +751,8 @@ class HipFlatVectorStore(VectorStore):
                 for i, v in zip(texts, emb):
                     vecs[i] = np.asarray(v, dtype=np.float32)
             q = np.stack([np.asarray(v, dtype=np.float32) for v in vecs])
+        if filters is not None and any(f is not None for f in filters):
+            return self._filtered_many_answers(q, k, list(filters), True)
         with self._guard.shared():
             scores, rows = self.index.search(q, min(k, self.ntotal))
             return self._map_batch(scores, rows, True)
@@ -744,13 +808,18 @@ class HipFlatVectorStore(VectorStore):
             self.timing[key] = self.timing.get(key, 0.0) + (now - t0)
         return now
 
-    def batch_search_by_vector(self, embeddings, k: int = 4, filter=None):      # noqa: A002
+    def batch_search_by_vector(self, embeddings, k: int = 4, filter=None, filters=None):      # noqa: A002
         """Many query vectors, one scan per 256.  Returns (scores fp32 [nq][k], row indices int64 [nq][k]); with `filter`
-        (one for the whole batch) k is clamped to the matching rows."""
+        (one for the whole batch) k is clamped to the matching rows; with `filters` (one per query, None = unfiltered) to the
+        most rows any query matches — a query with fewer has (-inf, -1) (metric "l2": (+inf, -1)) behind them."""
         self._checked_filter(filter)
+        filters = self._checked_filters(filter, filters, len(embeddings))
         if self.ntotal == 0:
             nq = len(embeddings)
             return np.zeros((nq, 0), np.float32), np.zeros((nq, 0), np.int64)
+        if filters is not None:
+            with self._guard.shared():
+                return self._filtered_many(embeddings, k, filters)[:2]
         if filter is not None:
             with self._guard.shared():
                 rs = self._resolve_filter(filter)
@@ -766,11 +835,12 @@ class HipFlatVectorStore(VectorStore):
             at += len(sc)
         return scores, rows
 
-    def _batch_answers(self, queries: Sequence[str], k: int, with_scores: bool, flt=None):
+    def _batch_answers(self, queries: Sequence[str], k: int, with_scores: bool, flt=None, filters=None):
         import time
 
         queries = list(queries)
         self._checked_filter(flt)
+        filters = self._checked_filters(flt, filters, len(queries))
         if self.ntotal == 0 or not queries:
             return [[] for _ in queries]
         t0 = time.perf_counter()
@@ -778,6 +848,8 @@ class HipFlatVectorStore(VectorStore):
         t0 = self._tick("embed_s", t0)
         if flt is not None:
             return self._filtered_answers(q, k, flt, with_scores)
+        if filters is not None:
+            return self._filtered_many_answers(q, k, filters, with_scores)
         out: list = []
         with self._guard.shared():
             for scores, rows in self._search_chunks(q, k):
@@ -789,11 +861,12 @@ class HipFlatVectorStore(VectorStore):
     def batch_similarity_search_with_score(self, queries: Sequence[str], k: int = 4, **kwargs: Any):
         """similarity_search_with_score for a list of queries: one encoder call (when the provider can batch), one scan per
         256 queries, each scan running while the answer before it becomes Documents.  Element i equals
-        similarity_search_with_score(queries[i], k).  `filter=`: one filter for the whole batch."""
-        return self._batch_answers(queries, k, True, kwargs.get("filter"))
+        similarity_search_with_score(queries[i], k).  `filter=`: one filter for the whole batch; `filters=`: one per query
+        (dict / callable / RowSet / None), element i then equals similarity_search_with_score(queries[i], k, filter=filters[i])."""
+        return self._batch_answers(queries, k, True, kwargs.get("filter"), kwargs.get("filters"))
 
     def batch_similarity_search(self, queries: Sequence[str], k: int = 4, **kwargs: Any) -> List[List[Document]]:
-        return self._batch_answers(queries, k, False, kwargs.get("filter"))
+        return self._batch_answers(queries, k, False, kwargs.get("filter"), kwargs.get("filters"))
 
     @property
     def coalesced_launches(self) -> Tuple[int, int]:

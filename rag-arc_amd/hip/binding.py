@@ -208,6 +208,11 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "rarc_strike_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
+    "rarc_search_rows_grouped_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "rarc_search_rows_grouped": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int64, c_int,
+                                         c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rarc_strike_rows_grouped": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "rarc_similar_pairs_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "rarc_similar_pairs": (c_int, [c_void_p, c_int64, c_int64, c_int, ctypes.c_double, c_void_p, c_size_t, c_int, c_void_p, c_void_p,
                                    c_int64, c_void_p, c_void_p, c_void_p]),

@@ -217,6 +217,56 @@ class RowSet:
         return rows
 
 
+# ---------------------------------------------------------------------------------------------------- one filter per query
+# The host side of FlatIndexF16.search_filtered_many (csrc/subset.hip, the grouped forms): pure functions, no device.
+def group_rowsets(rowsets) -> list:
+    """[(rowset or None, [positions])] of a sequence with one filter per query: queries that carry the SAME RowSet object (or
+    None) form one group; groups in order of first appearance, positions ascending."""
+    groups: dict = {}
+    for i, rs in enumerate(rowsets):
+        groups.setdefault(id(rs), (rs, []))[1].append(i)
+    return list(groups.values())
+
+
+def grouped_tile_queries(nq: int, d_pad: int) -> int:
+    """QT of rarc_search_rows_grouped (include/rarc.h): queries per tile for a call of nq queries of d_pad dimensions."""
+    return 1 if nq == 1 else (4 if d_pad > 2048 else 8)
+
+
+def build_tile_table(counts, ms, qt: int):
+    """The tile table of rarc_search_rows_grouped for queries sorted by group: group g has counts[g] >= 1 queries and a list
+    of ms[g] rows, the lists lying one behind the other.  Returns (tiles int64 [n_tiles][4] = (first query, queries <= qt,
+    list offset, m), list offsets int64 [groups]).  No tile spans two groups; the tiles cover every query once."""
+    ms = np.asarray(ms, dtype=np.int64).reshape(-1)
+    offs = np.concatenate([np.zeros(1, np.int64), np.cumsum(ms)[:-1]]) if ms.size else np.zeros(0, np.int64)
+    tiles, q0 = [], 0
+    for g, c in enumerate(counts):
+        if c < 1:
+            raise ValueError("a group has at least one query")
+        for s in range(0, int(c), int(qt)):
+            tiles.append((q0 + s, min(int(qt), int(c) - s), int(offs[g]), int(ms[g])))
+        q0 += int(c)
+    return np.asarray(tiles, dtype=np.int64).reshape(-1, 4), offs
+
+
+def filtered_many_plan(sizes, k: int, strategy: str, choose, kprime):
+    """The leg of every group of a search_filtered_many call.  sizes: per group (queries, m), m = None for the unfiltered
+    queries; choose(queries, k, m) is FlatIndexF16.filter_strategy, kprime(k, m) the k' an over-fetched search of that group
+    asks for.  Returns (legs, kp): legs[g] is "overfetch" (the ONE ordinary search of the call, then the strike) or "subset"
+    (the row lists); kp = the largest k' among the over-fetch groups and the unfiltered queries (k' = k), 0 if there are none.
+    A forced strategy applies to every filtered group; unfiltered queries always ride in the ordinary search."""
+    legs, kp = [], 0
+    for n_g, m_g in sizes:
+        if m_g is None:
+            leg, want = "overfetch", int(k)
+        else:
+            leg = choose(n_g, k, m_g) if strategy == "auto" else strategy
+            want = kprime(k, m_g) if leg == "overfetch" else 0
+        legs.append(leg)
+        kp = max(kp, want)
+    return legs, kp
+
+
 class FlatIndexF16:
     """Exact top-k inner-product search over fp16 (or, with storage="f8", fp8 e4m3fn + per-row scale)
     rows resident in HBM.
@@ -1443,9 +1493,11 @@ class FlatIndexF16:
 
     @property
     def filtered_stats(self) -> dict:
-        """Counters of search_filtered: 256-query batches answered by each strategy, and queries that over-fetch could not
-        answer and the row-list search answered instead."""
-        return self.__dict__.setdefault("_filtered_stats", {"subset_batches": 0, "overfetch_batches": 0, "fallback_queries": 0})
+        """Counters of search_filtered / search_filtered_many: 256-query batches answered by each strategy (a batch of mixed
+        filters counts once per leg it took), queries that over-fetch could not answer and the row-list search answered
+        instead, search_filtered_many calls and the distinct RowSets their 256-query batches held."""
+        return self.__dict__.setdefault("_filtered_stats", {"subset_batches": 0, "overfetch_batches": 0, "fallback_queries": 0,
+                                                            "grouped_calls": 0, "groups": 0})
 
     def _overfetch_k(self, k: int, m: int) -> int:
         return -(-3 * int(k) * int(self.ntotal) // (2 * max(int(m), 1))) + 32
@@ -1549,6 +1601,165 @@ class FlatIndexF16:
                                               self._xn.data_ptr() if l2 else 0, 1 if l2 else 0, oi.data_ptr(), osc.data_ptr(),
                                               status.data_ptr(), self._rows_ws.data_ptr(), self._rows_ws.numel(), stream),
                     "rarc_search_rows")
+
+    # -- one filter per query: the queries of a mixed batch share ONE over-fetched search + ONE grouped strike
+    # and ONE grouped row-list search, whatever the number of distinct filters
+    def _filter_kprime(self, k: int, m: int) -> int:
+        return max(int(k), min(self._overfetch_k(k, m), self.FILTER_OVERFETCH_MAX_K, int(self.ntotal)))
+
+    def search_filtered_many(self, queries, k: int, rowsets, strategy: str = "auto") -> Tuple[np.ndarray, np.ndarray]:
+        """search_filtered with one filter PER QUERY: rowsets[i] is a RowSet of this index or None (unfiltered), the same
+        object any number of times.  Row i of the answer is search_filtered(queries[i:i+1], k, rowsets[i]) — search(queries[i:i+1],
+        k) for None — ids and score bits, padding beyond min(k, m_i).  Queries are grouped by RowSet identity; per group "auto"
+        takes filter_strategy(queries of the group, k, m); a forced strategy applies to every filtered group."""
+        ids, scores = self.search_filtered_many_device(queries, k, rowsets, strategy)
+        return self.to_host(ids, scores)
+
+    def search_filtered_many_device(self, queries, k: int, rowsets, strategy: str = "auto"):
+        """search_filtered_many with the answer left on the device: (ids int64, scores fp32)."""
+        t = self.torch
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        if strategy not in ("auto", "subset", "overfetch"):
+            raise ValueError(f"unknown strategy: {strategy} ('auto', 'subset' or 'overfetch')")
+        self._refuse_filtered()
+        if k > B.WIDE_MAX_K:
+            raise B.RarcUnsupported(f"k={k} exceeds the limit of {B.WIDE_MAX_K} results per query")
+        q = t.as_tensor(queries, dtype=t.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq][{self.dim}] queries, got {tuple(q.shape)}")
+        rowsets = list(rowsets)
+        nq = int(q.shape[0])
+        if len(rowsets) != nq:
+            raise ValueError(f"search_filtered_many takes one RowSet (or None) per query: {nq} queries, {len(rowsets)} rowsets")
+        version = self._rows_version()
+        for i, rs in enumerate(rowsets):
+            if rs is None:
+                continue
+            if not isinstance(rs, RowSet) or rs._owner() is not self:
+                raise ValueError(f"rowsets[{i}]: search_filtered_many takes RowSets made by this index's rowset() (or None)")
+            if rs.version != version:
+                raise B.RarcError(f"rowsets[{i}]: the index has changed since this RowSet was made (an add extends no filter, a "
+                                  "delete renumbers rows): make a new one with rowset()")
+        with t.cuda.device(self.device):
+            q = q.to(self.device).contiguous()
+            pad = float("inf" if self.metric == "l2" else "-inf")
+            out_ids = t.full((nq, k), -1, dtype=t.int64, device=self.device)
+            out_sc = t.full((nq, k), pad, dtype=t.float32, device=self.device)
+            if self.ntotal == 0 or nq == 0:
+                return out_ids, out_sc
+            self.filtered_stats["grouped_calls"] += 1
+            lists: dict = {}            # the concatenated row lists of this call, by the RowSets they hold
+            for s0 in range(0, nq, B.MAX_QUERIES):
+                s1 = min(nq, s0 + B.MAX_QUERIES)
+                self._filtered_many_batch(q[s0:s1], k, rowsets[s0:s1], strategy, out_ids[s0:s1], out_sc[s0:s1], lists)
+            return out_ids, out_sc
+
+    def _upload_i64(self, arr: np.ndarray):
+        """A small int64 host array as a device tensor, through the pinned pool (no pageable staging copy)."""
+        t = self.torch
+        arr = np.ascontiguousarray(arr, dtype=np.int64).reshape(-1)
+        slot = self._pins.acquire(t, arr.size, 1)
+        try:
+            h = slot.ids[: arr.size]
+            h.numpy()[:] = arr
+            d = t.empty(arr.size, dtype=t.int64, device=self.device)
+            d.copy_(h, non_blocking=True)
+            done = t.cuda.Event()
+            done.record()
+            done.synchronize()          # (the slot may be handed out again once it is released)
+            return d
+        finally:
+            slot.release()
+
+    def _filtered_many_batch(self, q, k: int, rowsets, strategy: str, out_ids, out_sc, lists: dict) -> None:
+        """At most 256 queries, one filter each (validated by the caller): the answer into out_ids / out_sc."""
+        t = self.torch
+        stats = self.filtered_stats
+        groups = group_rowsets(rowsets)
+        stats["groups"] += sum(1 for rs, _ in groups if rs is not None)
+        legs, kp = filtered_many_plan([(len(pos), None if rs is None else rs.m) for rs, pos in groups], k, strategy,
+                                      self.filter_strategy, self._filter_kprime)
+        row_leg: dict = {}              # id(RowSet) -> (RowSet, positions) of the queries the row lists answer
+        for (rs, pos), leg in zip(groups, legs):
+            if leg == "subset":
+                row_leg[id(rs)] = (rs, list(pos))
+        over = [(rs, pos) for (rs, pos), leg in zip(groups, legs) if leg == "overfetch"]
+        if over:
+            # ONE ordinary search at the largest k' (a top-k' answer begins with the top-k'' answer for every k'' < k'), ONE
+            # strike with each query's own mask; the queries that kept too few join the row lists
+            pos = np.concatenate([np.asarray(p, np.int64) for _, p in over])
+            words = (int(self.ntotal) + 31) // 32
+            masks = [rs.bits for rs, _ in over if rs is not None]
+            off, lim, owner, at = [], [], [], 0
+            for rs, p in over:
+                off += [-1 if rs is None else at] * len(p)
+                lim += [0 if rs is None else min(int(k), rs.m)] * len(p)
+                owner += [rs] * len(p)
+                at += 0 if rs is None else words
+            n = pos.size
+            up = self._upload_i64(np.concatenate([pos, np.asarray(off, np.int64), np.asarray(lim, np.int64)]))
+            d_pos, d_off, d_lim = up[:n], up[n: 2 * n], up[2 * n:]
+            ids, sc = self.search_device(q.index_select(0, d_pos), kp)
+            with self._lock:
+                bits = masks[0] if len(masks) == 1 else (t.cat(masks) if masks else t.zeros(1, dtype=t.int32, device=self.device))
+                o_ids = t.empty((n, k), dtype=t.int64, device=self.device)
+                o_sc = t.empty((n, k), dtype=t.float32, device=self.device)
+                count = t.empty(n, dtype=t.int32, device=self.device)
+                B.check(self.lib.rarc_strike_rows_grouped(ids.data_ptr(), sc.data_ptr(), n, kp, bits.data_ptr(), d_off.data_ptr(),
+                                                          self.ntotal, self.id_base, k, 1 if self.metric == "l2" else 0,
+                                                          o_ids.data_ptr(), o_sc.data_ptr(), count.data_ptr(), self._stream()),
+                        "rarc_strike_rows_grouped")
+                out_ids[d_pos], out_sc[d_pos] = o_ids, o_sc
+                stats["overfetch_batches"] += 1
+                short = t.nonzero(count.to(t.int64) < d_lim).reshape(-1).cpu().tolist()      # (one read-back per batch)
+            for j in short:
+                row_leg.setdefault(id(owner[j]), (owner[j], []))[1].append(int(pos[j]))
+            stats["fallback_queries"] += len(short)
+        if row_leg:
+            with self._lock:
+                self._search_rows_grouped(q, k, list(row_leg.values()), out_ids, out_sc, lists)
+            stats["subset_batches"] += 1
+
+    def _search_rows_grouped(self, q, k: int, groups, out_ids, out_sc, lists: dict) -> None:
+        """rarc_search_rows_grouped for groups = [(RowSet, positions in q)], at most 256 queries in all (caller holds the lock):
+        the queries sorted by group, the lists one behind the other, the answers scattered back to their positions."""
+        t = self.torch
+        self._ensure_qbuf()
+        perm = np.concatenate([np.asarray(p, np.int64) for _, p in groups])
+        n = int(perm.size)
+        tiles, _ = build_tile_table([len(p) for _, p in groups], [rs.m for rs, _ in groups], grouped_tile_queries(n, self.d_pad))
+        m_max = max(rs.m for rs, _ in groups)
+        key = tuple(id(rs) for rs, _ in groups)
+        if key not in lists:
+            parts = [rs.rows for rs, _ in groups if rs.m]
+            lists[key] = None if not parts else (parts[0] if len(parts) == 1 else t.cat(parts))
+        d_lists = lists[key]
+        up = self._upload_i64(np.concatenate([perm, tiles.reshape(-1)]))
+        d_perm, d_tiles = up[:n], up[n:]
+        qs = q.index_select(0, d_perm)
+        norm = 1 if self.normalize else 0
+        mn = max(self.max_norm, 1.0) if norm else self.max_norm
+        stream = self._stream()
+        l2 = self.metric == "l2"
+        nbytes = int(self.lib.rarc_search_rows_grouped_workspace_bytes(n, k))
+        if getattr(self, "_rows_ws", None) is None or self._rows_ws.numel() < nbytes:
+            self._rows_ws = None
+            self._rows_ws = t.empty(nbytes, dtype=t.uint8, device=self.device)
+        status = t.empty(B.MAX_QUERIES, dtype=t.int32, device=self.device)
+        sub_ids = t.empty((n, k), dtype=t.int64, device=self.device)
+        sub_sc = t.empty((n, k), dtype=t.float32, device=self.device)
+        B.check(self.lib.rarc_prep_queries(qs.data_ptr(), qs.shape[1], n, self.dim, self.d_pad, norm, mn, 0,
+                                           self._qbuf["qblock"].data_ptr(), stream), "rarc_prep_queries")
+        B.check(self.lib.rarc_search_rows_grouped(self._rows.data_ptr(), 2 if self.storage == "f32" else 0, self.ntotal, self.d_pad,
+                                                  self._qbuf["qblock"].data_ptr(), n, d_lists.data_ptr() if d_lists is not None else 0,
+                                                  d_tiles.data_ptr(), int(tiles.shape[0]), m_max, k, self.id_base,
+                                                  self._xn.data_ptr() if l2 else 0, 1 if l2 else 0, sub_ids.data_ptr(),
+                                                  sub_sc.data_ptr(), status.data_ptr(), self._rows_ws.data_ptr(),
+                                                  self._rows_ws.numel(), stream), "rarc_search_rows_grouped")
+        out_ids[d_perm], out_sc[d_perm] = sub_ids, sub_sc
 
     def neighbors_above(self, queries, threshold: float, k_cap: int = 64):
         """Range query by score: for every query, the stored rows whose canonical score is >= threshold
