@@ -389,6 +389,26 @@ size_t rarc_mmr_workspace_doubles(int n, int d);
 int rarc_mmr_select(const float* d_cand, int64_t ld, const double* d_query, int n, int d, int normalize, int k,
                     double lambda, double* d_work, int32_t* d_out, void* stream);
 
+/* rarc_mmr_select for a BATCH of queries, the candidates read straight from resident rows: one workgroup per query, no gather,
+ * no widened copy.  For every query the picks are, index for index, what rarc_mmr_select returns for the same candidates
+ * gathered to fp32 (fp16 widened exactly; fp8 decoded to fp32 and multiplied by the row scale in fp32; fp32 as is; elements
+ * 0 .. d-1 of each row) and the same float64 query: every sum is the same sequential float64 sum over m = 0 .. d-1.
+ *   d_rows      fmt 0: fp16 rows [n_rows][d_pad] · 1: fp8 e4m3fn rows, d_rowscale = float [n_rows] · 2: fp32 rows.
+ *               16-byte aligned, d <= d_pad, d_pad a multiple of 16
+ *   d_queries   float64, query q at d_queries + q * ldq (ldq >= d)
+ *   d_cand_ids  int64 [nq][n], n <= 1024: what a search for n results returns — ids INCLUDING id_base.  A query's candidates
+ *               are its entries that name a row (id - id_base in [0, n_rows)), in order; -1 padding is skipped
+ *   d_out_ids   int64 [nq][k]: the selected candidates' ids in selection order, -1 beyond min(k, candidates of the query);
+ *               k >= the number of candidates: the candidates in their given order
+ *   d_ws        rarc_mmr_rows_workspace_bytes(nq, n, d) bytes (0 for sizes the call refuses), 8-byte aligned
+ * RARC_E_UNSUPPORTED: n > 1024 · RARC_E_WORKSPACE: workspace too small / misaligned · RARC_E_INVALID: null pointer, bad
+ * sizes, unknown fmt, fp8 rows without scales.  Nothing is launched on a refused call.
+ */
+size_t rarc_mmr_rows_workspace_bytes(int nq, int n, int d);
+int rarc_mmr_select_rows(const void* d_rows, int fmt, const float* d_rowscale, int64_t n_rows, int d_pad, int d,
+                         const double* d_queries, int64_t ldq, int nq, const int64_t* d_cand_ids, int n, int64_t id_base,
+                         int normalize, int k, double lambda, int64_t* d_out_ids, void* d_ws, size_t ws_bytes, void* stream);
+
 /*
  * Deterministic synthetic corpus / query generator (bench + full-size property
  * tests): counter-based integer hash -> 52-bit uniform -> N(0,1) by the inverse normal CDF (Wichura AS 241,

@@ -55,8 +55,9 @@ class VectorStoreRetriever(BaseRetriever):
 
     def batch_invoke(self, inputs: List[str], **kwargs: Any) -> List[List[Document]]:
         """invoke() for a list of queries in ONE pass of the store (one encoder call, one scan per 256 queries) when the
-        store can batch (`batch_similarity_search`: HipFlatVectorStore and its sharded form) and the search type is
-        "similarity"; otherwise query by query.  Element i equals invoke(inputs[i], **kwargs).
+        store can batch the search type (`batch_similarity_search`: HipFlatVectorStore and its sharded form;
+        `batch_max_marginal_relevance_search`, `batch_similarity_search_with_relevance_scores`: HipFlatVectorStore); otherwise
+        query by query.  Element i equals invoke(inputs[i], **kwargs).
         `filters=` (a sequence, one entry per query: dict / callable / prepared handle / None) gives every query a filter of its
         own — the tenants of a mixed batch share the store's pass; element i then equals invoke(inputs[i], filter=filters[i])."""
         inputs = list(inputs)
@@ -76,12 +77,17 @@ class VectorStoreRetriever(BaseRetriever):
                 return [self.invoke(q, **kwargs) for q in inputs]
             return [self.invoke(q, **{**kwargs, "filter": f}) for q, f in zip(inputs, filters)]
 
-        batched = getattr(self.vectorstore, "batch_similarity_search", None)
-        if self.search_type != "similarity" or batched is None:
+        name = {"similarity": "batch_similarity_search", "mmr": "batch_max_marginal_relevance_search",
+                "similarity_score_threshold": "batch_similarity_search_with_relevance_scores"}[self.search_type]
+        batched = getattr(self.vectorstore, name, None)
+        if batched is None:
             return one_by_one()
         try:
             more = {} if filters is None else {"filters": filters}
-            return [docs[:k] for docs in batched(inputs, **params, **more)]
+            answers = batched(inputs, **params, **more)
+            if self.search_type == "similarity_score_threshold":
+                answers = [[d for d, _ in pairs] for pairs in answers]
+            return [docs[:k] for docs in answers]
         except Exception as exc:
             # element i must equal invoke(inputs[i]): a query that cannot be answered raises from ITS invoke, the ones
             # before it are not lost to a caller that catches per query (MultiPathRetriever.batch_invoke does)

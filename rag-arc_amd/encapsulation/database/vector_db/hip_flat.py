@@ -926,6 +926,112 @@ class HipFlatVectorStore(VectorStore):
                                   "the retriever's 'similarity' modes), not by max_marginal_relevance_search: its fetch_k "
                                   "candidates are taken from the whole index")
 
+    # -- MMR for a batch of queries (extension; the reference has one query per call) ---------------------------------------
+    MMR_BATCH = 256               # queries per pass: one embed_queries, one search, one selection, one host mapping
+
+    @property
+    def mmr_stats(self) -> dict:
+        """Counters of the batch MMR entry points: calls that took the batched device path, the queries those answered, and
+        the queries answered one by one through the single call instead (reembed=True, an engine without the native library,
+        fetch_k beyond the selection kernel's 1024 candidates)."""
+        return self.__dict__.setdefault("_mmr_stats", {"batched_calls": 0, "batched_queries": 0, "fallback_queries": 0})
+
+    def _refuse_mmr_filters(self, kwargs) -> None:
+        """`filter=` / `filters=` on a batch MMR call: refused as the single call refuses `filter=`, before any launch.  A
+        `filters=` that holds only None is the unfiltered batch."""
+        self._refuse_mmr_filter(kwargs)
+        filters = kwargs.pop("filters", None)
+        if filters is not None:
+            for f in filters:
+                self._refuse_mmr_filter({"filter": f})
+
+    def _mmr_batched_path(self, k: int, fetch_k: int, kwargs) -> bool:
+        idx = self.index
+        return (not kwargs.get("reembed", True) and int(k) >= 1 and 1 <= int(fetch_k) <= 1024
+                and getattr(idx, "lib", None) is not None and hasattr(idx, "mmr_select_device") and hasattr(idx, "search_device"))
+
+    def _mmr_batch_pass(self, q64, k: int, fetch_k: int, lambda_mult: float) -> List[List[Document]]:
+        """One pass of at most MMR_BATCH queries (float64 [nq][dim], numpy or device tensor): the search for the candidates
+        takes the queries' float32 rounding, the selection the float64 values, as the single call; ids stay on the device
+        from the search to the selection, the selected rows come to the host once."""
+        import torch
+
+        q32 = q64.to(torch.float32) if hasattr(q64, "is_cuda") else q64.astype(np.float32)
+        norm = bool(self.normalize_L2 or self.metric == "cosine")
+        with self._guard.shared():
+            n = min(int(fetch_k), self.ntotal)
+            ids, _ = self.index.search_device(q32, n)
+            picked = self.index.mmr_select_device(q64, ids, min(int(k), n), lambda_mult, normalize=norm)
+            return self._map_batch(None, picked.cpu().numpy(), False)
+
+    def _mmr_batch(self, q64, nq: int, one, k: int, fetch_k: int, lambda_mult: float, kwargs) -> List[List[Document]]:
+        """Shared body of the two batch entry points.  q64(s0, s1): the float64 queries of a pass; one(i): the single call."""
+        self._refuse_mmr_filters(kwargs)
+        if self.ntotal == 0:
+            return [[] for _ in range(nq)]
+        stats = self.mmr_stats
+        if not self._mmr_batched_path(k, fetch_k, kwargs):
+            stats["fallback_queries"] += nq
+            return [one(i) for i in range(nq)]
+        out: list = []
+        for s0 in range(0, nq, self.MMR_BATCH):
+            out.extend(self._mmr_batch_pass(q64(s0, min(nq, s0 + self.MMR_BATCH)), k, fetch_k, lambda_mult))
+        stats["batched_calls"] += 1
+        stats["batched_queries"] += nq
+        return out
+
+    def _embed_batch_f64(self, queries: List[str]):
+        """Query texts -> float64 vectors holding exactly what embed_query gives for each text (a float32 device tensor when
+        the provider keeps them in HBM: widened on the device)."""
+        import torch
+
+        if hasattr(self.embedding, "embed_queries_device"):
+            return self.embedding.embed_queries_device(queries).to(torch.float64)
+        if hasattr(self.embedding, "embed_queries"):
+            emb = self.embedding.embed_queries(queries)
+            return emb.to(torch.float64) if hasattr(emb, "is_cuda") else np.asarray(emb, dtype=np.float64)
+        return np.asarray([self.embedding.embed_query(t) for t in queries], dtype=np.float64)
+
+    def batch_max_marginal_relevance_search(self, queries: Sequence[str], k: int = 4, fetch_k: int = 20, lambda_mult: float = 0.5,
+                                            **kwargs: Any) -> List[List[Document]]:
+        """max_marginal_relevance_search for a list of queries; element i equals the single call with the same arguments.
+        With `reembed=False`, the default engine and fetch_k <= 1024 every 256 queries take one encoder call, one search
+        for the candidates, one selection (rarc_mmr_select_rows: candidates read from the resident rows) and one host
+        mapping; otherwise the queries are answered one by one.  `filter=` / `filters=` are refused (mmr_stats counts)."""
+        queries = list(queries)
+        return self._mmr_batch(lambda s0, s1: self._embed_batch_f64(queries[s0:s1]), len(queries),
+                               lambda i: self.max_marginal_relevance_search(queries[i], k, fetch_k, lambda_mult, **kwargs),
+                               k, fetch_k, lambda_mult, kwargs)
+
+    def batch_max_marginal_relevance_search_by_vector(self, embeddings, k: int = 4, fetch_k: int = 20, lambda_mult: float = 0.5,
+                                                      **kwargs: Any) -> List[List[Document]]:
+        """max_marginal_relevance_search_by_vector for a batch of query vectors (a sequence, an array or a device tensor)."""
+        import torch
+
+        if hasattr(embeddings, "is_cuda"):
+            vecs = embeddings.to(torch.float64)
+            single = lambda i: embeddings[i].tolist()
+        else:
+            embeddings = list(embeddings)
+            vecs = None
+            single = lambda i: embeddings[i]
+
+        def q64(s0, s1):
+            return vecs[s0:s1] if vecs is not None else np.asarray(embeddings[s0:s1], dtype=np.float64)
+
+        return self._mmr_batch(q64, len(embeddings),
+                               lambda i: self.max_marginal_relevance_search_by_vector(single(i), k, fetch_k, lambda_mult, **kwargs),
+                               k, fetch_k, lambda_mult, kwargs)
+
+    def batch_similarity_search_with_relevance_scores(self, queries: Sequence[str], k: int = 4, **kwargs: Any):
+        """similarity_search_with_relevance_scores for a list of queries: batch_similarity_search_with_score (one encoder call,
+        one scan per 256 queries; `filter=` / `filters=` pass through), then per query the store's relevance function and the
+        `score_threshold` cut.  Element i equals the single call, its warnings included."""
+        thr = kwargs.pop("score_threshold", None)
+        fn = self._select_relevance_score_fn()
+        answers = self.batch_similarity_search_with_score(queries, k, **kwargs)
+        return [self._filter_relevance([(doc, fn(score)) for doc, score in pairs], thr) for pairs in answers]
+
     def _mmr_on_device(self, rows: List[int], embedding, k: int, lambda_mult: float) -> List[int]:
         """Selection order (indices into `rows`) of the MMR loop, computed on the device from the resident rows."""
         import torch

@@ -248,6 +248,13 @@ class HipShardedFlatVectorStore(HipFlatVectorStore):
                                       "the candidates' texts, as the reference does")
         return super().max_marginal_relevance_search_by_vector(embedding, k, fetch_k, lambda_mult, **kwargs)
 
+    # the batched MMR / relevance-score entry points belong to the one-GPU store (the selection reads ONE GPU's rows; the
+    # relevance batch rides on the coalescing-free SPMD search as the single calls do): a retriever's batch_invoke finds
+    # nothing here and answers those search types query by query
+    batch_max_marginal_relevance_search = None
+    batch_max_marginal_relevance_search_by_vector = None
+    batch_similarity_search_with_relevance_scores = None
+
     # -- persistence: one shard file per rank (hip_flat.save_local / load_local do the work) ----------------------------
     def _shard_layout(self):
         import torch.distributed as dist

@@ -1602,6 +1602,58 @@ class FlatIndexF16:
                                               status.data_ptr(), self._rows_ws.data_ptr(), self._rows_ws.numel(), stream),
                     "rarc_search_rows")
 
+    # -- batched MMR over the resident rows -------------------------------------------------------------
+    MMR_MAX_FETCH = 1024          # rarc_mmr_select_rows' candidates per query (MMR_MAX_N, csrc/fuse.hip)
+    # most bytes the selection's float64 workspace may take: the batch goes through in runs of queries that fit.  One query
+    # needs (n + 1) d doubles: 0.13 MB at n = 20, d = 768 (a batch of 256: 33 MB, one launch), 33.6 MB at the limits n = 1024,
+    # d = 4096 (seven queries per launch).  256 MiB holds a whole batch at fetch_k <= 170 for 768-d rows and is 0.1 % of the
+    # device's memory; beyond it the launches are long enough (hundreds of microseconds each) that splitting costs nothing.
+    MMR_WS_CAP_BYTES = 256 << 20
+
+    def mmr_select_device(self, queries_f64, cand_ids, k: int, lambda_mult: float = 0.5, normalize: Optional[bool] = None):
+        """Greedy MMR selection for a batch, candidates read from the resident rows (rarc_mmr_select_rows): queries_f64
+        float64 [nq][dim] (numpy or tensor), cand_ids int64 device tensor [nq][n] as search_device(q, n) returns it (ids
+        including id_base, -1 padding at the tail), n <= 1024.  Returns int64 [nq][k] on the device: the selected candidates' ids
+        in selection order, -1 beyond min(k, candidates of the query).  normalize: divide query and candidates by their
+        float64 norms first (default: what the index does to its rows)."""
+        t = self.torch
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        self._check_twin()
+        norm = self.normalize if normalize is None else bool(normalize)
+        with self._lock, t.cuda.device(self.device):
+            q = t.as_tensor(queries_f64, dtype=t.float64).to(self.device).contiguous()
+            if q.ndim == 1:
+                q = q[None, :]
+            ids = t.as_tensor(cand_ids, dtype=t.int64).to(self.device).contiguous()
+            if q.ndim != 2 or q.shape[1] != self.dim:
+                raise ValueError(f"expected [nq][{self.dim}] queries, got {tuple(q.shape)}")
+            if ids.ndim != 2 or ids.shape[0] != q.shape[0] or ids.shape[1] < 1:
+                raise ValueError(f"expected [{q.shape[0]}][n >= 1] candidate ids, got {tuple(ids.shape)}")
+            nq, n = int(ids.shape[0]), int(ids.shape[1])
+            if n > self.MMR_MAX_FETCH:
+                raise B.RarcUnsupported(f"{n} candidates per query exceed the limit of {self.MMR_MAX_FETCH}")
+            out = t.full((nq, int(k)), -1, dtype=t.int64, device=self.device)
+            if nq == 0 or self.ntotal == 0:
+                return out
+            per = int(self.lib.rarc_mmr_rows_workspace_bytes(1, n, self.dim))
+            run = max(1, min(nq, self.MMR_WS_CAP_BYTES // per))
+            need = run * per
+            if getattr(self, "_mmr_ws", None) is None or self._mmr_ws.numel() < need:
+                self._mmr_ws = None
+                self._mmr_ws = t.empty(need, dtype=t.uint8, device=self.device)
+            fmt = {"f16": 0, "f8": 1, "f32": 2}[self.storage]
+            scales = self._rowscale.data_ptr() if fmt == 1 else 0
+            stream = self._stream()
+            for s0 in range(0, nq, run):
+                s1 = min(nq, s0 + run)
+                B.check(self.lib.rarc_mmr_select_rows(self._rows.data_ptr(), fmt, scales, self.ntotal, self.d_pad, self.dim,
+                                                      q[s0:s1].data_ptr(), self.dim, s1 - s0, ids[s0:s1].data_ptr(), n,
+                                                      self.id_base, 1 if norm else 0, int(k), float(lambda_mult),
+                                                      out[s0:s1].data_ptr(), self._mmr_ws.data_ptr(), self._mmr_ws.numel(), stream),
+                        "rarc_mmr_select_rows")
+            return out
+
     # -- one filter per query (DESIGN 4.10e): the queries of a mixed batch share ONE over-fetched search + ONE grouped strike
     # and ONE grouped row-list search, whatever the number of distinct filters
     def _filter_kprime(self, k: int, m: int) -> int:
