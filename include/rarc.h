@@ -784,6 +784,27 @@ int rarc_similar_pairs(const float* d_rows, int64_t ld, int64_t n_rows, int d, d
                        unsigned long long* d_out_count, uint32_t* d_flags, void* stream);
 
 /*
+ * The exact k-nearest-neighbour graph of n embeddings: every row's top_k other rows by cosine — the event disambiguation of
+ * the reference's graph store (encapsulation/database/graph_db/event_graphrag_neo4j.py:600-672, _disambiguate_events_with_gds:
+ * gds.knn.write over every Event embedding with topK: 10, similarityCutoff: 0.85, one SIMILAR_TO edge per neighbour; it needs
+ * a Neo4j server with the GDS plugin — the failure is swallowed when it is absent, :671-672 — and GDS's kNN is NN-descent:
+ * approximate).  Here the answer is exact: the fp16 image and the score GEMM of rarc_similar_pairs nominate, per column (the
+ * row whose neighbours are sought), what reaches a threshold that rises to (top_k-th best approximate score so far) - 2 eps
+ * as chunks of rows go by; every nominee is then scored exactly and the top_k best kept (csrc/knn.hip).
+ * d_rows: fp32 [n_rows][ld], device, any scale; 1 <= d <= 4096; 1 <= top_k <= 256; -1 <= cutoff <= 1.
+ * Row i of the answer is the rows j != i (by index: an identical copy of row i is a neighbour) with cos(i, j) >= cutoff,
+ * ordered by (cosine descending, j ascending), cut at top_k: d_out_ids int64 [n_rows][top_k], d_out_scores double
+ * [n_rows][top_k] — the float64 cosine rarc_similar_pairs returns for the pair, bit for bit; a zero row has cosine 0 with
+ * everything — d_out_count int32 [n_rows]; slots past the count hold (-1, -inf).
+ * *d_flags (uint32): bit 0 = a column's nomination list (cand_cap entries) overflowed: the answer is incomplete — call again
+ * with a larger cand_cap (cand_cap >= n_rows rounded up to 256 cannot overflow).
+ * The workspace is rarc_knn_graph_workspace_bytes(n_rows, d, top_k, cand_cap) bytes (0 for arguments rarc_knn_graph refuses).
+ */
+size_t rarc_knn_graph_workspace_bytes(int64_t n_rows, int d, int top_k, int cand_cap);
+int rarc_knn_graph(const float* d_rows, int64_t ld, int64_t n_rows, int d, int top_k, double cutoff, void* d_ws, size_t ws_bytes,
+                   int cand_cap, int64_t* d_out_ids, double* d_out_scores, int32_t* d_out_count, uint32_t* d_flags, void* stream);
+
+/*
  * Deleting rows of a resident index: stable in-place compaction.  The reference deletes by clearing the index and
  * embedding every surviving text again (encapsulation/database/vector_db/VectorStore_Faiss.py:374-415); the surviving
  * rows are in HBM already, so here they move down over the holes: row i of the result is the i-th surviving row.

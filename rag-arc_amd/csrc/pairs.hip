@@ -14,55 +14,10 @@
 // rows, times the two inverse norms, fixed summation order — and kept if that reaches the threshold.  So the pairs returned
 // are exactly those whose float64 cosine is >= threshold (up to the last bits of a float64 dot product: sklearn's BLAS sums in
 // another order), at the cost of n^2 d / 2 MFMA flops: 100,000 entities x 1024 dimensions are 10 TFLOP — tens of milliseconds.
-#include "rarc_common.h"
+#include "pairs_common.h"   // the workspace, pairs_eps, the fixed-order wave sum and the exact cosine: shared with knn.hip
 
 int rarc_gemm_f16_select_n(const uint16_t* a, const uint16_t* w, int m, int n, int k, const float* thr, unsigned long long* cand,
                            uint32_t* count, uint32_t* status, uint32_t cap, uint32_t row0, uint32_t n_valid, hipStream_t s);
-
-namespace {
-constexpr int PAIRS_COLS = 4096;     // columns per GEMM launch (16 tiles wide: with >= 16 row tiles the chip is full)
-
-struct PairsWs {
-  uint16_t* image;       // [n_pad][d_pad] fp16, rows normalised, zero padded
-  double* inv_norm;      // [n_pad]
-  float* thr;            // [PAIRS_COLS]
-  uint32_t* count;       // [PAIRS_COLS]
-  uint32_t* status;      // [PAIRS_COLS]
-  unsigned long long* cand;   // [PAIRS_COLS][cap]
-};
-inline size_t a256(size_t v) { return (v + 255) & ~(size_t)255; }
-inline int64_t pad256(int64_t n) { return (n + 255) / 256 * 256; }
-size_t pairs_ws_bytes(int64_t n, int d_pad, int cap) {
-  const int64_t n_pad = pad256(n);
-  return a256((size_t)n_pad * d_pad * 2) + a256((size_t)n_pad * 8) + 3 * a256((size_t)PAIRS_COLS * 4) +
-         a256((size_t)PAIRS_COLS * cap * 8) + 256;
-}
-PairsWs pairs_carve(void* base, int64_t n, int d_pad, int cap) {
-  const int64_t n_pad = pad256(n);
-  char* b = (char*)(((uintptr_t)base + 255) & ~(uintptr_t)255);
-  PairsWs w;
-  w.image = (uint16_t*)b;    b += a256((size_t)n_pad * d_pad * 2);
-  w.inv_norm = (double*)b;   b += a256((size_t)n_pad * 8);
-  w.thr = (float*)b;         b += a256((size_t)PAIRS_COLS * 4);
-  w.count = (uint32_t*)b;    b += a256((size_t)PAIRS_COLS * 4);
-  w.status = (uint32_t*)b;   b += a256((size_t)PAIRS_COLS * 4);
-  w.cand = (unsigned long long*)b;
-  (void)cap;
-  return w;
-}
-
-// sum over a wave in a FIXED order (lane l holds the partial of elements l, l + 64, ...): a tree over the lane index, so the
-// exact score of a pair does not depend on where it was computed
-__device__ __forceinline__ double pairs_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-}  // namespace
-
-// |fp32-accumulated x16·y16 - x·y| for unit vectors x, y rounded to fp16 elementwise: each factor is off by 2^-11 relative
-// (or 2^-25 absolute under the normal range), the products' sum by d_pad·2^-24 at most (fp32 accumulation, MFMA order unknown).
-static inline float pairs_eps(int d_pad) { return 0.0009765625f + (float)d_pad * 1.1920928955078125e-07f + 1e-6f; }
 
 // one workgroup (4 waves) per row: double-precision norm, inverse norm, the normalised row as fp16 (zero row -> zeros, as
 // sklearn's normalize leaves it); rows [n, n_pad) and columns [d, d_pad) are written as zeros
@@ -128,11 +83,7 @@ __global__ __launch_bounds__(256) void pairs_finalize_kernel(const float* __rest
     for (uint32_t e = e0 + wave; e < e1; e += 4) {
       const int64_t i = (int64_t)rarc_candrow(cand[(size_t)q * cap + e]);
       if (i >= j) continue;                                          // (wave-uniform: the whole wave reads the same entry)
-      const float* x = rows + (size_t)i * ld;
-      double acc = 0.0;
-      for (int m = lane; m < d; m += 64) acc += (double)x[m] * (double)y[m];
-      acc = pairs_wave_sum(acc);
-      const double cosv = acc * inv_norm[i] * inv_j;
+      const double cosv = pairs_exact_cos(rows + (size_t)i * ld, y, d, lane, inv_norm[i], inv_j);
       if (lane == 0 && cosv >= threshold) {
         const uint32_t slot = atomicAdd(&s_keep, 1u);
         s_row[slot] = (uint32_t)i;
@@ -157,10 +108,24 @@ __global__ __launch_bounds__(256) void pairs_finalize_kernel(const float* __rest
   }
 }
 
+// a super-block's columns start with threshold t, empty lists and clear status words (knn.hip as well)
+int rarc_pairs_reset(const PairsWs& w, float t, int64_t col0, int64_t n_rows, hipStream_t s) {
+  hipLaunchKernelGGL(pairs_reset_kernel, dim3(PAIRS_COLS / 256), dim3(256), 0, s, w.thr, w.count, w.status, t, col0, n_rows);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+// the prepare pass for knn.hip as well: one launch, n_pad rows
+int rarc_pairs_prepare(const float* d_rows, int64_t ld, int64_t n_rows, int d, int d_pad, uint16_t* image, double* inv_norm,
+                       hipStream_t s) {
+  hipLaunchKernelGGL(pairs_prepare_kernel, dim3((unsigned)pad256(n_rows)), dim3(256), 0, s, d_rows, ld, n_rows, d, d_pad, image, inv_norm);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
 extern "C" size_t rarc_similar_pairs_workspace_bytes(int64_t n_rows, int d, int cand_cap) {
   if (n_rows <= 0 || d <= 0 || cand_cap <= 0) return 0;
-  const int d_pad = (d + 63) / 64 * 64 < 256 ? 256 : (d + 63) / 64 * 64;
-  return pairs_ws_bytes(n_rows, d_pad, cand_cap);
+  return pairs_ws_bytes(n_rows, pairs_d_pad(d), cand_cap);
 }
 
 // d_rows: fp32 [n_rows][ld] on the device, any scale (they are normalised here).  Pairs come out in no particular order
@@ -180,19 +145,17 @@ extern "C" int rarc_similar_pairs(const float* d_rows, int64_t ld, int64_t n_row
   RARC_HIP_CHECK(hipMemsetAsync(d_out_count, 0, 8, s));
   RARC_HIP_CHECK(hipMemsetAsync(d_flags, 0, 4, s));
   if (n_rows < 2) return RARC_OK;
-  const int d_pad = (d + 63) / 64 * 64 < 256 ? 256 : (d + 63) / 64 * 64;
+  const int d_pad = pairs_d_pad(d);
   RARC_REQUIRE(ws_bytes >= pairs_ws_bytes(n_rows, d_pad, cand_cap), RARC_E_WORKSPACE, "rarc_similar_pairs: workspace of %zu bytes, %zu needed",
                ws_bytes, pairs_ws_bytes(n_rows, d_pad, cand_cap));
-  const PairsWs w = pairs_carve(d_ws, n_rows, d_pad, cand_cap);
+  const PairsWs w = pairs_carve(d_ws, n_rows, d_pad);
   const int64_t n_pad = pad256(n_rows);
-  hipLaunchKernelGGL(pairs_prepare_kernel, dim3((unsigned)n_pad), dim3(256), 0, s, d_rows, ld, n_rows, d, d_pad, w.image, w.inv_norm);
-  RARC_HIP_CHECK(hipGetLastError());
+  if (int rc = rarc_pairs_prepare(d_rows, ld, n_rows, d, d_pad, w.image, w.inv_norm, s)) return rc;
   const float t_approx = (float)threshold - pairs_eps(d_pad);
   for (int64_t col0 = 0; col0 < n_rows; col0 += PAIRS_COLS) {
     const int64_t cols = n_pad - col0 < PAIRS_COLS ? n_pad - col0 : PAIRS_COLS;      // a multiple of 256
     const int64_t m = col0 + cols;                                                    // rows [0, m): every i < j of these columns
-    hipLaunchKernelGGL(pairs_reset_kernel, dim3(PAIRS_COLS / 256), dim3(256), 0, s, w.thr, w.count, w.status, t_approx, col0, n_rows);
-    RARC_HIP_CHECK(hipGetLastError());
+    if (int rc = rarc_pairs_reset(w, t_approx, col0, n_rows, s)) return rc;
     if (int rc = rarc_gemm_f16_select_n(w.image, w.image + (size_t)col0 * d_pad, (int)m, (int)cols, d_pad, w.thr, w.cand, w.count,
                                         w.status, (uint32_t)cand_cap, 0u, (uint32_t)n_rows, s))
       return rc;

@@ -1,5 +1,6 @@
-"""The one arithmetic step of the reference's graph store that sits on the dense hot path's kernels: entity de-duplication by
-all-pairs cosine (encapsulation/database/graph_db/Base_Neo4j.py:538-583).  The graph database itself is out of scope."""
-from .similarity import similar_pairs
+"""The arithmetic steps of the reference's graph store that sit on the dense hot path's kernels: entity de-duplication by
+all-pairs cosine (encapsulation/database/graph_db/Base_Neo4j.py:538-583) and event disambiguation by a k-nearest-neighbour
+graph (event_graphrag_neo4j.py:600-672).  The graph database itself is out of scope."""
+from .similarity import knn_graph, similar_pairs
 
-__all__ = ["similar_pairs"]
+__all__ = ["similar_pairs", "knn_graph"]

@@ -219,6 +219,9 @@ SIGNATURES = {
     "rarc_similar_pairs_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "rarc_similar_pairs": (c_int, [c_void_p, c_int64, c_int64, c_int, ctypes.c_double, c_void_p, c_size_t, c_int, c_void_p, c_void_p,
                                    c_int64, c_void_p, c_void_p, c_void_p]),
+    "rarc_knn_graph_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "rarc_knn_graph": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, ctypes.c_double, c_void_p, c_size_t, c_int, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
     "rarc_compact_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
     "rarc_vmem_create": (c_int, [c_int, c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_void_p)]),
     "rarc_vmem_grow": (c_int, [c_void_p, c_size_t]),
