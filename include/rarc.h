@@ -598,6 +598,27 @@ int rarc_lm_yes_no_logits_prefixed(const RarcLmModel* model, const int32_t* d_id
                                    size_t ws_bytes, uint16_t* d_out_f16, void* stream);
 
 /*
+ * Decoder-LM embeddings — the same forward with the ending of a sentence-transformers decoder embedder (Qwen3-Embedding:
+ * Transformer -> Pooling(lasttoken) -> Normalize; the reference's provider wraps any such model,
+ * core/file_management/embeddings/huggingface.py:12-22,96-98).  For LEFT-padded batches the last position is every
+ * sequence's last real token, so the embedding is the final RMSNorm of the last residual row, with the roundings of the
+ * logits path (the reference's fp16 model): nv[c] = half(final_norm[c] * half(x[c] * inv)), inv in fp32.
+ *   d_out    fp32 [n_seq][ld_out], columns [0, out_dim) written, the rest untouched
+ *   out_dim  1 .. hidden: the first out_dim components (Matryoshka truncation, sentence-transformers' truncate_dim)
+ *   normalize 0: (float)nv[c];  1: nv[c] / max(||nv[0..out_dim)||, 1e-12), the sum of squares in fp32 over the out_dim
+ *            components kept (truncation first, then Normalize); an all-zero row gives zeros
+ * model->lm_head is not read and may be null (Qwen3Model checkpoints have no head).  Shapes, d_ids / d_start, the workspace
+ * (rarc_lm_workspace_bytes) and the prefix arguments are those of the logits calls; additionally 1 <= out_dim <= hidden and
+ * ld_out >= out_dim.  The last layer still runs on the last positions only when its compact buffers fit.
+ */
+int rarc_lm_embed_last(const RarcLmModel* model, const int32_t* d_ids, const int32_t* d_start, int n_seq, int seq_len,
+                       int out_dim, int normalize, void* d_ws, size_t ws_bytes, float* d_out, int64_t ld_out, void* stream);
+int rarc_lm_embed_last_prefixed(const RarcLmModel* model, const int32_t* d_ids, const int32_t* d_start, int n_seq,
+                                int seq_len, const int32_t* d_prefix_of, const void* d_cache, int n_prefix,
+                                int prefix_len, const int32_t* d_prefix_start, int out_dim, int normalize, void* d_ws,
+                                size_t ws_bytes, float* d_out, int64_t ld_out, void* stream);
+
+/*
  * Batch WordPiece tokenisation on the host (no device involved) — what sits between the texts the reference hands to
  * `SentenceTransformer.encode` (core/file_management/embeddings/huggingface.py:116-126) and the encoder forward above: the
  * BERT tokeniser (native and multi-threaded in the reference's dependency too).  Same algorithm as the python restatement

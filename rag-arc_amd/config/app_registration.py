@@ -1,8 +1,8 @@
 """Counterpart of the reference's config/app_registration.py:1-5: the registry singleton plus a
 helper that registers this backend's retriever stacks under the framework's own mechanism."""
 from ..framework.register import Register
-from .modules import (HipLogitRerankerConfig, HipQwen3RerankerConfig, HipShardedFlatVectorStoreConfig,
-                      MultiPathRetrieverConfig, VectorStoreRetrieverConfig)
+from .modules import (HipLogitRerankerConfig, HipQwen3EmbeddingsConfig, HipQwen3RerankerConfig,
+                      HipShardedFlatVectorStoreConfig, MultiPathRetrieverConfig, VectorStoreRetrieverConfig)
 
 registrator = Register()
 
@@ -26,3 +26,7 @@ def register_reranker(config_path: str, app_name: str = "hip_reranker") -> None:
 
 def register_qwen3_reranker(config_path: str, app_name: str = "hip_qwen3_reranker") -> None:
     registrator.register(config_path, app_name, HipQwen3RerankerConfig)
+
+
+def register_qwen3_embeddings(config_path: str, app_name: str = "hip_qwen3_embeddings") -> None:
+    registrator.register(config_path, app_name, HipQwen3EmbeddingsConfig)

@@ -101,7 +101,55 @@ class HipBertEmbeddingsConfig(AbstractConfig):
                                                                prompt_name=self.prompt_name, prompt=self.prompt))
 
 
-EmbeddingsConfig = Annotated[Union[TableEmbeddingsConfig, HipBertEmbeddingsConfig], Field(discriminator="type")]
+class HipQwen3EmbeddingsConfig(AbstractConfig):
+    """A decoder-LM embedder (Qwen3-Embedding-0.6B / 4B / 8B: the reranker's decoder, last-token pooling, Normalize) as a
+    registered embedding provider.  `weights_path`: the checkpoint's state dict (.safetensors / .npz; Qwen3Model or
+    Qwen3ForCausalLM names — a head is not needed); `tokenizer_path`: its tokenizer.json, or `vocab_path` + `merges_path`;
+    the head geometry comes from its config.json (Qwen3-Embedding-0.6B: 16 / 8 heads of 128).  fp16 weights and activations,
+    fp32 accumulation and output: the class of a `torch_dtype=float16` sentence-transformers model."""
+    type: Literal["hip_qwen3_embeddings"] = "hip_qwen3_embeddings"
+    weights_path: str
+    tokenizer_path: Optional[str] = None
+    vocab_path: Optional[str] = None
+    merges_path: Optional[str] = None
+    num_attention_heads: int
+    num_key_value_heads: int
+    head_dim: int = 128
+    rms_norm_eps: float = 1e-6
+    rope_theta: float = 1e6
+    tie_word_embeddings: bool = True      # only decides whether a checkpoint without lm_head.weight could also give logits
+    prompt: str = ""                      # in front of every text (sentence-transformers' `prompt`)
+    query_prompt: Optional[str] = None    # the query methods' own prompt, e.g. "Instruct: ...\nQuery:"
+    dim: Optional[int] = None             # Matryoshka truncation (truncate_dim)
+    normalize: bool = True
+    max_length: int = 4096
+    batch_tokens: int = 32768
+    append_eos: bool = True
+    eos_token: str = "<|endoftext|>"      # looked up in the tokenizer; eos_token_id wins when given
+    eos_token_id: Optional[int] = None
+    prefix_cache: Optional[bool] = None   # None = the provider's default
+    device: int = 0
+
+    def build(self) -> AbstractModule:
+        from ..core.rerank.hip_qwen3 import HipCausalLM
+        from ..encapsulation.embeddings.hip_bert import load_state_dict
+        from ..encapsulation.embeddings.hip_qwen3 import HipQwen3Embeddings
+
+        tok = load_qwen_tokenizer(self.type, self.tokenizer_path, self.vocab_path, self.merges_path)
+        eos = self.eos_token_id if self.eos_token_id is not None else tok.convert_tokens_to_ids(self.eos_token)
+        if self.append_eos and eos is None:
+            raise ValueError(f"{self.type}: the tokenizer has no {self.eos_token!r} token: give eos_token_id")
+        lm = HipCausalLM(load_state_dict(self.weights_path), self.num_attention_heads, self.num_key_value_heads,
+                         self.head_dim, rms_norm_eps=self.rms_norm_eps, rope_theta=self.rope_theta, device=self.device,
+                         tie_word_embeddings=self.tie_word_embeddings)
+        return BuiltModule(config=self, impl=HipQwen3Embeddings(
+            lm, tok.encode, prompt=self.prompt, query_prompt=self.query_prompt, dim=self.dim, normalize=self.normalize,
+            max_length=self.max_length, batch_tokens=self.batch_tokens, append_eos=self.append_eos,
+            eos_token_id=0 if eos is None else int(eos), prefix_cache=self.prefix_cache))
+
+
+EmbeddingsConfig = Annotated[Union[TableEmbeddingsConfig, HipBertEmbeddingsConfig, HipQwen3EmbeddingsConfig],
+                             Field(discriminator="type")]
 
 
 class HipFlatVectorStoreConfig(AbstractConfig):
@@ -265,6 +313,69 @@ class HipLogitRerankerConfig(AbstractConfig):
                                                               instruction=self.instruction, device=self.device))
 
 
+# vocab.json carries no added tokens; Qwen2 / Qwen3 checkpoints list these, in this order, from id 151643 on
+# (tokenizer_config.json: added_tokens_decoder) — tokenizer.json has them inside and needs none of this
+QWEN_FIRST_SPECIAL_ID = 151643
+QWEN_SPECIAL_TOKENS = (
+    "<|endoftext|>", "<|im_start|>", "<|im_end|>", "<|object_ref_start|>", "<|object_ref_end|>", "<|box_start|>",
+    "<|box_end|>", "<|quad_start|>", "<|quad_end|>", "<|vision_start|>", "<|vision_end|>", "<|vision_pad|>",
+    "<|image_pad|>", "<|video_pad|>", "<tool_call>", "</tool_call>", "<|fim_prefix|>", "<|fim_middle|>",
+    "<|fim_suffix|>", "<|fim_pad|>", "<|repo_name|>", "<|file_sep|>", "<tool_response>", "</tool_response>",
+    "<think>", "</think>")
+
+
+def load_qwen_tokenizer(who: str, tokenizer_path: Optional[str], vocab_path: Optional[str], merges_path: Optional[str]):
+    """The tokenizer of a Qwen2 / Qwen3 checkpoint from local files: its tokenizer.json, or vocab.json + merges.txt (byte-level
+    BPE, rag_arc_amd.core.rerank.bpe).  Has encode(text) -> ids and convert_tokens_to_ids(token).  `who`: the config's tag,
+    for the error messages."""
+    from ..core.rerank.bpe import ByteLevelBPETokenizer
+
+    if tokenizer_path:
+        import json
+
+        with open(tokenizer_path, encoding="utf-8") as fh:
+            kind = json.load(fh).get("model", {}).get("type")
+        if kind == "BPE":
+            tok = ByteLevelBPETokenizer.from_tokenizer_json(tokenizer_path)
+        else:                                   # another tokenizer model: the library AutoTokenizer itself loads it with
+            from tokenizers import Tokenizer
+
+            lib_tok = Tokenizer.from_file(tokenizer_path)
+
+            class _LibraryTokenizer:
+                encode = staticmethod(lambda text: lib_tok.encode(text, add_special_tokens=False).ids)
+                convert_tokens_to_ids = staticmethod(lib_tok.token_to_id)
+
+            tok = _LibraryTokenizer
+    elif vocab_path and merges_path:
+        import json
+        import os
+
+        # the added tokens: the checkpoint's own list (tokenizer_config.json: added_tokens_decoder) when it lies next to
+        # vocab.json; otherwise Qwen2 / Qwen3's, but only if they fit THIS vocabulary — the first special id must follow
+        # the last vocab.json id and none of the tokens may already be an ordinary token; anything else fails loudly
+        special = None
+        cfg_path = os.path.join(os.path.dirname(os.path.abspath(vocab_path)), "tokenizer_config.json")
+        if os.path.exists(cfg_path):
+            with open(cfg_path, encoding="utf-8") as fh:
+                dec = json.load(fh).get("added_tokens_decoder") or {}
+            special = {v["content"]: int(i) for i, v in dec.items()} or None
+        if special is None:
+            with open(vocab_path, encoding="utf-8") as fh:
+                vocab = json.load(fh)
+            clash = [t for t in QWEN_SPECIAL_TOKENS if t in vocab]
+            if max(vocab.values()) + 1 != QWEN_FIRST_SPECIAL_ID or clash:
+                raise ValueError(f"{who}: {vocab_path} is not Qwen2/Qwen3's vocabulary (last id "
+                                 f"{max(vocab.values())}, expected {QWEN_FIRST_SPECIAL_ID - 1}; special tokens already "
+                                 f"present: {clash[:3]}): give tokenizer_path (tokenizer.json) or put the checkpoint's "
+                                 f"tokenizer_config.json next to vocab.json")
+            special = {t: i for i, t in enumerate(QWEN_SPECIAL_TOKENS, start=QWEN_FIRST_SPECIAL_ID)}
+        tok = ByteLevelBPETokenizer.from_files(vocab_path, merges_path, special)
+    else:
+        raise ValueError(f"{who}: give tokenizer_path, or vocab_path and merges_path")
+    return tok
+
+
 class HipQwen3RerankerConfig(AbstractConfig):
     """The reference's Qwen3Reranker (core/rerank/Reranker_Qwen3.py:6-75) with the LM forward on the MI355X
     (rarc_lm_yes_no_logits).  `weights_path`: a Qwen3ForCausalLM state dict (.safetensors / .npz, HuggingFace names);
@@ -286,67 +397,17 @@ class HipQwen3RerankerConfig(AbstractConfig):
     device: int = 0
 
     def build(self) -> AbstractModule:
-        from ..core.rerank.bpe import ByteLevelBPETokenizer
         from ..core.rerank.hip_qwen3 import HipCausalLM, HipQwen3Reranker
         from ..encapsulation.embeddings.hip_bert import load_state_dict
 
-        if self.tokenizer_path:
-            import json
-
-            with open(self.tokenizer_path, encoding="utf-8") as fh:
-                kind = json.load(fh).get("model", {}).get("type")
-            if kind == "BPE":
-                tok = ByteLevelBPETokenizer.from_tokenizer_json(self.tokenizer_path)
-            else:                                   # another tokenizer model: the library AutoTokenizer itself loads it with
-                from tokenizers import Tokenizer
-
-                lib_tok = Tokenizer.from_file(self.tokenizer_path)
-
-                class _LibraryTokenizer:
-                    encode = staticmethod(lambda text: lib_tok.encode(text, add_special_tokens=False).ids)
-                    convert_tokens_to_ids = staticmethod(lib_tok.token_to_id)
-
-                tok = _LibraryTokenizer
-        elif self.vocab_path and self.merges_path:
-            import json
-            import os
-
-            # the added tokens: the checkpoint's own list (tokenizer_config.json: added_tokens_decoder) when it lies next to
-            # vocab.json; otherwise Qwen2 / Qwen3's, but only if they fit THIS vocabulary — the first special id must follow
-            # the last vocab.json id and none of the tokens may already be an ordinary token; anything else fails loudly
-            special = None
-            cfg_path = os.path.join(os.path.dirname(os.path.abspath(self.vocab_path)), "tokenizer_config.json")
-            if os.path.exists(cfg_path):
-                with open(cfg_path, encoding="utf-8") as fh:
-                    dec = json.load(fh).get("added_tokens_decoder") or {}
-                special = {v["content"]: int(i) for i, v in dec.items()} or None
-            if special is None:
-                with open(self.vocab_path, encoding="utf-8") as fh:
-                    vocab = json.load(fh)
-                clash = [t for t in self.SPECIAL_TOKENS if t in vocab]
-                if max(vocab.values()) + 1 != self.FIRST_SPECIAL_ID or clash:
-                    raise ValueError(f"hip_qwen3_reranker: {self.vocab_path} is not Qwen2/Qwen3's vocabulary (last id "
-                                     f"{max(vocab.values())}, expected {self.FIRST_SPECIAL_ID - 1}; special tokens already "
-                                     f"present: {clash[:3]}): give tokenizer_path (tokenizer.json) or put the checkpoint's "
-                                     f"tokenizer_config.json next to vocab.json")
-                special = {t: i for i, t in enumerate(self.SPECIAL_TOKENS, start=self.FIRST_SPECIAL_ID)}
-            tok = ByteLevelBPETokenizer.from_files(self.vocab_path, self.merges_path, special)
-        else:
-            raise ValueError("hip_qwen3_reranker: give tokenizer_path, or vocab_path and merges_path")
+        tok = load_qwen_tokenizer(self.type, self.tokenizer_path, self.vocab_path, self.merges_path)
         lm = HipCausalLM(load_state_dict(self.weights_path), self.num_attention_heads, self.num_key_value_heads,
                          self.head_dim, rms_norm_eps=self.rms_norm_eps, rope_theta=self.rope_theta, device=self.device)
         rr = HipQwen3Reranker.from_tokenizer(lm, tok, max_length=self.max_length, instruction=self.instruction)
         return BuiltModule(config=self, impl=rr)
 
-    # vocab.json carries no added tokens; Qwen2 / Qwen3 checkpoints list these, in this order, from id 151643 on
-    # (tokenizer_config.json: added_tokens_decoder) — tokenizer.json has them inside and needs none of this
-    FIRST_SPECIAL_ID: ClassVar[int] = 151643
-    SPECIAL_TOKENS: ClassVar[tuple] = (
-        "<|endoftext|>", "<|im_start|>", "<|im_end|>", "<|object_ref_start|>", "<|object_ref_end|>", "<|box_start|>",
-        "<|box_end|>", "<|quad_start|>", "<|quad_end|>", "<|vision_start|>", "<|vision_end|>", "<|vision_pad|>",
-        "<|image_pad|>", "<|video_pad|>", "<tool_call>", "</tool_call>", "<|fim_prefix|>", "<|fim_middle|>",
-        "<|fim_suffix|>", "<|fim_pad|>", "<|repo_name|>", "<|file_sep|>", "<tool_response>", "</tool_response>",
-        "<think>", "</think>")
+    FIRST_SPECIAL_ID: ClassVar[int] = QWEN_FIRST_SPECIAL_ID
+    SPECIAL_TOKENS: ClassVar[tuple] = QWEN_SPECIAL_TOKENS
 
 
 RerankerConfig = Annotated[Union[HipLogitRerankerConfig, HipQwen3RerankerConfig], Field(discriminator="type")]

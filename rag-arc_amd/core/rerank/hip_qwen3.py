@@ -26,10 +26,15 @@ from .hip_reranker import HipLogitReranker
 
 
 class HipCausalLM:
-    """Qwen3-style decoder weights in HBM + the last-position (no, yes) logits of left-padded token batches."""
+    """Qwen3-style decoder weights in HBM + what the last position of left-padded token batches gives: the (no, yes) logits
+    (the reranker) or the final-normed hidden state itself (embed_last*: decoder-LM embeddings, rarc_lm_embed_last)."""
 
     def __init__(self, state_dict: Dict[str, "np.ndarray"], num_attention_heads: int, num_key_value_heads: int,
-                 head_dim: int, rms_norm_eps: float = 1e-6, rope_theta: float = 1e6, device: int = 0, fold_norms: bool = True):
+                 head_dim: int, rms_norm_eps: float = 1e-6, rope_theta: float = 1e6, device: int = 0, fold_norms: bool = True,
+                 tie_word_embeddings: bool = True):
+        """`state_dict`: Qwen3ForCausalLM names, or a bare Qwen3Model's (no "model." prefix, no head — what the
+        Qwen3-Embedding checkpoints hold).  Without `lm_head.weight` the head is the embedding table when
+        `tie_word_embeddings` (the checkpoint's config.json), else there is none: embed_last* work, the logits methods raise."""
         import torch
 
         if not torch.cuda.is_available():
@@ -37,6 +42,8 @@ class HipCausalLM:
         self.torch, self.lib = torch, B.load_library()
         self.device = torch.device("cuda", device)
         sd = state_dict
+        if "model.embed_tokens.weight" not in sd and "embed_tokens.weight" in sd:
+            sd = {"model." + k: v for k, v in sd.items()}
 
         def f16(v):
             if isinstance(v, torch.Tensor):
@@ -44,7 +51,8 @@ class HipCausalLM:
             return torch.as_tensor(np.asarray(v), dtype=torch.float32).to(self.device).half().contiguous()
 
         self.embed = f16(sd["model.embed_tokens.weight"])
-        self.lm_head = f16(sd["lm_head.weight"]) if "lm_head.weight" in sd else self.embed   # tied embeddings
+        # tied embeddings: the table is the head; untied and absent (a Qwen3Model checkpoint): no head, embeddings only
+        self.lm_head = f16(sd["lm_head.weight"]) if "lm_head.weight" in sd else (self.embed if tie_word_embeddings else None)
         self.final_norm = f16(sd["model.norm.weight"])
         self.vocab, self.hidden = int(self.embed.shape[0]), int(self.embed.shape[1])
         self.n_q, self.n_kv, self.head_dim = int(num_attention_heads), int(num_key_value_heads), int(head_dim)
@@ -80,9 +88,101 @@ class HipCausalLM:
         self._layer_tab = (B.LmLayer * len(self.layers))(*[
             B.LmLayer(**{k: v.data_ptr() for k, v in w.items()}) for w in self.layers])
         self._model = B.LmModel(self.hidden, len(self.layers), self.n_q, self.n_kv, self.head_dim, self.inter, self.vocab,
-                                float(rms_norm_eps), float(rope_theta), self.embed.data_ptr(), self.lm_head.data_ptr(),
+                                float(rms_norm_eps), float(rope_theta), self.embed.data_ptr(),
+                                None if self.lm_head is None else self.lm_head.data_ptr(),
                                 self.final_norm.data_ptr(), self._zero.data_ptr(), self._layer_tab)
+        # rarc_lm_prefix_kv asks for a complete model although it stops before the head: a headless model hands it the
+        # embedding table in that slot, which the call never reads
+        self._model_kv = self._model if self.lm_head is not None else B.LmModel(
+            *[getattr(self._model, f) if f != "lm_head" else self.embed.data_ptr() for f, _ in B.LmModel._fields_])
         self._ws = None
+
+    def _need_head(self, what: str):
+        if self.lm_head is None:
+            raise B.RarcError(f"{what}: this model has no lm_head (a Qwen3Model checkpoint with untied embeddings): "
+                              "it embeds (embed_last), it cannot give logits")
+
+    def _left_padded(self, input_ids, attention_mask):
+        """Host batch [n][L] LEFT padded -> (ids int32 [n_pad][L32], start int32 [n_pad], n): tokens (GEMM rows) must be a
+        multiple of 128, so the length is padded on the LEFT to a multiple of 32 (masked positions; rotary embeddings are
+        relative, so shifting every real token by the same amount changes nothing) and the batch to a multiple of 4 with
+        one-token sequences."""
+        ids = np.asarray(input_ids, dtype=np.int32)
+        mask = np.asarray(attention_mask).astype(bool)
+        if ids.ndim != 2 or mask.shape != ids.shape or ids.shape[0] == 0:
+            raise ValueError("input_ids and attention_mask must be [n][L]")
+        n, L = ids.shape
+        if not mask[:, -1].all() or (np.diff(mask.astype(np.int8), axis=1) < 0).any():
+            raise ValueError("batches must be LEFT padded (the reference's tokenizer uses padding_side='left')")
+        if ids[mask].min() < 0 or ids[mask].max() >= self.vocab:
+            raise ValueError(f"token ids must lie in [0, {self.vocab})")
+        start = (L - mask.sum(axis=1)).astype(np.int32)
+        L32 = -(-L // 32) * 32
+        if L32 != L:
+            ids = np.concatenate([np.zeros((n, L32 - L), np.int32), ids], axis=1)
+            start = start + (L32 - L)
+            L = L32
+        n_pad = -(-n // 4) * 4
+        if n_pad != n:
+            ids = np.concatenate([ids, np.zeros((n_pad - n, L), np.int32)])
+            start = np.concatenate([start, np.full(n_pad - n, L - 1, np.int32)])
+        return np.ascontiguousarray(np.where(ids < 0, 0, ids)), np.ascontiguousarray(start), n
+
+    def _workspace(self, n_tokens: int):
+        need = int(self.lib.rarc_lm_workspace_bytes(ctypes.addressof(self._model), n_tokens))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = self.torch.empty(need, dtype=self.torch.uint8, device=self.device)
+        return self._ws
+
+    def embed_last(self, input_ids, attention_mask, dim: Optional[int] = None, normalize: bool = True):
+        """Last-token embeddings of a LEFT-padded host batch [n][L] (sentence-transformers' Pooling(lasttoken) over a
+        decoder: the final-normed hidden state of every row's last token), the first `dim` components (None = hidden),
+        L2-normalised over those when `normalize`.  Returns an fp32 device tensor [n][dim]."""
+        t = self.torch
+        ids, start, n = self._left_padded(input_ids, attention_mask)
+        with t.cuda.device(self.device):
+            out = self.embed_last_device(t.from_numpy(ids).to(self.device), t.from_numpy(start).to(self.device), dim, normalize)
+        return out[:n]
+
+    def embed_last_device(self, d_ids, d_start, dim: Optional[int] = None, normalize: bool = True, out=None, prefix=None,
+                          prefix_of=None):
+        """embed_last() for batches that are already on the device: int32 tensors [n][L] (LEFT padded) and [n] (index of
+        each sequence's first real token), n * L a multiple of 128.  Nothing is copied, read back or validated on the host.
+        `out`: optional fp32 [n][>= dim] tensor with unit column stride (only the first dim columns are written).  `prefix` /
+        `prefix_of`: as in yes_no_logits_device — the batch holds the REMAINDERS, the embeddings are those of prefix +
+        remainder.  Returns fp32 [n][dim]."""
+        t = self.torch
+        if d_ids.dtype != t.int32 or d_start.dtype != t.int32 or d_ids.ndim != 2 or not d_ids.is_cuda:
+            raise ValueError("embed_last_device takes int32 device tensors [n][L], [n]")
+        n, L = d_ids.shape
+        if n * L == 0 or (n * L) % 128 or d_start.shape != (n,):
+            raise ValueError("n * L must be a positive multiple of 128")
+        if (prefix is None) != (prefix_of is None):
+            raise ValueError("prefix and prefix_of go together")
+        dim = self.hidden if dim is None else int(dim)
+        if not 1 <= dim <= self.hidden:
+            raise ValueError(f"dim must lie in [1, {self.hidden}]")
+        with t.cuda.device(self.device):
+            ws = self._workspace(n * L)
+            if out is None:
+                out = t.empty((n, dim), dtype=t.float32, device=self.device)
+            elif out.dtype != t.float32 or out.ndim != 2 or out.shape[0] != n or out.shape[1] < dim or out.stride(1) != 1 \
+                    or out.stride(0) < dim or out.device != self.device:
+                raise ValueError("out must be an fp32 [n][>= dim] tensor on the model's device with unit column stride")
+            st = t.cuda.current_stream(self.device).cuda_stream
+            if prefix is None:
+                B.check(self.lib.rarc_lm_embed_last(ctypes.addressof(self._model), d_ids.contiguous().data_ptr(),
+                                                    d_start.contiguous().data_ptr(), n, L, dim, int(bool(normalize)), ws.data_ptr(),
+                                                    ws.numel(), out.data_ptr(), out.stride(0), st), "rarc_lm_embed_last")
+            else:
+                if prefix_of.dtype != t.int32 or prefix_of.shape != (n,) or not prefix_of.is_cuda:
+                    raise ValueError("prefix_of must be an int32 device tensor [n]")
+                B.check(self.lib.rarc_lm_embed_last_prefixed(
+                    ctypes.addressof(self._model), d_ids.contiguous().data_ptr(), d_start.contiguous().data_ptr(), n, L,
+                    prefix_of.contiguous().data_ptr(), prefix["cache"].data_ptr(), prefix["n"], prefix["P"],
+                    prefix["start"].data_ptr(), dim, int(bool(normalize)), ws.data_ptr(), ws.numel(), out.data_ptr(),
+                    out.stride(0), st), "rarc_lm_embed_last_prefixed")
+            return out[:, :dim]
 
     def _interleave8(self, gate, up):
         """[2*inter][hidden]: 8 gate_proj rows, then the 8 up_proj rows of the same features, and so on — the layout
@@ -95,36 +195,17 @@ class HipCausalLM:
 
     def yes_no_logits(self, input_ids, attention_mask, no_id: int, yes_id: int):
         """input_ids / attention_mask: [n][L] LEFT padded (host arrays).  Returns fp16 device tensor [n][2] = (no, yes)."""
+        self._need_head("yes_no_logits")
         t = self.torch
-        ids = np.asarray(input_ids, dtype=np.int32)
-        mask = np.asarray(attention_mask).astype(bool)
-        if ids.ndim != 2 or mask.shape != ids.shape or ids.shape[0] == 0:
-            raise ValueError("input_ids and attention_mask must be [n][L]")
-        n, L = ids.shape
-        if not mask[:, -1].all() or (np.diff(mask.astype(np.int8), axis=1) < 0).any():
-            raise ValueError("batches must be LEFT padded (the reference's tokenizer uses padding_side='left')")
-        if ids[mask].min() < 0 or ids[mask].max() >= self.vocab or not (0 <= no_id < self.vocab and 0 <= yes_id < self.vocab):
+        if not (0 <= no_id < self.vocab and 0 <= yes_id < self.vocab):
             raise ValueError(f"token ids must lie in [0, {self.vocab})")
-        start = (L - mask.sum(axis=1)).astype(np.int32)
-        # tokens (GEMM rows) must be a multiple of 128: pad the length on the LEFT to a multiple of 32 (masked
-        # positions; rotary embeddings are relative, so shifting every real token by the same amount changes nothing)
-        # and the batch to a multiple of 4 with one-token sequences
-        L32 = -(-L // 32) * 32
-        if L32 != L:
-            ids = np.concatenate([np.zeros((n, L32 - L), np.int32), ids], axis=1)
-            start = start + (L32 - L)
-            L = L32
-        n_pad = -(-n // 4) * 4
-        if n_pad != n:
-            ids = np.concatenate([ids, np.zeros((n_pad - n, L), np.int32)])
-            start = np.concatenate([start, np.full(n_pad - n, L - 1, np.int32)])
+        ids, start, n = self._left_padded(input_ids, attention_mask)
+        n_pad, L = ids.shape
         with t.cuda.device(self.device):
             st = t.cuda.current_stream(self.device).cuda_stream
-            d_ids = t.from_numpy(np.ascontiguousarray(np.where(ids < 0, 0, ids))).to(self.device)
-            d_start = t.from_numpy(np.ascontiguousarray(start)).to(self.device)
-            need = int(self.lib.rarc_lm_workspace_bytes(ctypes.addressof(self._model), n_pad * L))
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = t.empty(need, dtype=t.uint8, device=self.device)
+            d_ids = t.from_numpy(ids).to(self.device)
+            d_start = t.from_numpy(start).to(self.device)
+            self._workspace(n_pad * L)
             out = t.empty((n_pad, 2), dtype=t.float16, device=self.device)
             B.check(self.lib.rarc_lm_yes_no_logits(ctypes.addressof(self._model), d_ids.data_ptr(), d_start.data_ptr(), n_pad,
                                                    L, int(no_id), int(yes_id), self._ws.data_ptr(), self._ws.numel(),
@@ -149,7 +230,7 @@ class HipCausalLM:
             cache = t.empty(int(self.lib.rarc_lm_prefix_cache_bytes(ctypes.addressof(self._model), n * P)), dtype=t.uint8,
                             device=self.device)
             d_start = d_start.contiguous()
-            B.check(self.lib.rarc_lm_prefix_kv(ctypes.addressof(self._model), d_ids.contiguous().data_ptr(), d_start.data_ptr(), n, P,
+            B.check(self.lib.rarc_lm_prefix_kv(ctypes.addressof(self._model_kv), d_ids.contiguous().data_ptr(), d_start.data_ptr(), n, P,
                                                self._ws.data_ptr(), self._ws.numel(), cache.data_ptr(), cache.numel(),
                                                t.cuda.current_stream(self.device).cuda_stream), "rarc_lm_prefix_kv")
         return {"cache": cache, "n": n, "P": P, "start": d_start}
@@ -160,6 +241,7 @@ class HipCausalLM:
         validated on the host (the kernels clamp token ids into the table).  Returns fp16 [n][2] = (no, yes).
         With `prefix` (from prefix_kv_device) and `prefix_of` (int32 [n]: the prefix each sequence continues, -1 none) the
         batch holds only the REMAINDERS of the prompts; the logits are those of prefix + remainder."""
+        self._need_head("yes_no_logits_device")
         t = self.torch
         if d_ids.dtype != t.int32 or d_start.dtype != t.int32 or d_ids.ndim != 2 or not d_ids.is_cuda:
             raise ValueError("yes_no_logits_device takes int32 device tensors [n][L], [n]")

@@ -869,6 +869,42 @@ __global__ __launch_bounds__(64) void rarc_lm_last_logits_kernel(const half_t* x
   }
 }
 
+// ---- last position: final RMSNorm, then the row itself as an fp32 embedding (last-token pooling; the ending of a
+// sentence-transformers decoder embedder: Pooling(lasttoken) [+ truncate_dim] [+ Normalize]).  Same roundings as the logits
+// kernel above: nv[c] = half(w_final[c] * half(x[c] * inv)).  normalize: out = nv / max(||nv[0..out_dim)||, 1e-12), the sum
+// of squares in fp32 over the first out_dim components only; an all-zero row stays zero.
+__global__ __launch_bounds__(64) void rarc_lm_last_embed_kernel(const half_t* x, const half_t* w_final, float eps, int row_stride,
+                                                                int row_off, int H, int out_dim, int normalize, float* out,
+                                                                long long ld_out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const half_t* xr = x + ((size_t)b * row_stride + row_off) * H;  // [T][H] rows: stride L, offset L-1; compact rows: 1, 0
+  float ss = 0.f;
+  for (int c = lane; c < H; c += 64) ss = __builtin_fmaf((float)xr[c], (float)xr[c], ss);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
+  const float inv = 1.0f / __builtin_sqrtf(ss / (float)H + eps);
+  float scale = 1.0f;
+  if (normalize) {
+    float nn = 0.f;
+    for (int c = lane; c < out_dim; c += 64) {
+      const float nv = (float)(half_t)((float)w_final[c] * (float)(half_t)((float)xr[c] * inv));
+      nn = __builtin_fmaf(nv, nv, nn);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nn += __shfl_xor(nn, o, 64);
+    scale = __builtin_fmaxf(__builtin_sqrtf(nn), 1e-12f);
+  }
+  float* orow = out + (size_t)b * (size_t)ld_out;
+  // (one component per trip, like the logits kernel's loop: vectorised by two, hipcc packs x * inv into v_pk_mul_f32 +
+  //  v_cvt_pk_f16_f32 — two roundings — where the single trip takes v_fma_mixlo_f16, which rounds the exact product once;
+  //  one component in ~10^4 then differs from the logits path in its last fp16 bit: tests/test_gpu_lm_embed.py, bit identity)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+  for (int c = lane; c < out_dim; c += 64) {
+    const float nv = (float)(half_t)((float)w_final[c] * (float)(half_t)((float)xr[c] * inv));
+    orow[c] = normalize ? nv / scale : nv;
+  }
+}
+
 // ---- last positions: dst[s] = src[s*L + L-1] for s < n_seq, zero rows up to n_rows (a multiple of 128 for the GEMMs) ----
 __global__ __launch_bounds__(256) void rarc_lm_gather_last_kernel(const half_t* src, int L, int W, int n_seq, int n_rows, half_t* dst) {
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -914,26 +950,39 @@ __global__ __launch_bounds__(256) void rarc_lm_copy_kv_kernel(const half_t* __re
 // mode 0: logits of the last positions (d_out_f16); `use` = optional prefix cache the sequences attend to first
 // mode 1: fill `fill` (a prefix cache) with the k | v rows of every layer for these sequences; no logits, and the last
 //         layer stops after its q|k|v projection (nothing else of it is ever read)
+// mode 2: `emb` given — mode 0 with the other ending: the final-normed last rows themselves as fp32 embeddings
+//         (rarc_lm_last_embed_kernel); lm_head is not read and may be null.  `who` names the entry point in its messages.
 struct LmPrefixUse { const half_t* cache; const int32_t* pidx; const int32_t* pstart; int n_prefix, P; };
+struct LmEmbedOut { float* out; long long ld; int out_dim, normalize; const char* who; };
 static int lm_forward(const RarcLmModel* m, const int32_t* d_ids, const int32_t* d_start, int n_seq, int seq_len, int no_id,
                       int yes_id, void* d_ws, size_t ws_bytes, uint16_t* d_out_f16, void* stream, const LmPrefixUse* use,
-                      half_t* fill) {
-  RARC_REQUIRE(m && m->layers && d_ids && d_start && d_ws && (d_out_f16 || fill), RARC_E_INVALID, "rarc_lm_yes_no_logits: null pointer");
-  RARC_REQUIRE(m->embed && m->lm_head && m->final_norm && m->zero_bias, RARC_E_INVALID, "rarc_lm_yes_no_logits: incomplete model");
+                      half_t* fill, const LmEmbedOut* emb = nullptr) {
+  if (emb) {   // the embedding entries' own argument checks, before the shared ones (and before anything touches a device)
+    RARC_REQUIRE(m && m->layers && d_ids && d_start && d_ws && emb->out, RARC_E_INVALID, "%s: null pointer", emb->who);
+    RARC_REQUIRE(m->embed && m->final_norm && m->zero_bias, RARC_E_INVALID, "%s: incomplete model", emb->who);
+    RARC_REQUIRE(emb->out_dim >= 1 && emb->out_dim <= m->hidden, RARC_E_INVALID, "%s: out_dim %d outside [1, hidden = %d]", emb->who,
+                 emb->out_dim, m->hidden);
+    RARC_REQUIRE(emb->ld >= emb->out_dim, RARC_E_INVALID, "%s: ld_out %lld is smaller than out_dim %d", emb->who, emb->ld, emb->out_dim);
+    RARC_REQUIRE(n_seq > 0 && seq_len > 0 && (long long)n_seq * seq_len % 128 == 0, RARC_E_INVALID,
+                 "%s: n_seq*seq_len must be a positive multiple of 128 (got %lld)", emb->who, (long long)n_seq * seq_len);
+  }
+  const char* who = emb ? emb->who : "rarc_lm_yes_no_logits";
+  RARC_REQUIRE(m && m->layers && d_ids && d_start && d_ws && (d_out_f16 || fill || emb), RARC_E_INVALID, "%s: null pointer", who);
+  RARC_REQUIRE(m->embed && (m->lm_head || emb) && m->final_norm && m->zero_bias, RARC_E_INVALID, "%s: incomplete model", who);
   const int H = m->hidden, I = m->inter, DH = m->head_dim, NQ = m->n_q_heads, NKV = m->n_kv_heads;
-  RARC_REQUIRE(n_seq > 0 && seq_len > 0 && m->n_layers > 0, RARC_E_INVALID, "rarc_lm_yes_no_logits: empty batch or model");
+  RARC_REQUIRE(n_seq > 0 && seq_len > 0 && m->n_layers > 0, RARC_E_INVALID, "%s: empty batch or model", who);
   RARC_REQUIRE((DH == 64 || DH == 128) && NQ > 0 && NKV > 0 && NQ % NKV == 0, RARC_E_UNSUPPORTED,
-               "rarc_lm_yes_no_logits: head_dim must be 64 or 128 and the q heads a multiple of the kv heads");
+               "%s: head_dim must be 64 or 128 and the q heads a multiple of the kv heads", who);
   const int QKV = (NQ + 2 * NKV) * DH, QD = NQ * DH;
   RARC_REQUIRE(H % 128 == 0 && I % 128 == 0 && QKV % 128 == 0 && QD % 64 == 0 && H <= 8192, RARC_E_UNSUPPORTED,
-               "rarc_lm_yes_no_logits: hidden, inter and the fused qkv width must be multiples of 128");
+               "%s: hidden, inter and the fused qkv width must be multiples of 128", who);
   RARC_REQUIRE(m->vocab > 0 && no_id >= 0 && yes_id >= 0 && no_id < m->vocab && yes_id < m->vocab, RARC_E_INVALID,
-               "rarc_lm_yes_no_logits: token ids outside the vocabulary");
+               "%s: token ids outside the vocabulary", who);
   const long long t_ll = (long long)n_seq * seq_len;
   RARC_REQUIRE(t_ll % 128 == 0 && t_ll < (1ll << 31), RARC_E_UNSUPPORTED,
-               "rarc_lm_yes_no_logits: n_seq*seq_len must be a multiple of 128 (got %lld)", t_ll);
+               "%s: n_seq*seq_len must be a multiple of 128 (got %lld)", who, t_ll);
   const int T = (int)t_ll;
-  RARC_REQUIRE(ws_bytes >= rarc_lm_workspace_bytes(m, T), RARC_E_WORKSPACE, "rarc_lm_yes_no_logits: workspace too small");
+  RARC_REQUIRE(ws_bytes >= rarc_lm_workspace_bytes(m, T), RARC_E_WORKSPACE, "%s: workspace too small", who);
   hipStream_t s = (hipStream_t)stream;
   char* w = (char*)d_ws;
   // The 256-row tile kernels (and the SwiGLU epilogue that only they have) take M % 256 == 0: a batch of T = 256 j + 128
@@ -976,7 +1025,7 @@ static int lm_forward(const RarcLmModel* m, const int32_t* d_ids, const int32_t*
 
   const int P = use ? use->P : 0;
   const int rope_rows = P + seq_len;
-  RARC_REQUIRE(rope_rows <= T + 4096, RARC_E_UNSUPPORTED, "rarc_lm_yes_no_logits: prefix of %d rows is too long for this batch", P);
+  RARC_REQUIRE(rope_rows <= T + 4096, RARC_E_UNSUPPORTED, "%s: prefix of %d rows is too long for this batch", who, P);
   const size_t kv_cols = (size_t)2 * NKV * DH;
   const size_t cache_layer = use ? lm_align((size_t)use->n_prefix * P * kv_cols * 2) : (fill ? lm_align((size_t)T * kv_cols * 2) : 0);
   hipLaunchKernelGGL(rarc_lm_rope_table_kernel, dim3((rope_rows * (DH / 2) + 255) / 256), dim3(256), 0, s, rope_rows, DH,
@@ -1089,8 +1138,12 @@ static int lm_forward(const RarcLmModel* m, const int32_t* d_ids, const int32_t*
       hipLaunchKernelGGL(rarc_lm_rmsnorm_kernel, dim3(gb), dim3(256), 0, s, x_l, (const half_t*)d_l, (const half_t*)nullptr,
                          m->rms_eps, Mp, H, (half_t*)nullptr);
       RARC_HIP_CHECK(hipGetLastError());
-      hipLaunchKernelGGL(rarc_lm_last_logits_kernel, dim3(n_seq), dim3(64), 0, s, (const half_t*)x_l, (const half_t*)m->final_norm,
-                         (const half_t*)m->lm_head, m->rms_eps, 1, 0, H, no_id, yes_id, (half_t*)d_out_f16);
+      if (emb)
+        hipLaunchKernelGGL(rarc_lm_last_embed_kernel, dim3(n_seq), dim3(64), 0, s, (const half_t*)x_l, (const half_t*)m->final_norm,
+                           m->rms_eps, 1, 0, H, emb->out_dim, emb->normalize, emb->out, emb->ld);
+      else
+        hipLaunchKernelGGL(rarc_lm_last_logits_kernel, dim3(n_seq), dim3(64), 0, s, (const half_t*)x_l, (const half_t*)m->final_norm,
+                           (const half_t*)m->lm_head, m->rms_eps, 1, 0, H, no_id, yes_id, (half_t*)d_out_f16);
       RARC_HIP_CHECK(hipGetLastError());
       return RARC_OK;
     }
@@ -1121,8 +1174,12 @@ static int lm_forward(const RarcLmModel* m, const int32_t* d_ids, const int32_t*
                        T, H, (half_t*)nullptr);
     RARC_HIP_CHECK(hipGetLastError());
   }
-  hipLaunchKernelGGL(rarc_lm_last_logits_kernel, dim3(n_seq), dim3(64), 0, s, (const half_t*)x, (const half_t*)m->final_norm,
-                     (const half_t*)m->lm_head, m->rms_eps, seq_len, seq_len - 1, H, no_id, yes_id, (half_t*)d_out_f16);
+  if (emb)
+    hipLaunchKernelGGL(rarc_lm_last_embed_kernel, dim3(n_seq), dim3(64), 0, s, (const half_t*)x, (const half_t*)m->final_norm,
+                       m->rms_eps, seq_len, seq_len - 1, H, emb->out_dim, emb->normalize, emb->out, emb->ld);
+  else
+    hipLaunchKernelGGL(rarc_lm_last_logits_kernel, dim3(n_seq), dim3(64), 0, s, (const half_t*)x, (const half_t*)m->final_norm,
+                       (const half_t*)m->lm_head, m->rms_eps, seq_len, seq_len - 1, H, no_id, yes_id, (half_t*)d_out_f16);
   RARC_HIP_CHECK(hipGetLastError());
   return RARC_OK;
 }
@@ -1153,4 +1210,25 @@ extern "C" int rarc_lm_yes_no_logits_prefixed(const RarcLmModel* m, const int32_
   RARC_REQUIRE(n_prefix > 0 && prefix_len > 0 && prefix_len <= 4096, RARC_E_INVALID, "rarc_lm_yes_no_logits_prefixed: bad prefix shape");
   const LmPrefixUse use{(const half_t*)d_cache, d_prefix_of, d_prefix_start, n_prefix, prefix_len};
   return lm_forward(m, d_ids, d_start, n_seq, seq_len, no_id, yes_id, d_ws, ws_bytes, d_out_f16, stream, &use, nullptr);
+}
+
+// ---- decoder-LM embeddings: the same forward, ending in last-token pooling (+ Matryoshka truncation, + Normalize) ------------
+extern "C" int rarc_lm_embed_last(const RarcLmModel* m, const int32_t* d_ids, const int32_t* d_start, int n_seq, int seq_len,
+                                  int out_dim, int normalize, void* d_ws, size_t ws_bytes, float* d_out, int64_t ld_out,
+                                  void* stream) {
+  RARC_RANGE();
+  const LmEmbedOut emb{d_out, (long long)ld_out, out_dim, normalize ? 1 : 0, "rarc_lm_embed_last"};
+  return lm_forward(m, d_ids, d_start, n_seq, seq_len, 0, 0, d_ws, ws_bytes, nullptr, stream, nullptr, nullptr, &emb);
+}
+
+extern "C" int rarc_lm_embed_last_prefixed(const RarcLmModel* m, const int32_t* d_ids, const int32_t* d_start, int n_seq,
+                                           int seq_len, const int32_t* d_prefix_of, const void* d_cache, int n_prefix,
+                                           int prefix_len, const int32_t* d_prefix_start, int out_dim, int normalize, void* d_ws,
+                                           size_t ws_bytes, float* d_out, int64_t ld_out, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(m && d_prefix_of && d_cache && d_prefix_start && d_out, RARC_E_INVALID, "rarc_lm_embed_last_prefixed: null pointer");
+  RARC_REQUIRE(n_prefix > 0 && prefix_len > 0 && prefix_len <= 4096, RARC_E_INVALID, "rarc_lm_embed_last_prefixed: bad prefix shape");
+  const LmPrefixUse use{(const half_t*)d_cache, d_prefix_of, d_prefix_start, n_prefix, prefix_len};
+  const LmEmbedOut emb{d_out, (long long)ld_out, out_dim, normalize ? 1 : 0, "rarc_lm_embed_last_prefixed"};
+  return lm_forward(m, d_ids, d_start, n_seq, seq_len, 0, 0, d_ws, ws_bytes, nullptr, stream, &use, nullptr, &emb);
 }
