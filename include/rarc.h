@@ -826,6 +826,48 @@ int rarc_knn_graph(const float* d_rows, int64_t ld, int64_t n_rows, int d, int t
                    int cand_cap, int64_t* d_out_ids, double* d_out_scores, int32_t* d_out_count, uint32_t* d_flags, void* stream);
 
 /*
+ * Louvain communities of an undirected edge list — step 2 of the reference's entity de-duplication
+ * (encapsulation/database/graph_db/Base_Neo4j.py:646-658: gds.louvain.stream(graph, {maxIterations: 10}) over the SIMILAR edges
+ * rarc_similar_pairs finds), without a Neo4j server and its GDS plugin.  The algorithm is defined in integers (DESIGN 4.13c,
+ * restated by tests/louvain_ref.py); the answer does not depend on the order of the edges or on thread timing (csrc/louvain.hip).
+ * The loops over sweeps and levels are the caller's (graph_db/communities.py): three words are read per sweep, two per level.
+ * Limits of every entry: 2 <= n < 2^31 - 1 vertices, 1 <= m < 2^30 edges (every product of the rule then fits int64).
+ *
+ * rarc_graph_csr — one level's graph in d_graph (rarc_graph_csr_workspace_bytes(n, m) bytes, 0 for a refused shape):
+ *   d_pairs int64 [m][2], (i, j) with 0 <= i < j < n, each pair once (a pair outside that range is skipped);
+ *   d_weights uint32 [m] or null (every weight 1); d_loops uint32 [n] or null (no self-loops).
+ *   Adjacency in both directions (degree count, scan, fill: the order inside a row is arbitrary and nothing depends on it),
+ *   weighted degrees, M2, and the vertices listed by degree class for the sweep.
+ * rarc_louvain_init — slot 0 of d_state (rarc_louvain_workspace_bytes(n, m) bytes) becomes c(v) = v; d_out3 = {0, Qn, 0}.
+ * rarc_louvain_sweep — sweep number `sweep` (>= 0: it selects the movers) reads slot `cur` (0 | 1) and writes the other one:
+ *   labels, tot_C, sizes; d_out3 int64 [3] = {vertices moved, Qn of the new labelling, movers that had a target: moved, or held
+ *   back by the singleton rule — a sweep without any is idle}.  The caller keeps the sweep by passing
+ *   the other slot as `cur` next time and discards it by passing the same one.
+ * rarc_louvain_aggregate — after a level: the communities of slot `cur` are renumbered 0 .. n_c - 1 in ascending label order,
+ *   d_labels int64 [n0] (original vertex -> vertex of this level) is composed with that map in place, and the next level's
+ *   input is written: d_out_pairs int64 [m][2], d_out_weights uint32 [m] (weight per community pair, arbitrary order),
+ *   d_out_loops uint32 [n] (inside weight); d_out_counts int64 [2] = {n_c, m_c}.
+ * rarc_louvain_labels — d_labels int64 [n0] of any labelling with values in [0, n0) -> the smallest member of each label's
+ *   class, in place; d_ws: rarc_louvain_labels_workspace_bytes(n0) bytes.
+ * rarc_louvain_limits — out4 = {largest degree of the 8-lane form, of the wave form, of the LDS-table form, LDS table slots};
+ *   a vertex of a larger degree takes the global-memory table.
+ */
+size_t rarc_graph_csr_workspace_bytes(int64_t n, int64_t m);
+int rarc_graph_csr(const int64_t* d_pairs, const uint32_t* d_weights, const uint32_t* d_loops, int64_t n, int64_t m, void* d_graph,
+                   size_t graph_bytes, void* stream);
+size_t rarc_louvain_workspace_bytes(int64_t n, int64_t m);
+int rarc_louvain_init(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, void* d_state, size_t state_bytes, int64_t* d_out3,
+                      void* stream);
+int rarc_louvain_sweep(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, void* d_state, size_t state_bytes, int cur, int sweep,
+                       int64_t* d_out3, void* stream);
+int rarc_louvain_aggregate(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, void* d_state, size_t state_bytes, int cur,
+                           int64_t* d_labels, int64_t n0, int64_t* d_out_pairs, uint32_t* d_out_weights, uint32_t* d_out_loops,
+                           int64_t* d_out_counts, void* stream);
+size_t rarc_louvain_labels_workspace_bytes(int64_t n0);
+int rarc_louvain_labels(int64_t* d_labels, int64_t n0, void* d_ws, size_t ws_bytes, void* stream);
+int rarc_louvain_limits(int* out4);
+
+/*
  * Deleting rows of a resident index: stable in-place compaction.  The reference deletes by clearing the index and
  * embedding every surviving text again (encapsulation/database/vector_db/VectorStore_Faiss.py:374-415); the surviving
  * rows are in HBM already, so here they move down over the holes: row i of the result is the i-th surviving row.

@@ -27,6 +27,35 @@ MAX_DIM = 4096
 MAX_TOP_K = 256      # csrc/knn.hip: KNN_KMAX
 
 
+def _pairs_on_device(lib, x, threshold: float, dev):
+    """rarc_similar_pairs' launch-and-regrow loop on contiguous fp32 rows [n >= 2][d] of `dev` (the current device):
+    (pairs int64 [cap][2], cosines float64 [cap], found) — device tensors whose first `found` entries are the pairs, in no
+    particular order.  `similar_pairs` copies them to the host; `entity_clusters` clusters them where they are."""
+    import torch
+
+    n, d = int(x.shape[0]), int(x.shape[1])
+    cand_cap, out_cap = 256, max(1024, 4 * n)
+    n_pad = (n + 255) // 256 * 256
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    flags = torch.zeros(1, dtype=torch.int32, device=dev)
+    while True:
+        ws = torch.empty(int(lib.rarc_similar_pairs_workspace_bytes(n, d, cand_cap)), dtype=torch.uint8, device=dev)
+        pairs = torch.empty((out_cap, 2), dtype=torch.int64, device=dev)
+        scores = torch.empty(out_cap, dtype=torch.float64, device=dev)
+        B.check(lib.rarc_similar_pairs(x.data_ptr(), x.stride(0), n, d, ctypes.c_double(threshold), ws.data_ptr(),
+                                       ws.numel(), cand_cap, pairs.data_ptr(), scores.data_ptr(), out_cap, count.data_ptr(),
+                                       flags.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "rarc_similar_pairs")
+        f, found = int(flags.item()), int(count.item())
+        if f == 0:
+            return pairs, scores, found
+        if f & 1:
+            if cand_cap >= n_pad:
+                raise B.RarcError("rarc_similar_pairs flagged a nomination list that holds every row")
+            cand_cap = min(4 * cand_cap, n_pad)
+        if f & 2:
+            out_cap = max(found, 2 * out_cap)       # (an overflowed list hid nominations: the count may still grow)
+
+
 def similar_pairs(embeddings, threshold: float = 0.95, device: int = 0, as_arrays: bool = False):
     """[(i, j, cosine)] for every i < j with cosine(embeddings[i], embeddings[j]) >= threshold, ordered by (i, j).
     embeddings: [n][d] array-like of floats (the reference holds python lists) or a torch tensor (used where it is).
@@ -56,28 +85,8 @@ def similar_pairs(embeddings, threshold: float = 0.95, device: int = 0, as_array
         raise B.RarcError(f"embeddings of {d} dimensions: the all-pairs kernel takes 1..{MAX_DIM}")
     if not 0.0 < float(threshold) <= 1.0:
         raise ValueError("threshold must lie in (0, 1]")
-    x = x.contiguous()
-    cand_cap, out_cap = 256, max(1024, 4 * n)
-    n_pad = (n + 255) // 256 * 256
-    count = torch.zeros(1, dtype=torch.int64, device=dev)
-    flags = torch.zeros(1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        while True:
-            ws = torch.empty(int(lib.rarc_similar_pairs_workspace_bytes(n, d, cand_cap)), dtype=torch.uint8, device=dev)
-            pairs = torch.empty((out_cap, 2), dtype=torch.int64, device=dev)
-            scores = torch.empty(out_cap, dtype=torch.float64, device=dev)
-            B.check(lib.rarc_similar_pairs(x.data_ptr(), x.stride(0), n, d, ctypes.c_double(float(threshold)), ws.data_ptr(),
-                                           ws.numel(), cand_cap, pairs.data_ptr(), scores.data_ptr(), out_cap, count.data_ptr(),
-                                           flags.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "rarc_similar_pairs")
-            f, found = int(flags.item()), int(count.item())
-            if f == 0:
-                break
-            if f & 1:
-                if cand_cap >= n_pad:
-                    raise B.RarcError("rarc_similar_pairs flagged a nomination list that holds every row")
-                cand_cap = min(4 * cand_cap, n_pad)
-            if f & 2:
-                out_cap = max(found, 2 * out_cap)       # (an overflowed list hid nominations: the count may still grow)
+        pairs, scores, found = _pairs_on_device(lib, x.contiguous(), float(threshold), dev)
         p = pairs[:found].cpu().numpy()
         s = scores[:found].cpu().numpy()
     order = np.lexsort((p[:, 1], p[:, 0]))

@@ -226,6 +226,16 @@ SIGNATURES = {
     "rarc_knn_graph_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
     "rarc_knn_graph": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, ctypes.c_double, c_void_p, c_size_t, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p]),
+    "rarc_graph_csr_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "rarc_graph_csr": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
+    "rarc_louvain_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "rarc_louvain_init": (c_int, [c_void_p, c_size_t, c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "rarc_louvain_sweep": (c_int, [c_void_p, c_size_t, c_int64, c_int64, c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p]),
+    "rarc_louvain_aggregate": (c_int, [c_void_p, c_size_t, c_int64, c_int64, c_void_p, c_size_t, c_int, c_void_p, c_int64, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_louvain_labels_workspace_bytes": (c_size_t, [c_int64]),
+    "rarc_louvain_labels": (c_int, [c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "rarc_louvain_limits": (c_int, [ctypes.POINTER(c_int)]),
     "rarc_compact_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
     "rarc_vmem_create": (c_int, [c_int, c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_void_p)]),
     "rarc_vmem_grow": (c_int, [c_void_p, c_size_t]),

@@ -1,0 +1,119 @@
+"""The Louvain rule of DESIGN §4.13c as tests/louvain_ref.py restates it: hand-checked cases, invariance under the order of the
+edge list, and — where networkx is installed — its quality beside networkx's own Louvain on the inputs the rule was tabled on."""
+import random
+
+import pytest
+
+from tests import louvain_ref as R
+
+
+def test_path_of_three_ends_in_one_community():
+    """Sweep 0 moves vertex 2 to 1 (0 may not join the larger singleton label 1), sweep 1 moves 0: Qn -6 -> -2 -> 0."""
+    trace = []
+    assert R.louvain(3, R.path_graph(3), trace=trace) == [0, 0, 0]
+    assert [e[-1] for e in trace if e[0] == "level"][0] == -6
+    assert [e[3] for e in trace if e[0] == "sweep"] == [-2, 0]
+
+
+def test_a_single_edge():
+    """Vertex 0 is a mover in every sweep but may not join the larger singleton label 1; vertex 1 is no mover before sweep 3.  The
+    sweeps 0..2 move nothing but are not idle — a mover has a target — so the level lasts until vertex 1 moves."""
+    trace = []
+    assert R.louvain(2, [(0, 1)], trace=trace) == [0, 0]
+    assert [e[1] for e in trace if e[0] == "sweep"] == [3]
+
+
+def test_singletons_of_a_perfect_matching_merge_towards_the_smaller_label():
+    """Every vertex's only gain is its partner.  Without the singleton rule two movers would swap labels and stay apart; with it
+    only the larger end moves, and only in a sweep in which it is a mover."""
+    n = 64
+    edges = [(2 * i, 2 * i + 1) for i in range(n // 2)]
+    comm = list(range(n))
+    adj = [dict() for _ in range(n)]
+    for a, b in edges:
+        adj[a][b] = adj[b][a] = 1
+    new, moved, targets = R.sweep(adj, [0] * n, [1] * n, n, comm, 0)
+    assert targets == sum(R.is_mover(v, 0) for v in range(n))
+    for a, b in edges:
+        assert new[a] == a and new[b] == (a if R.is_mover(b, 0) else b)
+    assert moved == sum(R.is_mover(b, 0) for _, b in edges) > 0
+    assert R.louvain(n, edges) == [v - v % 2 for v in range(n)]
+
+
+def test_disjoint_cliques_come_back_as_the_cliques():
+    sizes = [2, 3, 5, 8, 40, 1, 1]
+    n, edges = R.disjoint_cliques(sizes)
+    want, lo = [], 0
+    for s in sizes:
+        want += [lo] * s
+        lo += s
+    assert R.louvain(n, edges) == want
+
+
+def test_complete_bipartite_stays_all_singletons():
+    """The known limit of gains taken against the sweep's start: the first sweep of K30,30 overshoots and is discarded."""
+    n, edges = R.complete_bipartite(30, 30)
+    trace = []
+    assert R.louvain(n, edges, trace=trace) == list(range(n))
+    sweeps = [e for e in trace if e[0] == "sweep"]
+    assert len(sweeps) == 1 and sweeps[0][3] <= trace[0][2]
+
+
+@pytest.mark.parametrize("graph", [R.ring_of_cliques(30, 5), R.grid_graph(12, 9), (200, R.path_graph(200)), (64, R.cycle_graph(64))],
+                         ids=["ring", "grid", "path", "cycle"])
+def test_the_order_of_the_edge_list_does_not_matter(graph):
+    n, edges = graph
+    want = R.louvain(n, edges)
+    shuffled = list(edges)
+    random.Random(7).shuffle(shuffled)
+    assert R.louvain(n, shuffled) == want
+    assert R.normalise(n, [(b, a) for a, b in shuffled] + shuffled[:5]) == sorted(edges)
+
+
+def test_limits_on_sweeps_and_levels():
+    n, edges = 200, R.path_graph(200)
+    full, one_level, one_sweep = R.louvain(n, edges), R.louvain(n, edges, max_levels=1), R.louvain(n, edges, max_iterations=1)
+    assert len(set(full)) < len(set(one_level)) < n and len(set(full)) <= len(set(one_sweep)) < n
+    with pytest.raises(ValueError):
+        R.louvain(n, edges, max_iterations=0)
+    with pytest.raises(ValueError):
+        R.normalise(3, [(1, 1)])
+    with pytest.raises(ValueError):
+        R.normalise(3, [(0, 3)])
+
+
+def _nx_inputs(nx):
+    return {
+        "ring": nx.ring_of_cliques(30, 5),
+        "planted-20x50": nx.planted_partition_graph(20, 50, .3, .005, seed=1),
+        "planted-50x40": nx.planted_partition_graph(50, 40, .2, .002, seed=2),
+        "grid": nx.convert_node_labels_to_integers(nx.grid_2d_graph(40, 40)),
+        "barabasi-albert": nx.barabasi_albert_graph(3000, 3, seed=3),
+    }
+
+
+@pytest.mark.parametrize("name", ["ring", "planted-20x50", "planted-50x40", "grid", "barabasi-albert"])
+def test_modularity_beside_networkx(name):
+    """A condition, not a measurement: modularity >= networkx's minimum over seeds 0..4 minus 0.02 (the rule's worst gap on
+    these inputs was 0.0084 when it was written down), and Qn / M2^2 is networkx's modularity of the same partition."""
+    nx = pytest.importorskip("networkx")
+    G = _nx_inputs(nx)[name]
+    n = G.number_of_nodes()
+    edges = R.normalise(n, G.edges())
+    labels = R.louvain(n, edges)
+    qn, m2 = R.quality_of_labels(n, edges, labels)
+    mine = qn / m2 ** 2
+    parts = R.clusters_from_labels(labels, min_size=1)
+    assert abs(mine - nx.community.modularity(G, parts)) <= 1e-12
+    theirs = min(nx.community.modularity(G, nx.community.louvain_communities(G, seed=s)) for s in range(5))
+    print(f"{name}: this rule {mine:.4f}, networkx min over seeds 0..4 {theirs:.4f}")
+    assert mine >= theirs - 0.02
+
+
+def test_the_generators_are_networkx_s():
+    nx = pytest.importorskip("networkx")
+    for (n, edges), G in ((R.ring_of_cliques(30, 5), nx.ring_of_cliques(30, 5)),
+                          (R.grid_graph(40, 40), nx.convert_node_labels_to_integers(nx.grid_2d_graph(40, 40))),
+                          ((200, R.path_graph(200)), nx.path_graph(200)), ((64, R.cycle_graph(64)), nx.cycle_graph(64)),
+                          (R.complete_bipartite(30, 30), nx.complete_bipartite_graph(30, 30))):
+        assert n == G.number_of_nodes() and sorted(edges) == R.normalise(n, G.edges())
