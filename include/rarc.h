@@ -868,6 +868,45 @@ int rarc_louvain_labels(int64_t* d_labels, int64_t n0, void* d_ws, size_t ws_byt
 int rarc_louvain_limits(int* out4);
 
 /*
+ * Personalized PageRank over the graph rarc_graph_csr wrote, for a batch of nq queries at once — what a graph store is queried
+ * with (gds.pageRank.stream(graph, {sourceNodes, dampingFactor: 0.85, maxIterations: 20}); HippoRAG-style retrievers run one
+ * per query).  The rule is fixed point (restated by tests/ppr_ref.py): ONE = 2^40 units of mass, damping as
+ * damping_q16 / 65536, every sum an integer sum — the same bits for any order of the edges, either form of the step and any
+ * batch (csrc/ppr.hip).  The undirected graph's weights are uint32 >= 1 with a total below 2^31.
+ * Limits of every entry: 2 <= n < 2^31 - 1, 1 <= m < 2^30 (as rarc_graph_csr), 1 <= nq <= 256; refused before any launch.
+ * d_ws: rarc_ppr_workspace_bytes(n, m, nq) bytes (0 for a refused shape), 256-byte aligned: the state int64 [n][nq],
+ * vertex-major (teleport, p, and p // W in two slots), and the per-query delta and done words.
+ *
+ * rarc_ppr_seed — d_seeds int64 [nq][n_slots] (a vertex, or -1 = unused; 1 <= n_slots <= 64; a vertex may repeat),
+ *   d_seed_weights uint32 [nq][n_slots], each <= 2^20.  Writes the teleport vector t_q(v) = sum over q's slots naming v of
+ *   (w << 40) // Wq (Wq = the sum of q's weights; Wq = 0: the query scores 0 everywhere), p_0 = t, slot 0, and clears delta / done.
+ * rarc_ppr_step — one iteration p'(v) = ((65536 - a) t(v) + a flow(v)) >> 16, flow(v) = sum over neighbours u of
+ *   w_uv (p(u) // W(u)) (an isolated v: flow(v) = p(v)), for every query not frozen; it reads slot `cur` (0 | 1; 0 after the seed)
+ *   and writes the other: pass cur ^ 1 next time.  delta_q = max_v |p' - p|; a query with delta_q <= tolerance (in units of
+ *   2^-40) is frozen: done_q = 1 and its column is not updated again.  d_done_out: uint32 [nq] that receives the done words,
+ *   or null — a caller without a tolerance reads nothing between steps.
+ *   Two forms, picked by nq: up to 32 queries the lanes of a wave share a vertex's neighbours (vertex-parallel), beyond that a
+ *   lane is a query (query-parallel); a vertex of more than 64 neighbours is split across the waves of a workgroup in both.
+ * rarc_ppr_scores — d_out_scores double [nq][n] = p / 2^40, exact.
+ * rarc_ppr_topk — per query the top_k (1 .. 8192) vertices of positive score by (score descending, vertex ascending):
+ *   d_out_ids int64 [nq][top_k], d_out_scores double [nq][top_k], d_out_count int32 [nq] = min(top_k, vertices with a positive
+ *   score); slots past the count hold (-1, -inf).  The sort key carries the vertex in 24 bits: n >= 2^24 returns
+ *   RARC_E_UNSUPPORTED (rarc_ppr_scores has no such limit).  `cur` as rarc_ppr_step would get it next: the keys are built in
+ *   the slot that step would overwrite, so stepping may go on afterwards.
+ * rarc_ppr_limits — out6 = {largest degree a single wave walks (a larger one is split), largest nq of the vertex-parallel form,
+ *   largest nq, largest n_slots, largest top_k, bits of a vertex in the top-k key}.
+ */
+size_t rarc_ppr_workspace_bytes(int64_t n, int64_t m, int nq);
+int rarc_ppr_seed(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, const int64_t* d_seeds, const uint32_t* d_seed_weights,
+                  int nq, int n_slots, void* d_ws, size_t ws_bytes, void* stream);
+int rarc_ppr_step(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, int nq, int damping_q16, int64_t tolerance, int cur,
+                  void* d_ws, size_t ws_bytes, uint32_t* d_done_out, void* stream);
+int rarc_ppr_scores(int64_t n, int64_t m, int nq, const void* d_ws, size_t ws_bytes, double* d_out_scores, void* stream);
+int rarc_ppr_topk(int64_t n, int64_t m, int nq, int top_k, int cur, void* d_ws, size_t ws_bytes, int64_t* d_out_ids,
+                  double* d_out_scores, int32_t* d_out_count, void* stream);
+int rarc_ppr_limits(int* out6);
+
+/*
  * Deleting rows of a resident index: stable in-place compaction.  The reference deletes by clearing the index and
  * embedding every surviving text again (encapsulation/database/vector_db/VectorStore_Faiss.py:374-415); the surviving
  * rows are in HBM already, so here they move down over the holes: row i of the result is the i-th surviving row.

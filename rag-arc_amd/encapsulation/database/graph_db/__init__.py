@@ -1,8 +1,9 @@
 """The arithmetic steps of the reference's graph store that sit on the dense hot path's kernels: entity de-duplication by
 all-pairs cosine (encapsulation/database/graph_db/Base_Neo4j.py:538-583) and the Louvain communities of those pairs (:646-658),
-and event disambiguation by a k-nearest-neighbour graph (event_graphrag_neo4j.py:600-672).  The graph database itself is out
-of scope."""
+event disambiguation by a k-nearest-neighbour graph (event_graphrag_neo4j.py:600-672), and retrieval from the graph those
+build: personalized PageRank from the entities a query links to.  The graph database itself is out of scope."""
 from .communities import entity_clusters, louvain_communities
+from .pagerank import EntityGraph, personalized_pagerank
 from .similarity import knn_graph, similar_pairs
 
-__all__ = ["similar_pairs", "knn_graph", "louvain_communities", "entity_clusters"]
+__all__ = ["similar_pairs", "knn_graph", "louvain_communities", "entity_clusters", "EntityGraph", "personalized_pagerank"]

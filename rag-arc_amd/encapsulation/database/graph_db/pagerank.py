@@ -1,0 +1,285 @@
+"""Personalized PageRank over the entity graph, on the MI355X (csrc/ppr.hip): the retrieval a graph store is queried with.
+
+What it replaces: the reference stores entities, events and their relations and leaves every graph computation to Neo4j GDS;
+a retriever over that graph (HippoRAG-style, or upstream RAG-ARC's graph retriever) runs
+
+    CALL gds.pageRank.stream(graph, {sourceNodes: seeds, dampingFactor: 0.85, maxIterations: 20})
+
+once per query.  Here a batch of queries is one sparse-matrix x dense-matrix power iteration next to the CSR `rarc_graph_csr`
+built: `EntityGraph(n, pairs)` keeps the graph resident, `personalized_pagerank(seeds)` ranks from given seeds, and
+`retrieve(index, queries)` takes the seeds from a `FlatIndexF16` search without leaving HBM.
+
+The rule is fixed point (restated by tests/ppr_ref.py): the scores are the same bits for any order of the
+edges and any batch, and row q of a batch equals the one-query call.  No CPU fallback: without a device this raises."""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from ....hip import binding as B
+from .communities import MAX_EDGES, MAX_VERTICES
+
+ONE = 1 << 40                  # the unit of mass (csrc/ppr.hip)
+MAX_SEEDS = 64                 # seed slots per query
+MAX_SEED_WEIGHT = 1 << 20      # a seed weight after quantisation
+MAX_BATCH = 256                # queries per launch; larger batches are cut here
+MAX_TOP_K = 8192
+MAX_TOPK_VERTICES = 1 << 24    # the top-k key carries the vertex in 24 bits
+MAX_TOTAL_WEIGHT = 1 << 31     # total edge weight: every weighted degree then fits 32 bits
+
+
+def limits() -> dict:
+    """The shape limits of the kernels (csrc/ppr.hip): the largest degree one wave walks (a vertex of a larger one is split
+    across a workgroup), the largest batch of the vertex-parallel form of the step, and the argument limits."""
+    out = (ctypes.c_int * 6)()
+    B.check(B.load_library().rarc_ppr_limits(out), "rarc_ppr_limits")
+    return {"split_degree": out[0], "vertex_parallel_max_batch": out[1], "max_batch": out[2], "max_seeds": out[3], "max_top_k": out[4],
+            "topk_vertex_bits": out[5]}
+
+
+def quantise_seed_weights(w: np.ndarray) -> np.ndarray:
+    """float [B][s] >= 0 -> uint32: each row scaled so its largest weight is 1, then round(w * 2^20); an all-zero row stays zero"""
+    w = np.asarray(w, dtype=np.float64)
+    mx = w.max(axis=1, keepdims=True) if w.shape[1] else np.zeros((w.shape[0], 1))
+    safe = np.where(mx > 0, mx, 1.0)
+    return np.rint(w / safe * float(MAX_SEED_WEIGHT)).astype(np.uint32)
+
+
+def _normalise_pairs(n: int, pairs, weights):
+    """exactly louvain_communities' normalisation of host pairs (swapped to i < j, duplicates dropped); the weights of
+    duplicates add up"""
+    arr = np.asarray(pairs)
+    if arr.size == 0:
+        arr = np.zeros((0, 2), np.int64)
+    if arr.ndim != 2 or arr.shape[1] != 2:
+        raise ValueError(f"expected [m][2] pairs, got an array of shape {arr.shape}")
+    if not np.issubdtype(arr.dtype, np.integer):
+        if not np.all(arr == np.floor(arr)):
+            raise ValueError("pairs must be integers")
+    arr = arr.astype(np.int64)
+    w = None
+    if weights is not None:
+        w = np.asarray(weights)
+        if w.shape != (arr.shape[0],):
+            raise ValueError(f"expected {arr.shape[0]} weights, got an array of shape {w.shape}")
+        if not np.all(w == np.floor(w)) or (w.size and (w.min() < 1 or w.max() >= 1 << 32)):
+            raise ValueError("edge weights must be integers in [1, 2^32)")
+        w = w.astype(np.int64)
+    if arr.shape[0]:
+        if arr.min() < 0 or arr.max() >= n:
+            raise ValueError(f"a pair names a vertex outside [0, {n})")
+        if np.any(arr[:, 0] == arr[:, 1]):
+            raise ValueError("a pair (i, i): self-loops are not part of the input")
+        arr, inverse = np.unique(np.stack([arr.min(axis=1), arr.max(axis=1)], axis=1), axis=0, return_inverse=True)
+        if w is not None:
+            w = np.bincount(inverse.ravel(), weights=w.astype(np.float64), minlength=arr.shape[0]).astype(np.int64)
+    return arr, w
+
+
+class EntityGraph:
+    """An undirected graph on n vertices, resident on the device as the CSR of `rarc_graph_csr`.
+    pairs: an [m][2] array-like — normalised as louvain_communities normalises it: swapped to i < j, duplicates dropped (the
+    weights of duplicates add up) — or an int64 device tensor [m][2], used where it is: every pair i < j, each once.
+    weights: integers >= 1 per pair (unit by default), their total below 2^31."""
+
+    def __init__(self, n: int, pairs, weights=None, device: int = 0):
+        import torch
+
+        n = int(n)
+        on_device = isinstance(pairs, torch.Tensor) and pairs.is_cuda
+        if on_device:
+            if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int64:
+                raise ValueError(f"expected an int64 [m][2] tensor of pairs, got {pairs.dtype} {tuple(pairs.shape)}")
+            m = int(pairs.shape[0])
+            w = None
+            if weights is not None:
+                w = np.asarray(weights.cpu().numpy() if isinstance(weights, torch.Tensor) else weights)
+                if w.shape != (m,) or not np.all(w == np.floor(w)) or (m and (w.min() < 1 or w.max() >= 1 << 32)):
+                    raise ValueError(f"edge weights must be {m} integers in [1, 2^32)")
+                w = w.astype(np.int64)
+        else:
+            arr, w = _normalise_pairs(n, pairs.cpu().numpy() if isinstance(pairs, torch.Tensor) else pairs, weights)
+            m = int(arr.shape[0])
+        if n < 2:
+            raise ValueError("a graph needs at least 2 vertices")
+        if m < 1:
+            raise ValueError("a graph needs at least 1 edge")
+        if m >= MAX_EDGES or n >= MAX_VERTICES:
+            raise B.RarcUnsupported(f"EntityGraph(n={n}, {m} edges): the kernels take n < 2^31 - 1 vertices and m < 2^30 edges")
+        if (int(w.sum()) if w is not None else m) >= MAX_TOTAL_WEIGHT:
+            raise B.RarcUnsupported("the total edge weight must stay below 2^31 (every weighted degree then fits 32 bits)")
+        if on_device and not bool(((pairs[:, 0] >= 0) & (pairs[:, 0] < pairs[:, 1]) & (pairs[:, 1] < n)).all().item()):
+            raise ValueError(f"device pairs must satisfy 0 <= i < j < {n}")
+        if not torch.cuda.is_available():
+            raise B.RarcError("no ROCm device visible: the HIP backend has no CPU fallback")
+        self.torch, self.lib = torch, B.load_library()
+        self.n, self.m = n, m
+        self.device = torch.device("cuda", device)
+        with torch.cuda.device(self.device):
+            p = pairs.to(self.device).contiguous() if on_device else torch.from_numpy(np.ascontiguousarray(arr)).to(self.device)
+            wd = None if w is None else torch.from_numpy(w.astype(np.uint32).view(np.int32)).to(self.device)
+            self._graph = torch.empty(int(self.lib.rarc_graph_csr_workspace_bytes(n, m)), dtype=torch.uint8, device=self.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            B.check(self.lib.rarc_graph_csr(p.data_ptr(), wd.data_ptr() if wd is not None else None, None, n, m, self._graph.data_ptr(),
+                                            self._graph.numel(), stream), "rarc_graph_csr")
+            torch.cuda.current_stream(self.device).synchronize()        # (p and wd may be freed: the CSR has its own copy)
+        self._ws = None
+
+    # ---------------------------------------------------------------------------------------------------------------- arguments
+    @staticmethod
+    def _check_run(damping, max_iterations, tolerance, top_k, n):
+        damping, tolerance = float(damping), float(tolerance)
+        if not 0.0 <= damping < 1.0:
+            raise ValueError("damping must lie in [0, 1)")
+        a = int(round(damping * 65536))
+        if a >= 65536:
+            raise ValueError("damping rounds to 1 at 16 bits")
+        if int(max_iterations) < 0:
+            raise ValueError("max_iterations must not be negative")
+        if not 0.0 <= tolerance <= 1.0:
+            raise ValueError("tolerance must lie in [0, 1]")
+        if top_k is not None:
+            if not 1 <= int(top_k) <= MAX_TOP_K:
+                raise ValueError(f"top_k must lie in [1, {MAX_TOP_K}]")
+            if n >= MAX_TOPK_VERTICES:
+                raise B.RarcUnsupported(f"top_k over n={n} vertices: the top-k key carries the vertex in 24 bits, n < 2^24 = "
+                                        f"{MAX_TOPK_VERTICES}; ask for the scores (top_k=None) instead")
+        return a, int(tolerance * ONE)
+
+    def _seed_tensors(self, seeds, seed_weights):
+        """-> (device int64 [B][s], device int32 [B][s] holding the uint32 weights)"""
+        t = self.torch
+        if isinstance(seeds, t.Tensor):
+            if seeds.ndim != 2 or seeds.dtype != t.int64:
+                raise ValueError(f"expected an int64 [B][s] tensor of seeds, got {seeds.dtype} {tuple(seeds.shape)}")
+            nq, s = int(seeds.shape[0]), int(seeds.shape[1])
+            if nq < 1:
+                raise ValueError("no queries")
+            if not 1 <= s <= MAX_SEEDS:
+                raise ValueError(f"{s} seed slots per query: 1 .. {MAX_SEEDS} are taken")
+            sd = seeds.to(self.device).contiguous()
+            if not bool(((sd >= -1) & (sd < self.n)).all().item()):
+                raise ValueError(f"a seed names a vertex outside [0, {self.n})")
+            if seed_weights is None:
+                wd = t.ones((nq, s), dtype=t.int32, device=self.device)
+            elif isinstance(seed_weights, t.Tensor) and not seed_weights.dtype.is_floating_point:
+                wd = seed_weights.to(self.device)
+                if tuple(wd.shape) != (nq, s) or not bool(((wd >= 0) & (wd <= MAX_SEED_WEIGHT)).all().item()):
+                    raise ValueError(f"integer seed weights must be [B][s] in [0, 2^20]")
+                wd = wd.to(t.int32).contiguous()
+            else:
+                wf = t.as_tensor(seed_weights).to(device=self.device, dtype=t.float64)
+                if tuple(wf.shape) != (nq, s) or not bool((t.isfinite(wf) & (wf >= 0)).all().item()):
+                    raise ValueError("seed weights must be [B][s], finite and not negative")
+                mx = wf.max(dim=1, keepdim=True).values
+                wd = t.round(wf / t.where(mx > 0, mx, t.ones_like(mx)) * float(MAX_SEED_WEIGHT)).to(t.int32).contiguous()
+            return sd, wd
+        rows = [list(r) for r in seeds]
+        if not rows:
+            raise ValueError("no queries")
+        s = max(1, max(len(r) for r in rows))
+        if s > MAX_SEEDS:
+            raise ValueError(f"{s} seeds in a query: at most {MAX_SEEDS} are taken")
+        sd = np.full((len(rows), s), -1, np.int64)
+        wf = np.zeros((len(rows), s), np.float64)
+        for i, r in enumerate(rows):
+            v = np.asarray(r)
+            if v.size and (not np.all(v == np.floor(v)) or v.min() < 0 or v.max() >= self.n):
+                raise ValueError(f"a seed names a vertex outside [0, {self.n})")
+            sd[i, :len(r)] = v
+            if seed_weights is None:
+                wf[i, :len(r)] = 1.0
+            else:
+                w = np.asarray(seed_weights[i], dtype=np.float64)
+                if w.shape != (len(r),):
+                    raise ValueError(f"query {i}: {len(r)} seeds and weights of shape {w.shape}")
+                if not np.all(np.isfinite(w)) or np.any(w < 0):
+                    raise ValueError("seed weights must be finite and not negative")
+                wf[i, :len(r)] = w
+        wq = quantise_seed_weights(wf)
+        return t.from_numpy(sd).to(self.device), t.from_numpy(wq.view(np.int32)).to(self.device)
+
+    # ---------------------------------------------------------------------------------------------------------------- the run
+    def _run(self, sd, wd, a: int, tol: int, max_iterations: int, top_k):
+        """one launch batch (<= 256 queries) -> device tensors: scores [B][n], or (ids, scores, counts)"""
+        t, lib, n, m = self.torch, self.lib, self.n, self.m
+        nq, s = int(sd.shape[0]), int(sd.shape[1])
+        need = int(lib.rarc_ppr_workspace_bytes(n, m, nq))
+        if need == 0:
+            raise B.RarcError(f"personalized_pagerank: n={n}, m={m}, {nq} queries refused by rarc_ppr_workspace_bytes")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = t.empty(need, dtype=t.uint8, device=self.device)
+        g, gb, ws, wb = self._graph.data_ptr(), self._graph.numel(), self._ws.data_ptr(), self._ws.numel()
+        stream = t.cuda.current_stream(self.device).cuda_stream
+        B.check(lib.rarc_ppr_seed(g, gb, n, m, sd.data_ptr(), wd.data_ptr(), nq, s, ws, wb, stream), "rarc_ppr_seed")
+        done = t.zeros(nq, dtype=t.int32, device=self.device) if tol > 0 else None
+        cur = 0
+        for _ in range(max_iterations):
+            B.check(lib.rarc_ppr_step(g, gb, n, m, nq, a, tol, cur, ws, wb, done.data_ptr() if done is not None else None, stream),
+                    "rarc_ppr_step")
+            cur ^= 1
+            if done is not None and bool(done.all().item()):        # B words per iteration, only under a tolerance
+                break
+        if top_k is None:
+            out = t.empty((nq, n), dtype=t.float64, device=self.device)
+            B.check(lib.rarc_ppr_scores(n, m, nq, ws, wb, out.data_ptr(), stream), "rarc_ppr_scores")
+            return out
+        ids = t.empty((nq, top_k), dtype=t.int64, device=self.device)
+        sc = t.empty((nq, top_k), dtype=t.float64, device=self.device)
+        cnt = t.empty(nq, dtype=t.int32, device=self.device)
+        B.check(lib.rarc_ppr_topk(n, m, nq, top_k, cur, ws, wb, ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(), stream), "rarc_ppr_topk")
+        return ids, sc, cnt
+
+    def _ranked(self, sd, wd, a, tol, max_iterations, top_k, as_device):
+        t = self.torch
+        parts = [self._run(sd[s0:s0 + MAX_BATCH], wd[s0:s0 + MAX_BATCH], a, tol, int(max_iterations), top_k)
+                 for s0 in range(0, int(sd.shape[0]), MAX_BATCH)]
+        if top_k is None:
+            out = parts[0] if len(parts) == 1 else t.cat(parts)
+            return out if as_device else out.cpu().numpy()
+        out = parts[0] if len(parts) == 1 else tuple(t.cat([p[i] for p in parts]) for i in range(3))
+        return out if as_device else tuple(x.cpu().numpy() for x in out)
+
+    def personalized_pagerank(self, seeds, seed_weights=None, damping: float = 0.85, max_iterations: int = 20, tolerance: float = 0.0,
+                              top_k=None, as_device: bool = False):
+        """Personalized PageRank from each query's seeds.
+        seeds: a list of lists of vertices, or a device int64 [B][s] tensor padded with -1; at most 64 per query, a vertex may
+        repeat.  seed_weights: per seed, floats >= 0 (each query scaled so its largest is 1, then round(w * 2^20)); unit by
+        default; a query whose weights are all zero scores 0 everywhere.
+        tolerance: a query whose largest change in a step is <= tolerance stops there, on its own; 0 runs max_iterations steps.
+        -> float64 [B][n] scores (p / 2^40, exact), or with top_k (ids int64 [B][k], scores float64 [B][k], counts int32 [B]):
+        the vertices of positive score by (score descending, vertex ascending), (-1, -inf) past the count.
+        as_device=True leaves the results on the GPU.  ValueError for a negative or non-finite weight, a vertex outside [0, n)
+        or more than 64 seeds."""
+        a, tol = self._check_run(damping, max_iterations, tolerance, top_k, self.n)
+        with self.torch.cuda.device(self.device):
+            sd, wd = self._seed_tensors(seeds, seed_weights)
+            return self._ranked(sd, wd, a, tol, max_iterations, None if top_k is None else int(top_k), as_device)
+
+    def retrieve(self, index, queries, seeds_per_query: int = 5, top_k: int = 10, damping: float = 0.85, max_iterations: int = 20,
+                 tolerance: float = 0.0, as_device: bool = False):
+        """Graph retrieval for embedded queries: row i of `index` (a FlatIndexF16) is the embedding of vertex i; each query's
+        seeds are the index's own top-`seeds_per_query` (id, score) answer, the scores clipped at 0 as weights, taken on the
+        device — the answer feeds rarc_ppr_seed directly, nothing leaves HBM between the search and the ranking.
+        -> (ids, scores, counts) as personalized_pagerank(top_k=top_k)."""
+        t = self.torch
+        if int(index.ntotal) != self.n:
+            raise ValueError(f"the index holds {int(index.ntotal)} rows and the graph {self.n} vertices: row i must be vertex i")
+        if not 1 <= int(seeds_per_query) <= MAX_SEEDS:
+            raise ValueError(f"seeds_per_query must lie in [1, {MAX_SEEDS}]")
+        a, tol = self._check_run(damping, max_iterations, tolerance, top_k, self.n)
+        ids, scores = index.search_device(queries, int(seeds_per_query))
+        with t.cuda.device(self.device):
+            ids = ids.to(self.device)
+            w = scores.to(device=self.device, dtype=t.float64)
+            w = t.where((ids >= 0) & (w > 0), w, t.zeros_like(w))          # clipped at 0; a slot past ntotal carries nothing
+            mx = w.max(dim=1, keepdim=True).values
+            wd = t.round(w / t.where(mx > 0, mx, t.ones_like(mx)) * float(MAX_SEED_WEIGHT)).to(t.int32).contiguous()
+            return self._ranked(ids.contiguous(), wd, a, tol, max_iterations, int(top_k), as_device)
+
+
+def personalized_pagerank(n: int, pairs, seeds, weights=None, device: int = 0, **kw):
+    """The one-shot form: EntityGraph(n, pairs, weights, device).personalized_pagerank(seeds, **kw)."""
+    return EntityGraph(n, pairs, weights=weights, device=device).personalized_pagerank(seeds, **kw)
