@@ -907,6 +907,40 @@ int rarc_ppr_topk(int64_t n, int64_t m, int nq, int top_k, int cur, void* d_ws, 
 int rarc_ppr_limits(int* out6);
 
 /*
+ * Passage retrieval from the PPR state: the mass of the entities pushed through the mention links (chunk)-[:MENTIONS]->(entity)
+ * onto the chunks, and the chunks ranked — how a PPR-based graph retriever (HippoRAG's, upstream RAG-ARC's) ends.  The rule
+ * continues the one above (restated by tests/passage_ref.py): a mention map is a set of triples (c, e, w),
+ * 0 <= c < n_chunks, 0 <= e < n, w an integer in [1, 2^12), every (c, e) once, given as a CSR by chunk: d_row_ptr int64
+ * [n_chunks + 1], d_ent int32 [nnz], d_w uint32 [nnz].  With p_q the state of query q,
+ *   S_q(c) = (sum over c's mentions (e, w) of w * p_q(e)) >> 12 < 2^40,   score = S / 2^28 (exact)
+ * — integer sums: the same bits for any order of the mentions, either form of the kernel and any batch.
+ * Limits: n, m, nq as above, 1 <= n_chunks < 2^31 - 1, nnz >= 1, d_ws and d_cws 256-byte aligned, every array aligned to its
+ * element; refused before any launch.  The host entry cannot read the device arrays, so the kernel guards itself: a chunk's
+ * range [row_ptr[c], row_ptr[c + 1]) is clamped to [0, nnz], an entry with e outside [0, n) or w outside [1, 2^12)
+ * contributes nothing, a listed chunk outside [0, n_chunks) is skipped — no index leaves its buffer, whatever they hold.
+ * d_cws: rarc_ppr_chunks_workspace_bytes(n_chunks, nq) bytes (0 for a refused shape): S, the top-k keys and the counts.
+ *
+ * rarc_ppr_chunks — reads p of the PPR workspace d_ws (`cur` as rarc_ppr_step would get it next; the workspace is only read,
+ *   so stepping may go on) and writes S as int64 [n_chunks][nq], chunk-major, into d_cws.  d_split int32 [n_split]: the chunks
+ *   of more than 64 mentions (rarc_ppr_chunks_limits), each split across the waves of a workgroup; may be null when n_split = 0.
+ *   A chunk of more than 64 mentions that the list omits scores 0.  Two forms by nq, as rarc_ppr_step.
+ * rarc_ppr_chunks_scores — d_out_scores double [nq][n_chunks] = S / 2^28.
+ * rarc_ppr_chunks_topk — per query the top_k (1 .. 8192) chunks of positive score by (score descending, chunk ascending):
+ *   ids int64 [nq][top_k], scores double [nq][top_k], count int32 [nq]; (-1, -inf) past the count.  n_chunks >= 2^24 returns
+ *   RARC_E_UNSUPPORTED (the key carries the chunk in 24 bits; rarc_ppr_chunks_scores has no such limit).
+ * rarc_ppr_chunks_limits — out4 = {most mentions a single wave walks (a chunk of more is split), bits of a mention weight,
+ *   the shift of a score (S / 2^28), bits of a chunk in the top-k key}.
+ */
+size_t rarc_ppr_chunks_workspace_bytes(int64_t n_chunks, int nq);
+int rarc_ppr_chunks(int64_t n, int64_t m, int nq, int cur, const void* d_ws, size_t ws_bytes, const int64_t* d_row_ptr,
+                    const int32_t* d_ent, const uint32_t* d_w, int64_t n_chunks, int64_t nnz, const int32_t* d_split, int64_t n_split,
+                    void* d_cws, size_t cws_bytes, void* stream);
+int rarc_ppr_chunks_scores(int64_t n_chunks, int nq, const void* d_cws, size_t cws_bytes, double* d_out_scores, void* stream);
+int rarc_ppr_chunks_topk(int64_t n_chunks, int nq, int top_k, void* d_cws, size_t cws_bytes, int64_t* d_out_ids, double* d_out_scores,
+                         int32_t* d_out_count, void* stream);
+int rarc_ppr_chunks_limits(int* out4);
+
+/*
  * Deleting rows of a resident index: stable in-place compaction.  The reference deletes by clearing the index and
  * embedding every surviving text again (encapsulation/database/vector_db/VectorStore_Faiss.py:374-415); the surviving
  * rows are in HBM already, so here they move down over the holes: row i of the result is the i-th surviving row.

@@ -1,7 +1,7 @@
 """Counterpart of the reference's config/app_registration.py:1-5: the registry singleton plus a
 helper that registers this backend's retriever stacks under the framework's own mechanism."""
 from ..framework.register import Register
-from .modules import (HipLogitRerankerConfig, HipQwen3EmbeddingsConfig, HipQwen3RerankerConfig,
+from .modules import (HipGraphRetrieverConfig, HipLogitRerankerConfig, HipQwen3EmbeddingsConfig, HipQwen3RerankerConfig,
                       HipShardedFlatVectorStoreConfig, MultiPathRetrieverConfig, VectorStoreRetrieverConfig)
 
 registrator = Register()
@@ -18,6 +18,10 @@ def register_sharded_vectorstore(config_path: str, app_name: str = "hip_sharded_
 
 def register_multipath_retriever(config_path: str, app_name: str = "hip_multipath_retriever") -> None:
     registrator.register(config_path, app_name, MultiPathRetrieverConfig)
+
+
+def register_graph_retriever(config_path: str, app_name: str = "hip_graph_retriever") -> None:
+    registrator.register(config_path, app_name, HipGraphRetrieverConfig)
 
 
 def register_reranker(config_path: str, app_name: str = "hip_reranker") -> None:

@@ -8,7 +8,9 @@ JSON -> <Config>(**data).build() -> module graph, e.g.
                      "vectorstore": {"type": "hip_flat_vectorstore", "metric": "cosine",
                                      "embedding": {"type": "table_embeddings", "path": "emb.npz"},
                                      "corpus_path": "corpus.npz"}},
-                    {"type": "hip_bm25_retriever", "corpus_path": "corpus.npz", "k1": 1.5, "b": 0.75}]}
+                    {"type": "hip_bm25_retriever", "corpus_path": "corpus.npz", "k1": 1.5, "b": 0.75},
+                    {"type": "hip_graph_retriever", "graph_path": "graph.npz",
+                     "embedding": {"type": "table_embeddings", "path": "emb.npz"}}]}
 """
 from dataclasses import dataclass, field
 from typing import ClassVar, Annotated, Any, Dict, List, Literal, Optional, Union
@@ -296,6 +298,41 @@ class HipBM25RetrieverConfig(AbstractConfig):
         return BuiltModule(config=self, impl=retriever)
 
 
+class HipGraphRetrieverConfig(AbstractConfig):
+    """The graph arm of hybrid retrieval (core/retrieval/graph.py): the query's nearest entities seed a personalized PageRank
+    over the entity graph, and its mass is pushed through the mention links onto the chunks.
+    `graph_path`: .npz with `pairs` int [m][2] (and optional `pair_weights`), `mentions` int [nnz][2] of (chunk, entity) (and
+    optional `mention_weights`), `entity_embeddings` float32 [n][d] (row i = vertex i), `texts` (chunk i = text i; optional
+    `ids`).  `embedding`: the provider that embeds the queries, in the space of `entity_embeddings`."""
+    type: Literal["hip_graph_retriever"] = "hip_graph_retriever"
+    graph_path: str
+    embedding: EmbeddingsConfig
+    metric: Literal["cosine", "ip"] = "cosine"
+    k: int = 5
+    seeds_per_query: int = 5
+    damping: float = 0.85
+    max_iterations: int = 20
+    tolerance: float = 0.0
+    device: int = 0
+
+    def build(self) -> AbstractModule:
+        import numpy as np
+
+        from ..core.retrieval.graph import HipGraphRetriever
+
+        data = np.load(self.graph_path, allow_pickle=False)
+        for name in ("pairs", "mentions", "entity_embeddings", "texts"):
+            if name not in data:
+                raise ValueError(f"hip_graph_retriever: {self.graph_path} has no `{name}`")
+        retriever = HipGraphRetriever.from_arrays(
+            self.embedding.build().impl, data["entity_embeddings"], data["pairs"], data["mentions"], [str(t) for t in data["texts"]],
+            pair_weights=data["pair_weights"] if "pair_weights" in data else None,
+            mention_weights=data["mention_weights"] if "mention_weights" in data else None,
+            ids=[str(i) for i in data["ids"]] if "ids" in data else None, metric=self.metric, device=self.device, k=self.k,
+            seeds_per_query=self.seeds_per_query, damping=self.damping, max_iterations=self.max_iterations, tolerance=self.tolerance)
+        return BuiltModule(config=self, impl=retriever)
+
+
 class HipLogitRerankerConfig(AbstractConfig):
     """The yes/no-logit reranker as a registered module (core/rerank/Reranker_Qwen3.py:6-75).  The score -> order
     step runs in the rarc_rerank_order kernel; the (no, yes) logits come from `logits_path`, an .npz table of
@@ -426,7 +463,8 @@ class RRFusionConfig(AbstractConfig):
 
 class MultiPathRetrieverConfig(AbstractConfig):
     type: Literal["multipath_retriever"] = "multipath_retriever"
-    retrievers: List[Annotated[Union[VectorStoreRetrieverConfig, HipBM25RetrieverConfig], Field(discriminator="type")]]
+    retrievers: List[Annotated[Union[VectorStoreRetrieverConfig, HipBM25RetrieverConfig, HipGraphRetrieverConfig],
+                                     Field(discriminator="type")]]
     fusion: RRFusionConfig = Field(default_factory=RRFusionConfig)
     top_k_per_retriever: int = 50
 

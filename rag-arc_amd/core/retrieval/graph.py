@@ -1,0 +1,121 @@
+"""Graph retriever on the MI355X: the third arm of hybrid retrieval beside the dense and the lexical one.
+
+A query is embedded, linked to the entities nearest to it (a `FlatIndexF16` over the entity embeddings, row i = vertex i),
+personalized PageRank spreads from those seeds over the entity graph, and the mass of the entities is pushed through the
+(chunk)-[:MENTIONS]->(entity) links onto the chunks — the way HippoRAG's and upstream RAG-ARC's graph retrievers end.  The
+search, the PageRank, the projection and the top-k all run in librarc_hip.so without leaving HBM
+(`EntityGraph.retrieve_chunks`); what comes back to the host is k (chunk, score) pairs per query.
+
+Each returned Document is a copy of the stored chunk with a `score` attribute (the exact fixed-point score S / 2^28), which is
+what `MultiPathRetriever` reads with getattr(d, "score", 1.0).  No CPU fallback: without a device the constructor raises."""
+import dataclasses
+import uuid
+from typing import Any, Dict, Iterable, List, Optional
+
+import numpy as np
+
+from ..utils.data_model import Document
+from .base import BaseRetriever
+
+
+class HipGraphRetriever(BaseRetriever):
+    def __init__(self, embedding, index, graph, mentions, docs: List[Document], k: int = 5, seeds_per_query: int = 5,
+                 damping: float = 0.85, max_iterations: int = 20, tolerance: float = 0.0, **kwargs):
+        super().__init__(**kwargs)
+        self._validate_k(k)
+        docs = list(docs)
+        if int(index.ntotal) != graph.n:
+            raise ValueError(f"the index holds {int(index.ntotal)} rows and the graph {graph.n} vertices: row i must be vertex i")
+        if mentions.n_entities != graph.n:
+            raise ValueError(f"the mention map is over {mentions.n_entities} entities and the graph has {graph.n} vertices")
+        if mentions.n_chunks != len(docs):
+            raise ValueError(f"the mention map is over {mentions.n_chunks} chunks and {len(docs)} documents were given: chunk i must be "
+                             f"document i")
+        graph._check_run(damping, max_iterations, tolerance, None, graph.n)      # the refusals of retrieve_chunks, up front
+        graph._check_index(index, seeds_per_query)
+        self.embedding, self.index, self.graph, self.mentions, self.docs = embedding, index, graph, mentions, docs
+        self.k = k
+        self.seeds_per_query, self.damping = int(seeds_per_query), float(damping)
+        self.max_iterations, self.tolerance = int(max_iterations), float(tolerance)
+
+    @staticmethod
+    def _validate_k(k) -> None:
+        if isinstance(k, bool) or not isinstance(k, int) or k <= 0:
+            raise ValueError(f"k must be > 0, got {k!r}")
+
+    @classmethod
+    def from_arrays(cls, embedding, entity_embeddings, pairs, mentions, texts: Iterable[str], pair_weights=None, mention_weights=None,
+                    ids: Optional[Iterable[str]] = None, metadatas: Optional[Iterable[Dict[str, Any]]] = None, metric: str = "cosine",
+                    device: int = 0, **kwargs: Any) -> "HipGraphRetriever":
+        """entity_embeddings: float32 [n][d], row i = vertex i; pairs / pair_weights: the entity graph's edges (EntityGraph);
+        mentions / mention_weights: (chunk, entity) links (MentionMap); texts (and ids, metadatas): the chunks, chunk i = text i."""
+        from ...encapsulation.database.graph_db import EntityGraph, MentionMap
+        from ...hip.engine import FlatIndexF16
+
+        texts = [str(t) for t in texts]
+        if not texts:
+            raise ValueError("texts must not be empty")
+        metadatas = list(metadatas) if metadatas is not None else [{} for _ in texts]
+        ids = [str(i) for i in ids] if ids is not None else [str(uuid.uuid4()) for _ in texts]
+        if len(metadatas) != len(texts) or len(ids) != len(texts):
+            raise ValueError(f"{len(texts)} texts, {len(metadatas)} metadatas, {len(ids)} ids")
+        cls._validate_k(kwargs.get("k", 5))
+        x = np.ascontiguousarray(entity_embeddings, dtype=np.float32)
+        if x.ndim != 2 or x.shape[0] < 2:
+            raise ValueError(f"expected [n][d] entity embeddings with n >= 2, got an array of shape {x.shape}")
+        n = int(x.shape[0])
+        graph = EntityGraph(n, pairs, weights=pair_weights, device=device)          # (refusals first: the graph and the map
+        mention_map = MentionMap(len(texts), n, mentions, weights=mention_weights, device=device)   # check before anything is stored)
+        index = FlatIndexF16(int(x.shape[1]), metric=metric, device=device)
+        index.add(x)
+        docs = [Document(content=t, metadata=m, id=i) for t, m, i in zip(texts, metadatas, ids)]
+        return cls(embedding, index, graph, mention_map, docs, **kwargs)
+
+    # -- queries ----------------------------------------------------------------------------------------------------------
+    def _embed(self, texts: List[str]):
+        """one embedding batch: on the device where the provider can, else one host array"""
+        emb = self.embedding
+        for name in ("embed_queries_device", "embed_queries"):
+            batched = getattr(emb, name, None)
+            if batched is not None:
+                return batched(texts)
+        return np.asarray([emb.embed_query(t) for t in texts], dtype=np.float32)
+
+    def _get_relevant_documents(self, query: str, **kwargs: Any) -> List[Document]:
+        return self.batch_invoke([query], **kwargs)[0]
+
+    def batch_invoke(self, inputs: List[str], **kwargs: Any) -> List[List[Document]]:
+        """invoke() for a list of queries: one embedding batch, one search and one PageRank run per 256 queries.  Element i
+        equals invoke(inputs[i], **kwargs) — every query is ranked on its own, by integer arithmetic."""
+        inputs = list(inputs)
+        k = kwargs.get("k", self.k)
+        self._validate_k(k)
+        if not inputs:
+            return []
+        ids, scores, counts = self.graph.retrieve_chunks(self.index, self._embed(inputs), self.mentions, seeds_per_query=self.seeds_per_query,
+                                                         top_k=min(k, len(self.docs)), damping=self.damping,
+                                                         max_iterations=self.max_iterations, tolerance=self.tolerance)
+        out: List[List[Document]] = []
+        for q in range(len(inputs)):
+            answer = []
+            for c, s in zip(ids[q, :counts[q]].tolist(), scores[q, :counts[q]].tolist()):
+                doc = dataclasses.replace(self.docs[c])
+                doc.score = s
+                answer.append(doc)
+            out.append(answer)
+        return out
+
+    # -- information --------------------------------------------------------------------------------------------------------
+    def update_k(self, new_k: int) -> None:
+        self._validate_k(new_k)
+        self.k = new_k
+
+    def get_document_count(self) -> int:
+        return len(self.docs)
+
+    def get_name(self) -> str:
+        return "HipGraphRetriever"
+
+    def __repr__(self) -> str:
+        return (f"{self.__class__.__name__}(entities={self.graph.n}, edges={self.graph.m}, chunks={len(self.docs)}, "
+                f"mentions={self.mentions.nnz}, k={self.k}, seeds_per_query={self.seeds_per_query})")

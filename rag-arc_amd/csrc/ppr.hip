@@ -32,6 +32,9 @@
 // and in both a vertex of more than LV_DEG_WAVE = 64 neighbours (the degree lists 2 and 3 of the blob) is split across the four
 // waves of a workgroup, which are joined by integer adds in LDS: each wave writes 64 (or 128) consecutive 8-byte words, wave 0
 // reads them back the same way — consecutive lanes on consecutive bank pairs, no conflict.
+//
+// The last section projects the state through a mention map onto chunks (rarc_ppr_chunks*): its rule, its
+// bounds and its guards are stated there.
 #include "graph_csr.h"
 #include "canon_topk.h"
 
@@ -272,8 +275,9 @@ __global__ __launch_bounds__(256) void ppr_mark_kernel(int B, const u64* __restr
 // pairs).  KEYS: (p << 24) | (~v & 0xFFFFFF) where p > 0, else 0 — below every real key — and the positives counted per query;
 // otherwise p / 2^40 as float64, exact because p <= 2^40 < 2^53.  A vertex that holds ALL the mass (p = 2^40: one seed and
 // damping 0, or an isolated seed) is keyed as 2^40 - 1: every other vertex of the query then holds 0, the order stands, and the
-// score of an answer is read from p, not from its key
-template <bool KEYS>
+// score of an answer is read from p, not from its key.  SHIFT: the score is x / 2^SHIFT (40 for the vertices; the chunks of
+// the passage projection below are transposed, keyed and ranked by the same kernels over their state S, at 28)
+template <bool KEYS, int SHIFT = PPR_ONE_SHIFT>
 __global__ __launch_bounds__(256) void ppr_transpose_kernel(int64_t n, int B, const u64* __restrict__ p, u64* keys, double* scores,
                                                             uint32_t* positive) {
   __shared__ u64 s_tile[64][65];
@@ -301,7 +305,7 @@ __global__ __launch_bounds__(256) void ppr_transpose_kernel(int64_t n, int B, co
         const u64 mask = __builtin_amdgcn_ballot_w64(pos);
         if (lane == 0 && mask) atomicAdd(&positive[q], (uint32_t)__builtin_popcountll(mask));
       } else if (v < n) {
-        scores[(size_t)q * n + v] = (double)x * 0x1p-40;
+        scores[(size_t)q * n + v] = (double)x * (1.0 / (double)(1ull << SHIFT));
       }
     }
     __syncthreads();
@@ -309,6 +313,7 @@ __global__ __launch_bounds__(256) void ppr_transpose_kernel(int64_t n, int B, co
 }
 
 // one workgroup per query: the min(k, positives) best keys in exact order (canon_topk.h), (-1, -inf) behind them
+template <int SHIFT>
 __global__ __launch_bounds__(1024) void ppr_topk_kernel(const u64* __restrict__ keys_all, uint32_t n, int B, uint32_t k,
                                                         const uint32_t* __restrict__ positive, const u64* __restrict__ p,
                                                         int64_t* out_ids, double* out_scores, int32_t* out_count) {
@@ -328,7 +333,7 @@ __global__ __launch_bounds__(1024) void ppr_topk_kernel(const u64* __restrict__ 
     const bool real = i < kk;
     const uint32_t v = real ? ~(uint32_t)s_top[i] & 0xFFFFFFu : 0u;
     out_ids[(size_t)q * k + i] = real ? (int64_t)v : -1;
-    out_scores[(size_t)q * k + i] = real && v < n ? (double)p[(size_t)v * B + q] * 0x1p-40 : -(double)INFINITY;
+    out_scores[(size_t)q * k + i] = real && v < n ? (double)p[(size_t)v * B + q] * (1.0 / (double)(1ull << SHIFT)) : -(double)INFINITY;
   }
   if (threadIdx.x == 0) out_count[q] = (int32_t)kk;
 }
@@ -461,7 +466,7 @@ extern "C" int rarc_ppr_topk(int64_t n, int64_t m, int nq, int top_k, int cur, v
   hipStream_t s = (hipStream_t)stream;
   static RarcPerDevice attr_done;
   if (size_t& done = attr_done.cur(); !done) {
-    RARC_HIP_CHECK(hipFuncSetAttribute((const void*)ppr_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+    RARC_HIP_CHECK(hipFuncSetAttribute((const void*)ppr_topk_kernel<PPR_ONE_SHIFT>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
     done = 1;
   }
   u64* keys = ws.c[cur ^ 1];                               // the slot the next step overwrites anyway: [B][n] keys
@@ -472,8 +477,264 @@ extern "C" int rarc_ppr_topk(int64_t n, int64_t m, int nq, int top_k, int cur, v
   const uint32_t kmax = (uint32_t)((int64_t)top_k < n ? (int64_t)top_k : n);
   uint32_t pow2 = 1;
   while (pow2 < kmax) pow2 <<= 1;
-  hipLaunchKernelGGL(ppr_topk_kernel, dim3(nq), dim3(1024), (size_t)pow2 * 8, s, (const u64*)keys, (uint32_t)n, nq, (uint32_t)top_k,
+  hipLaunchKernelGGL(ppr_topk_kernel<PPR_ONE_SHIFT>, dim3(nq), dim3(1024), (size_t)pow2 * 8, s, (const u64*)keys, (uint32_t)n, nq, (uint32_t)top_k,
                      (const uint32_t*)ws.positive, (const u64*)ws.p, d_out_ids, d_out_scores, d_out_count);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+// ---- passages: the PPR mass of the entities pushed through the mention links onto the chunks ---------------------
+// What a PPR-based graph retriever returns is chunks, not entities (the reference stores the link: (chunk)-[:MENTIONS]->(entity)).
+// The rule continues the one above (tests/passage_ref.py restates it in Python integers): a mention map is a set of triples
+// (c, e, w), 0 <= c < n_chunks, 0 <= e < n, w an integer in [1, 2^12), every (c, e) once, held as a CSR by chunk, and
+//   S_q(c) = (sum over c's mentions (e, w) of w * p_q(e)) >> 12,   score = S / 2^28  ( = sum w p / ONE floored to 2^-28, exact)
+// Nothing overflows: sum_e p_q(e) <= ONE = 2^40 and every (c, e) appears once, so sum w p <= (2^12 - 1) ONE < 2^52, and
+// S < 2^40 strictly: the top-k key (S << 24) | (~c & 0xFFFFFF) needs no "all the mass" case.  Integer sums: the same bits for
+// any order of the mentions, either form of the kernel and any batch; a frozen query is projected like any other.
+//
+// The kernel is the step's sibling, not an instantiation of it: the same two forms (chunk-parallel up to 32 queries, a lane a
+// query beyond, two queries and one 16-byte load per lane for even B > 64), four loads in flight, a chunk of more than
+// PPR_CHUNK_SPLIT_DEGREE mentions split across the four waves of a workgroup and joined in LDS — but none of the step's
+// delta / done / teleport work, and guards the step does not need, because the CSR comes from the caller and no host entry can
+// read it: a chunk's range is clamped to [0, nnz], an entry with e outside [0, n) or w outside [1, 2^12) contributes nothing
+// (its row of p is not read), and a listed chunk outside [0, n_chunks) is skipped.  Whatever the arrays hold, no index leaves
+// its buffer.  The chunks of more than PPR_CHUNK_SPLIT_DEGREE mentions are listed by the host while it builds the CSR; one that
+// the list omits scores 0 (the first launch writes that, the second overwrites it for the listed ones).
+//
+// The chunk workspace is {positive counts u32 [256]} | S u64 [n_chunks][B] | keys u64 [B][n_chunks]: the PPR workspace is only
+// read, so stepping — and rarc_ppr_topk — may go on afterwards.
+constexpr int PPR_CHUNK_SPLIT_DEGREE = LV_DEG_WAVE;
+constexpr int PPR_CHUNK_WEIGHT_BITS = 12;
+constexpr int PPR_CHUNK_SCORE_SHIFT = PPR_ONE_SHIFT - PPR_CHUNK_WEIGHT_BITS;
+constexpr int64_t PPR_CHUNK_N_LIMIT = LV_N_LIMIT;             // n_chunks < 2^31 - 1: a chunk id is an int32 in the split list
+constexpr size_t PPR_CHUNK_CTL_BYTES = 1024;                // positive u32 [256]
+
+struct PprChunkWs {
+  uint32_t* positive;
+  u64* s;
+  u64* keys;
+  size_t bytes;
+};
+static inline bool ppr_chunk_shape_ok(int64_t n_chunks, int nq) { return n_chunks >= 1 && n_chunks < PPR_CHUNK_N_LIMIT && nq >= 1 && nq <= PPR_MAX_B; }
+static PprChunkWs ppr_chunk_carve(const void* base, int64_t n_chunks, int nq) {
+  char* b = (char*)base;
+  size_t o = 0;
+  PprChunkWs w;
+  auto take = [&](size_t bytes) { char* p = b + o; o += lv_align(bytes); return p; };
+  w.positive = (uint32_t*)take(PPR_CHUNK_CTL_BYTES);
+  const size_t state = (size_t)n_chunks * (size_t)nq * 8;
+  w.s = (u64*)take(state);
+  w.keys = (u64*)take(state);
+  w.bytes = o;
+  return w;
+}
+
+struct PprChunkArgs {
+  const int64_t* row_ptr;
+  const int32_t* ent;
+  const uint32_t* w;
+  const u64* p;
+  u64* s;
+  int64_t n;
+  int64_t n_chunks;
+  int64_t nnz;
+  int B;
+};
+
+// one mention: the weight that counts (0 for an entry outside the rule) and the row of p it reads (row 0 when it counts for nothing)
+__device__ __forceinline__ void ppr_chunk_entry(int32_t e, uint32_t w, int64_t n, size_t& row, u64& weight) {
+  const bool ok = e >= 0 && (int64_t)e < n && w >= 1u && w < (1u << PPR_CHUNK_WEIGHT_BITS);
+  row = ok ? (size_t)e : 0;
+  weight = ok ? (u64)w : 0;
+}
+
+// BP, QPL, SPLIT as in ppr_step_kernel; list: the chunks of more than PPR_CHUNK_SPLIT_DEGREE mentions, list_count of them
+template <int BP, int QPL, bool SPLIT>
+__global__ __launch_bounds__(256) void ppr_chunks_kernel(const PprChunkArgs a, const int32_t* __restrict__ list, int64_t list_count) {
+  constexpr int NSLOT = 64 / BP;
+  constexpr int STEP = SPLIT ? 4 * NSLOT : NSLOT;
+  __shared__ u64 s_part[SPLIT ? 4 * BP * QPL : 1];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int slot = lane / BP, ql = lane % BP;
+  const int B = a.B;
+  const int chunks = (B + BP * QPL - 1) / (BP * QPL);
+  const int64_t items = (SPLIT ? list_count : a.n_chunks) * chunks;
+  const int64_t first = SPLIT ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + wave;
+  const int64_t stride = SPLIT ? (int64_t)gridDim.x : (int64_t)gridDim.x * 4;
+  for (int64_t item = first; item < items; item += stride) {
+    const int64_t ci = item / chunks;
+    const int chunk = (int)(item - ci * chunks);
+    const int64_t c = SPLIT ? (int64_t)list[ci] : ci;
+    if (SPLIT && (c < 0 || c >= a.n_chunks)) continue;                 // (workgroup-uniform: every thread reads the same entry)
+    int64_t r0 = a.row_ptr[c], r1 = a.row_ptr[c + 1];
+    r0 = r0 < 0 ? 0 : (r0 > a.nnz ? a.nnz : r0);
+    r1 = r1 < r0 ? r0 : (r1 > a.nnz ? a.nnz : r1);
+    const int64_t deg = r1 - r0;
+    const int q = chunk * BP * QPL + ql * QPL;                         // this lane's first query; q + QPL <= B or q >= B
+    const bool in_b = q < B;
+    u64 acc[QPL];
+#pragma unroll
+    for (int i = 0; i < QPL; ++i) acc[i] = 0;
+    if (in_b && (SPLIT || deg <= PPR_CHUNK_SPLIT_DEGREE)) {            // (a lane past the batch reads no row of p)
+      int64_t e = (SPLIT ? wave * NSLOT : 0) + slot;
+      for (; e + 3 * STEP < deg; e += 4 * STEP) {                      // four mentions in flight
+        size_t row[4];
+        u64 w[4];
+        u64 x[4][QPL];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ppr_chunk_entry(a.ent[r0 + e + j * STEP], a.w[r0 + e + j * STEP], a.n, row[j], w[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ppr_load<QPL>(a.p + row[j] * B + q, x[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int i = 0; i < QPL; ++i) acc[i] += w[j] * x[j][i];
+      }
+      for (; e < deg; e += STEP) {
+        size_t row;
+        u64 w;
+        ppr_chunk_entry(a.ent[r0 + e], a.w[r0 + e], a.n, row, w);
+        u64 x[QPL];
+        ppr_load<QPL>(a.p + row * B + q, x);
+#pragma unroll
+        for (int i = 0; i < QPL; ++i) acc[i] += w * x[i];
+      }
+    }
+    // the slots of a wave: integer shuffle-adds (every lane takes part, an idle one with zeros)
+#pragma unroll
+    for (int i = 0; i < QPL; ++i)
+#pragma unroll
+      for (int d = BP; d < 64; d <<= 1) acc[i] += (u64)__shfl_xor((long long)acc[i], d, 64);
+    if (SPLIT) {                                                       // the waves of the workgroup: integer adds in LDS
+      if (slot == 0) {
+#pragma unroll
+        for (int i = 0; i < QPL; ++i) s_part[(wave * BP + ql) * QPL + i] = acc[i];
+      }
+      __syncthreads();
+      if (wave == 0 && slot == 0) {
+#pragma unroll
+        for (int i = 0; i < QPL; ++i)
+          acc[i] = (s_part[ql * QPL + i] + s_part[(BP + ql) * QPL + i]) + (s_part[(2 * BP + ql) * QPL + i] + s_part[(3 * BP + ql) * QPL + i]);
+      }
+      __syncthreads();
+    }
+    if (slot == 0 && in_b && (!SPLIT || wave == 0)) {                  // (a chunk left to the SPLIT launch: 0 until that overwrites it)
+#pragma unroll
+      for (int i = 0; i < QPL; ++i) a.s[(size_t)c * B + q + i] = acc[i] >> PPR_CHUNK_WEIGHT_BITS;
+    }
+  }
+}
+
+template <int BP, int QPL>
+static void ppr_launch_chunks(const PprChunkArgs& a, const int32_t* d_split, int64_t n_split, hipStream_t s) {
+  const int chunks = (a.B + BP * QPL - 1) / (BP * QPL);
+  hipLaunchKernelGGL((ppr_chunks_kernel<BP, QPL, false>), dim3(lv_grid(a.n_chunks * chunks, 4, 8192)), dim3(256), 0, s, a, (const int32_t*)nullptr,
+                     (int64_t)0);
+  if (n_split > 0)
+    hipLaunchKernelGGL((ppr_chunks_kernel<BP, QPL, true>), dim3(lv_grid(n_split * chunks, 1, 2048)), dim3(256), 0, s, a, d_split, n_split);
+}
+
+extern "C" int rarc_ppr_chunks_limits(int* out4) {
+  RARC_REQUIRE(out4, RARC_E_INVALID, "rarc_ppr_chunks_limits: null pointer");
+  out4[0] = PPR_CHUNK_SPLIT_DEGREE;
+  out4[1] = PPR_CHUNK_WEIGHT_BITS;
+  out4[2] = PPR_CHUNK_SCORE_SHIFT;
+  out4[3] = 24;
+  return RARC_OK;
+}
+
+extern "C" size_t rarc_ppr_chunks_workspace_bytes(int64_t n_chunks, int nq) {
+  if (!ppr_chunk_shape_ok(n_chunks, nq)) return 0;
+  return ppr_chunk_carve(nullptr, n_chunks, nq).bytes;
+}
+
+#define PPR_ALIGNED(P, A) (((uintptr_t)(P) & (uintptr_t)((A)-1)) == 0)
+#define PPR_CHUNK_SHAPE_CHECKS(NAME)                                                                                                     \
+  RARC_REQUIRE(n_chunks >= 1 && n_chunks < PPR_CHUNK_N_LIMIT, RARC_E_INVALID, NAME ": n_chunks=%lld out of range (1 <= n_chunks < 2^31 - 1)", \
+               (long long)n_chunks);                                                                                                     \
+  RARC_REQUIRE(nq >= 1 && nq <= PPR_MAX_B, RARC_E_INVALID, NAME ": %d queries out of range (1 <= B <= %d per call)", nq, PPR_MAX_B);     \
+  RARC_REQUIRE(PPR_ALIGNED(d_cws, 256), RARC_E_INVALID, NAME ": the chunk workspace is not 256-byte aligned");                           \
+  const PprChunkWs cws = ppr_chunk_carve(d_cws, n_chunks, nq);                                                                           \
+  RARC_REQUIRE(cws_bytes >= cws.bytes, RARC_E_WORKSPACE, NAME ": chunk workspace of %zu bytes, %zu needed", cws_bytes, cws.bytes)
+
+extern "C" int rarc_ppr_chunks(int64_t n, int64_t m, int nq, int cur, const void* d_ws, size_t ws_bytes, const int64_t* d_row_ptr,
+                               const int32_t* d_ent, const uint32_t* d_w, int64_t n_chunks, int64_t nnz, const int32_t* d_split,
+                               int64_t n_split, void* d_cws, size_t cws_bytes, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_ws && d_row_ptr && d_ent && d_w && d_cws && (d_split || n_split == 0), RARC_E_INVALID, "rarc_ppr_chunks: null pointer");
+  RARC_REQUIRE(PPR_ALIGNED(d_ws, 256), RARC_E_INVALID, "rarc_ppr_chunks: the PPR workspace is not 256-byte aligned");
+  RARC_REQUIRE(PPR_ALIGNED(d_row_ptr, 8) && PPR_ALIGNED(d_ent, 4) && PPR_ALIGNED(d_w, 4) && PPR_ALIGNED(d_split, 4), RARC_E_INVALID,
+               "rarc_ppr_chunks: a mention array is not aligned to its element (row_ptr 8 bytes, entities, weights and the split list 4)");
+  PPR_SHAPE_CHECKS("rarc_ppr_chunks");
+  PPR_CHUNK_SHAPE_CHECKS("rarc_ppr_chunks");
+  RARC_REQUIRE(nnz >= 1, RARC_E_INVALID, "rarc_ppr_chunks: nnz=%lld mentions out of range (nnz >= 1)", (long long)nnz);
+  RARC_REQUIRE(n_split >= 0 && n_split <= n_chunks, RARC_E_INVALID, "rarc_ppr_chunks: %lld split chunks out of range (0 <= n_split <= n_chunks)",
+               (long long)n_split);
+  RARC_REQUIRE(cur == 0 || cur == 1, RARC_E_INVALID, "rarc_ppr_chunks: slot %d is neither 0 nor 1", cur);
+  hipStream_t s = (hipStream_t)stream;
+  PprChunkArgs a;
+  a.row_ptr = d_row_ptr;
+  a.ent = d_ent;
+  a.w = d_w;
+  a.p = ws.p;                                              // p is written in place by every step: the same array for either `cur`
+  a.s = cws.s;
+  a.n = n;
+  a.n_chunks = n_chunks;
+  a.nnz = nnz;
+  a.B = nq;
+  if (nq > PPR_VERTEX_PARALLEL_MAX_B) {
+    if (nq > 64 && nq % 2 == 0) ppr_launch_chunks<64, 2>(a, d_split, n_split, s);
+    else ppr_launch_chunks<64, 1>(a, d_split, n_split, s);
+  } else if (nq > 16) ppr_launch_chunks<32, 1>(a, d_split, n_split, s);
+  else if (nq > 8) ppr_launch_chunks<16, 1>(a, d_split, n_split, s);
+  else if (nq > 4) ppr_launch_chunks<8, 1>(a, d_split, n_split, s);
+  else if (nq > 2) ppr_launch_chunks<4, 1>(a, d_split, n_split, s);
+  else if (nq > 1) ppr_launch_chunks<2, 1>(a, d_split, n_split, s);
+  else ppr_launch_chunks<1, 1>(a, d_split, n_split, s);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+extern "C" int rarc_ppr_chunks_scores(int64_t n_chunks, int nq, const void* d_cws, size_t cws_bytes, double* d_out_scores, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_cws && d_out_scores, RARC_E_INVALID, "rarc_ppr_chunks_scores: null pointer");
+  RARC_REQUIRE(PPR_ALIGNED(d_out_scores, 8), RARC_E_INVALID, "rarc_ppr_chunks_scores: the scores are not 8-byte aligned");
+  PPR_CHUNK_SHAPE_CHECKS("rarc_ppr_chunks_scores");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t tiles = ((n_chunks + 63) / 64) * ((nq + 63) / 64);
+  hipLaunchKernelGGL((ppr_transpose_kernel<false, PPR_CHUNK_SCORE_SHIFT>), dim3(lv_grid(tiles, 1, 8192)), dim3(256), 0, s, n_chunks, nq,
+                     (const u64*)cws.s, (u64*)nullptr, d_out_scores, (uint32_t*)nullptr);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+extern "C" int rarc_ppr_chunks_topk(int64_t n_chunks, int nq, int top_k, void* d_cws, size_t cws_bytes, int64_t* d_out_ids,
+                                    double* d_out_scores, int32_t* d_out_count, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_cws && d_out_ids && d_out_scores && d_out_count, RARC_E_INVALID, "rarc_ppr_chunks_topk: null pointer");
+  RARC_REQUIRE(PPR_ALIGNED(d_out_ids, 8) && PPR_ALIGNED(d_out_scores, 8) && PPR_ALIGNED(d_out_count, 4), RARC_E_INVALID,
+               "rarc_ppr_chunks_topk: an output is not aligned to its element (ids and scores 8 bytes, counts 4)");
+  RARC_REQUIRE(n_chunks < PPR_TOPK_N_LIMIT, RARC_E_UNSUPPORTED,
+               "rarc_ppr_chunks_topk: n_chunks=%lld: the top-k key carries the chunk in 24 bits, n_chunks < 2^24 = 16777216 "
+               "(rarc_ppr_chunks_scores has no such limit)",
+               (long long)n_chunks);
+  PPR_CHUNK_SHAPE_CHECKS("rarc_ppr_chunks_topk");
+  RARC_REQUIRE(top_k >= 1 && top_k <= PPR_MAX_K, RARC_E_INVALID, "rarc_ppr_chunks_topk: top_k=%d out of range (1 <= k <= %d)", top_k, PPR_MAX_K);
+  hipStream_t s = (hipStream_t)stream;
+  static RarcPerDevice attr_done;
+  if (size_t& done = attr_done.cur(); !done) {
+    RARC_HIP_CHECK(hipFuncSetAttribute((const void*)ppr_topk_kernel<PPR_CHUNK_SCORE_SHIFT>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+    done = 1;
+  }
+  RARC_HIP_CHECK(hipMemsetAsync(cws.positive, 0, (size_t)PPR_MAX_B * 4, s));
+  const int64_t tiles = ((n_chunks + 63) / 64) * ((nq + 63) / 64);
+  hipLaunchKernelGGL((ppr_transpose_kernel<true, PPR_CHUNK_SCORE_SHIFT>), dim3(lv_grid(tiles, 1, 8192)), dim3(256), 0, s, n_chunks, nq,
+                     (const u64*)cws.s, cws.keys, (double*)nullptr, cws.positive);
+  const uint32_t kmax = (uint32_t)((int64_t)top_k < n_chunks ? (int64_t)top_k : n_chunks);
+  uint32_t pow2 = 1;
+  while (pow2 < kmax) pow2 <<= 1;
+  hipLaunchKernelGGL(ppr_topk_kernel<PPR_CHUNK_SCORE_SHIFT>, dim3(nq), dim3(1024), (size_t)pow2 * 8, s, (const u64*)cws.keys, (uint32_t)n_chunks, nq,
+                     (uint32_t)top_k, (const uint32_t*)cws.positive, (const u64*)cws.s, d_out_ids, d_out_scores, d_out_count);
   RARC_HIP_CHECK(hipGetLastError());
   return RARC_OK;
 }

@@ -1,9 +1,11 @@
 """The arithmetic steps of the reference's graph store that sit on the dense hot path's kernels: entity de-duplication by
 all-pairs cosine (encapsulation/database/graph_db/Base_Neo4j.py:538-583) and the Louvain communities of those pairs (:646-658),
 event disambiguation by a k-nearest-neighbour graph (event_graphrag_neo4j.py:600-672), and retrieval from the graph those
-build: personalized PageRank from the entities a query links to.  The graph database itself is out of scope."""
+build: personalized PageRank from the entities a query links to, pushed through the (chunk)-[:MENTIONS]->(entity) links
+(event_graphrag_neo4j.py:508-536) onto the chunks a retriever returns.  The graph database itself is out of scope."""
 from .communities import entity_clusters, louvain_communities
 from .pagerank import EntityGraph, personalized_pagerank
+from .passages import MentionMap
 from .similarity import knn_graph, similar_pairs
 
-__all__ = ["similar_pairs", "knn_graph", "louvain_communities", "entity_clusters", "EntityGraph", "personalized_pagerank"]
+__all__ = ["similar_pairs", "knn_graph", "louvain_communities", "entity_clusters", "EntityGraph", "personalized_pagerank", "MentionMap"]

@@ -201,8 +201,8 @@ class EntityGraph:
         return t.from_numpy(sd).to(self.device), t.from_numpy(wq.view(np.int32)).to(self.device)
 
     # ---------------------------------------------------------------------------------------------------------------- the run
-    def _run(self, sd, wd, a: int, tol: int, max_iterations: int, top_k):
-        """one launch batch (<= 256 queries) -> device tensors: scores [B][n], or (ids, scores, counts)"""
+    def _iterate(self, sd, wd, a: int, tol: int, max_iterations: int) -> int:
+        """seeds one launch batch (<= 256 queries) and runs its steps in the workspace -> `cur`, as the next step would get it"""
         t, lib, n, m = self.torch, self.lib, self.n, self.m
         nq, s = int(sd.shape[0]), int(sd.shape[1])
         need = int(lib.rarc_ppr_workspace_bytes(n, m, nq))
@@ -222,6 +222,18 @@ class EntityGraph:
             cur ^= 1
             if done is not None and bool(done.all().item()):        # B words per iteration, only under a tolerance
                 break
+        return cur
+
+    def _run(self, sd, wd, a: int, tol: int, max_iterations: int, top_k, mentions=None):
+        """one launch batch (<= 256 queries) -> device tensors: scores [B][n], or (ids, scores, counts); with `mentions` (a
+        MentionMap) the same over its chunks: the iterations are shared, only the tail differs"""
+        t, lib, n, m = self.torch, self.lib, self.n, self.m
+        nq = int(sd.shape[0])
+        cur = self._iterate(sd, wd, a, tol, max_iterations)
+        if mentions is not None:
+            return mentions.project(n, m, nq, cur, self._ws, top_k)
+        ws, wb = self._ws.data_ptr(), self._ws.numel()
+        stream = t.cuda.current_stream(self.device).cuda_stream
         if top_k is None:
             out = t.empty((nq, n), dtype=t.float64, device=self.device)
             B.check(lib.rarc_ppr_scores(n, m, nq, ws, wb, out.data_ptr(), stream), "rarc_ppr_scores")
@@ -232,9 +244,10 @@ class EntityGraph:
         B.check(lib.rarc_ppr_topk(n, m, nq, top_k, cur, ws, wb, ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(), stream), "rarc_ppr_topk")
         return ids, sc, cnt
 
-    def _ranked(self, sd, wd, a, tol, max_iterations, top_k, as_device):
+    def _ranked(self, sd, wd, a, tol, max_iterations, top_k, as_device, mentions=None):
         t = self.torch
-        parts = [self._run(sd[s0:s0 + MAX_BATCH], wd[s0:s0 + MAX_BATCH], a, tol, int(max_iterations), top_k)
+        more = {} if mentions is None else {"mentions": mentions}
+        parts = [self._run(sd[s0:s0 + MAX_BATCH], wd[s0:s0 + MAX_BATCH], a, tol, int(max_iterations), top_k, **more)
                  for s0 in range(0, int(sd.shape[0]), MAX_BATCH)]
         if top_k is None:
             out = parts[0] if len(parts) == 1 else t.cat(parts)
@@ -264,12 +277,21 @@ class EntityGraph:
         seeds are the index's own top-`seeds_per_query` (id, score) answer, the scores clipped at 0 as weights, taken on the
         device — the answer feeds rarc_ppr_seed directly, nothing leaves HBM between the search and the ranking.
         -> (ids, scores, counts) as personalized_pagerank(top_k=top_k)."""
-        t = self.torch
+        self._check_index(index, seeds_per_query)
+        a, tol = self._check_run(damping, max_iterations, tolerance, top_k, self.n)
+        sd, wd = self._index_seeds(index, queries, seeds_per_query)
+        with self.torch.cuda.device(self.device):
+            return self._ranked(sd, wd, a, tol, max_iterations, int(top_k), as_device)
+
+    def _check_index(self, index, seeds_per_query):
         if int(index.ntotal) != self.n:
             raise ValueError(f"the index holds {int(index.ntotal)} rows and the graph {self.n} vertices: row i must be vertex i")
         if not 1 <= int(seeds_per_query) <= MAX_SEEDS:
             raise ValueError(f"seeds_per_query must lie in [1, {MAX_SEEDS}]")
-        a, tol = self._check_run(damping, max_iterations, tolerance, top_k, self.n)
+
+    def _index_seeds(self, index, queries, seeds_per_query):
+        """the index's own top-`seeds_per_query` answer as seed tensors: (ids, quantised weights), both on the device"""
+        t = self.torch
         ids, scores = index.search_device(queries, int(seeds_per_query))
         with t.cuda.device(self.device):
             ids = ids.to(self.device)
@@ -277,7 +299,44 @@ class EntityGraph:
             w = t.where((ids >= 0) & (w > 0), w, t.zeros_like(w))          # clipped at 0; a slot past ntotal carries nothing
             mx = w.max(dim=1, keepdim=True).values
             wd = t.round(w / t.where(mx > 0, mx, t.ones_like(mx)) * float(MAX_SEED_WEIGHT)).to(t.int32).contiguous()
-            return self._ranked(ids.contiguous(), wd, a, tol, max_iterations, int(top_k), as_device)
+            return ids.contiguous(), wd
+
+    # ---------------------------------------------------------------------------------------------------------------- passages
+    def _check_chunks(self, mentions, damping, max_iterations, tolerance, top_k):
+        from .passages import MentionMap
+
+        if not isinstance(mentions, MentionMap):
+            raise ValueError("mentions must be a MentionMap")
+        if mentions.n_entities != self.n:
+            raise ValueError(f"the mention map is over {mentions.n_entities} entities and the graph has {self.n} vertices: entity i must be "
+                             f"vertex i")
+        if mentions.device != self.device:
+            raise ValueError(f"the mention map lives on {mentions.device} and the graph on {self.device}")
+        a, tol = self._check_run(damping, max_iterations, tolerance, None, self.n)
+        mentions.check_top_k(top_k)
+        return a, tol
+
+    def rank_chunks(self, mentions, seeds, seed_weights=None, damping: float = 0.85, max_iterations: int = 20, tolerance: float = 0.0,
+                    top_k=None, as_device: bool = False):
+        """personalized_pagerank, ending in chunks: the state of every query is pushed through `mentions` (a MentionMap over
+        this graph's vertices), S(c) = (sum over c's mentions (e, w) of w * p(e)) >> 12, without leaving the device.
+        -> float64 [B][n_chunks] scores (S / 2^28, exact), or with top_k (ids int64 [B][k], scores float64 [B][k], counts
+        int32 [B]): the chunks of positive score by (score descending, chunk ascending), (-1, -inf) past the count — a chunk
+        without mentions is never returned.  Every other argument as personalized_pagerank."""
+        a, tol = self._check_chunks(mentions, damping, max_iterations, tolerance, top_k)
+        with self.torch.cuda.device(self.device):
+            sd, wd = self._seed_tensors(seeds, seed_weights)
+            return self._ranked(sd, wd, a, tol, max_iterations, None if top_k is None else int(top_k), as_device, mentions=mentions)
+
+    def retrieve_chunks(self, index, queries, mentions, seeds_per_query: int = 5, top_k: int = 10, damping: float = 0.85,
+                        max_iterations: int = 20, tolerance: float = 0.0, as_device: bool = False):
+        """retrieve, ending in chunks: the seeds are the index's own top-`seeds_per_query` answer, the ranking is rank_chunks'.
+        -> (ids, scores, counts) as rank_chunks(top_k=top_k)."""
+        self._check_index(index, seeds_per_query)
+        a, tol = self._check_chunks(mentions, damping, max_iterations, tolerance, top_k)
+        sd, wd = self._index_seeds(index, queries, seeds_per_query)
+        with self.torch.cuda.device(self.device):
+            return self._ranked(sd, wd, a, tol, max_iterations, int(top_k), as_device, mentions=mentions)
 
 
 def personalized_pagerank(n: int, pairs, seeds, weights=None, device: int = 0, **kw):

@@ -1,0 +1,143 @@
+"""Passage retrieval from the entity graph, on the MI355X (csrc/ppr.hip, its last section): the PageRank mass of the entities
+pushed through the mention links onto the chunks, and the chunks ranked.
+
+What it replaces: the reference stores `(chunk)-[:MENTIONS]->(entity)` (event_graphrag_neo4j.py:508-536), and every PPR-based
+graph retriever (HippoRAG's, upstream RAG-ARC's) ends by summing, per passage, the PageRank of the entities it mentions.  With
+`EntityGraph.personalized_pagerank(top_k=None)` that is a [B][n] float64 matrix pulled to the host, a sparse product and a sort;
+here `MentionMap` keeps the links resident as a CSR by chunk and `EntityGraph.rank_chunks` / `.retrieve_chunks` project and rank
+next to the PPR state, without leaving HBM.
+
+The rule is fixed point (restated by tests/passage_ref.py): S(c) = (sum over c's mentions (e, w) of w * p(e)) >> 12
+with integer weights w in [1, 2^12), the score S / 2^28 — the same bits for any order of the mentions and any batch.  Only the sum
+is offered: a length normalisation is the caller's, through w.  No CPU fallback: without a device this raises."""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from ....hip import binding as B
+
+MAX_MENTION_WEIGHT = 1 << 12   # a (chunk, entity) weight, duplicates summed, stays below this
+SCORE_SHIFT = 28               # score = S / 2^28
+MAX_CHUNKS = (1 << 31) - 1     # n_chunks < 2^31 - 1: a chunk id is an int32 on the device
+MAX_TOPK_CHUNKS = 1 << 24      # the top-k key carries the chunk in 24 bits
+MAX_TOP_K = 8192
+
+
+def limits() -> dict:
+    """The constants of the projection (csrc/ppr.hip): the most mentions a single wave walks (a chunk of more is split across a
+    workgroup), the bits of a mention weight, the shift of a score and the bits of a chunk in the top-k key."""
+    out = (ctypes.c_int * 4)()
+    B.check(B.load_library().rarc_ppr_chunks_limits(out), "rarc_ppr_chunks_limits")
+    return {"split_degree": out[0], "weight_bits": out[1], "score_shift": out[2], "topk_chunk_bits": out[3]}
+
+
+def mention_csr(n_chunks: int, n_entities: int, mentions, weights=None, split_degree: int = 64):
+    """Host mentions -> (row_ptr int64 [n_chunks + 1], entities int32 [nnz], weights uint32 [nnz], split int32 [...]): the
+    duplicates of a (chunk, entity) merged (their weights add up), sorted by (chunk, entity); `split` lists the chunks of more
+    than `split_degree` mentions.  ValueError / RarcUnsupported, naming the limit, for an id out of range, a weight that is no
+    integer >= 1, a summed weight >= 2^12, or no mention at all."""
+    n_chunks, n_entities = int(n_chunks), int(n_entities)
+    if n_chunks < 1:
+        raise ValueError("a mention map needs at least 1 chunk")
+    if n_chunks >= MAX_CHUNKS:
+        raise B.RarcUnsupported(f"MentionMap(n_chunks={n_chunks}): the kernels take n_chunks < 2^31 - 1")
+    if n_entities < 1:
+        raise ValueError("a mention map needs at least 1 entity")
+    arr = np.asarray(mentions)
+    if arr.size == 0:
+        arr = np.zeros((0, 2), np.int64)
+    if arr.ndim != 2 or arr.shape[1] != 2:
+        raise ValueError(f"expected [nnz][2] (chunk, entity) mentions, got an array of shape {arr.shape}")
+    if not np.issubdtype(arr.dtype, np.integer) and not np.all(arr == np.floor(arr)):
+        raise ValueError("mentions must be integers")
+    arr = arr.astype(np.int64)
+    if arr.shape[0] < 1:
+        raise ValueError("a mention map needs at least 1 mention (nnz >= 1)")
+    if weights is None:
+        w = np.ones(arr.shape[0], np.int64)
+    else:
+        w = np.asarray(weights)
+        if w.shape != (arr.shape[0],):
+            raise ValueError(f"expected {arr.shape[0]} weights, got an array of shape {w.shape}")
+        if not np.all(w == np.floor(w)) or w.min() < 1:
+            raise ValueError("mention weights must be integers >= 1")
+        if w.max() >= MAX_MENTION_WEIGHT:
+            raise B.RarcUnsupported(f"a mention weight of {int(w.max())}: the weight of a (chunk, entity) must stay below 2^12 = {MAX_MENTION_WEIGHT}")
+        w = w.astype(np.int64)
+    if arr[:, 0].min() < 0 or arr[:, 0].max() >= n_chunks:
+        raise ValueError(f"a mention names a chunk outside [0, {n_chunks})")
+    if arr[:, 1].min() < 0 or arr[:, 1].max() >= n_entities:
+        raise ValueError(f"a mention names an entity outside [0, {n_entities})")
+    key, inverse = np.unique(arr[:, 0] * n_entities + arr[:, 1], return_inverse=True)      # sorted by (chunk, entity)
+    wsum = np.bincount(inverse.ravel(), weights=w.astype(np.float64), minlength=key.shape[0]).astype(np.int64)
+    if wsum.max() >= MAX_MENTION_WEIGHT:
+        raise B.RarcUnsupported(f"the weights of a repeated (chunk, entity) add up to {int(wsum.max())}: the sum must stay below 2^12 = "
+                                f"{MAX_MENTION_WEIGHT}")
+    chunk = key // n_entities
+    degree = np.bincount(chunk, minlength=n_chunks)
+    row_ptr = np.zeros(n_chunks + 1, np.int64)
+    np.cumsum(degree, out=row_ptr[1:])
+    split = np.flatnonzero(degree > int(split_degree)).astype(np.int32)
+    return row_ptr, (key % n_entities).astype(np.int32), wsum.astype(np.uint32), split
+
+
+class MentionMap:
+    """The links (chunk)-[:MENTIONS]->(entity), resident on the device as a CSR by chunk.
+    mentions: an [nnz][2] array-like of (chunk, entity); weights: integers >= 1 per mention (unit by default) — how often the
+    chunk mentions the entity, or any weight the caller prefers.  A repeated (chunk, entity) is one mention whose weights add
+    up; every weight, summed, stays below 2^12."""
+
+    def __init__(self, n_chunks: int, n_entities: int, mentions, weights=None, device: int = 0):
+        import torch
+
+        lim = limits()
+        row_ptr, ent, w, split = mention_csr(n_chunks, n_entities, mentions, weights, split_degree=lim["split_degree"])
+        if not torch.cuda.is_available():
+            raise B.RarcError("no ROCm device visible: the HIP backend has no CPU fallback")
+        self.torch, self.lib = torch, B.load_library()
+        self.n_chunks, self.n_entities, self.nnz = int(n_chunks), int(n_entities), int(ent.shape[0])
+        self.split_degree = lim["split_degree"]
+        self.device = torch.device("cuda", device)
+        with torch.cuda.device(self.device):
+            self._row_ptr = torch.from_numpy(row_ptr).to(self.device)
+            self._ent = torch.from_numpy(ent).to(self.device)
+            self._w = torch.from_numpy(w.view(np.int32)).to(self.device)
+            self._split = torch.from_numpy(split).to(self.device) if split.size else None
+        self.n_split = int(split.size)
+        self._cws = None
+
+    def check_top_k(self, top_k) -> None:
+        if top_k is None:
+            return
+        if not 1 <= int(top_k) <= MAX_TOP_K:
+            raise ValueError(f"top_k must lie in [1, {MAX_TOP_K}]")
+        if self.n_chunks >= MAX_TOPK_CHUNKS:
+            raise B.RarcUnsupported(f"top_k over n_chunks={self.n_chunks}: the top-k key carries the chunk in 24 bits, n_chunks < 2^24 = "
+                                    f"{MAX_TOPK_CHUNKS}; ask for the scores (top_k=None) instead")
+
+    def project(self, n: int, m: int, nq: int, cur: int, ws, top_k):
+        """The tail of one launch batch: the PPR state in `ws` (a device uint8 tensor, rarc_ppr_workspace_bytes) -> device tensors,
+        scores float64 [nq][n_chunks] or (ids, scores, counts)"""
+        t, lib, nc = self.torch, self.lib, self.n_chunks
+        need = int(lib.rarc_ppr_chunks_workspace_bytes(nc, nq))
+        if need == 0:
+            raise B.RarcError(f"rank_chunks: n_chunks={nc}, {nq} queries refused by rarc_ppr_chunks_workspace_bytes")
+        if self._cws is None or self._cws.numel() < need:
+            self._cws = None
+            self._cws = t.empty(need, dtype=t.uint8, device=self.device)
+        cws, cb = self._cws.data_ptr(), self._cws.numel()
+        stream = t.cuda.current_stream(self.device).cuda_stream
+        B.check(lib.rarc_ppr_chunks(n, m, nq, cur, ws.data_ptr(), ws.numel(), self._row_ptr.data_ptr(), self._ent.data_ptr(), self._w.data_ptr(),
+                                    nc, self.nnz, self._split.data_ptr() if self._split is not None else None, self.n_split, cws, cb, stream),
+                "rarc_ppr_chunks")
+        if top_k is None:
+            out = t.empty((nq, nc), dtype=t.float64, device=self.device)
+            B.check(lib.rarc_ppr_chunks_scores(nc, nq, cws, cb, out.data_ptr(), stream), "rarc_ppr_chunks_scores")
+            return out
+        ids = t.empty((nq, top_k), dtype=t.int64, device=self.device)
+        sc = t.empty((nq, top_k), dtype=t.float64, device=self.device)
+        cnt = t.empty(nq, dtype=t.int32, device=self.device)
+        B.check(lib.rarc_ppr_chunks_topk(nc, nq, top_k, cws, cb, ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(), stream), "rarc_ppr_chunks_topk")
+        return ids, sc, cnt
