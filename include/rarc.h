@@ -723,6 +723,18 @@ int rarc_debug_wide_bounds(const void* d_ws, size_t ws_bytes, int d_pad, int can
  * fp32 number the scan dequantises with.  Both are finite and positive for every mx (zero, subnormal, infinite and NaN
  * included) and mx * sq <= 127.4.  Host code only: touches no device, runs on a machine without one. */
 int rarc_debug_query_scale8(float mx, float* sq, float* qi);
+/* Test hooks for the dynamic tail of the int8-prefilter scan (csrc/scan_q8.hip).  Host code only: touch no device.
+ * _plan: what the launcher decides for a launch over tiles [t_begin, n_tiles) on `grid` workgroups, rows of d_pad dimensions in
+ * row format fmt, a dynamic share of pct per cent and a size limit of min_mib MiB of rows per workgroup: *t_dyn = first tile
+ * handed out by ticket (== n_tiles: no tail), *r0 = tile rounds of a first-level chunk, *unit = rounds the loop consumes at once.
+ * _chunks: the ranges of tickets k_first .. k_first + n - 1, t0[i] / t_end[i] = first tile and end of chunk i (tiles t0, t0 +
+ * stride, ... below t_end; t0 >= n_tiles: past the end).  _counter_offset: byte offset in the search workspace of the uint32
+ * ticket counter of the launch-th scan launch of a search (0-3; -1 otherwise), zero after a search whose launch had no tail. */
+int rarc_debug_q8_tail_plan(uint32_t t_begin, uint32_t n_tiles, uint32_t grid, int d_pad, int fmt, int pct, int min_mib,
+                            uint32_t* t_dyn, uint32_t* r0, uint32_t* unit);
+int rarc_debug_q8_tail_chunks(uint32_t k_first, uint32_t n, uint32_t stride, uint32_t unit, uint32_t t_dyn, uint32_t r0,
+                              uint32_t n_tiles, uint32_t* t0, uint32_t* t_end);
+int64_t rarc_debug_q8_tail_counter_offset(int launch);
 
 /*
  * Exact top-k over a LIST of rows of one index — the search behind a metadata filter (a LangChain-style `filter=` on the

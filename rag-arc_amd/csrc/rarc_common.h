@@ -33,7 +33,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // binscale : float   [256]
 // bininv   : float   [256]         1 / scale (bin width)
 // cnt      : uint32  [256]         (repair scratch counter lives in cnt[0])
-// flags    : uint32  [64]
+// flags    : uint32  [64]            zeroed by the seed pass of every search; [1] = OR of the status bits,
+//                                  [RARC_WS_TAIL_FLAG + i] = ticket counter of the i-th scan_q8 launch (dynamic tail)
 // hist     : uint32  [256][NB]     per-query score histogram of appended candidates
 // cnt2     : uint32  [256 wg][256] candidates appended per (workgroup, query)
 // seed     : float   [256][65536]  scores of the strided seed sample (initial thresholds)
@@ -49,6 +50,7 @@ constexpr size_t RARC_WS_BINSCALE = 2048;
 constexpr size_t RARC_WS_BININV = 3072;
 constexpr size_t RARC_WS_CNT = 4096;
 constexpr size_t RARC_WS_FLAGS = 5120;
+constexpr int RARC_WS_TAIL_FLAG = 32;  // flags[32 .. 35]: one ticket counter per launch of a cascaded scan (at most four)
 static_assert(RARC_WS_FLAGS + 4 == RARC_WS_ANYFLAG_OFFSET, "include/rarc.h out of sync");
 constexpr size_t RARC_WS_HIST = 8192;
 constexpr size_t RARC_WS_CNT2 = RARC_WS_HIST + (size_t)RARC_MAX_QUERIES * RARC_NB * 4;

@@ -31,6 +31,9 @@
 // Algorithmic HBM bytes per launch: n_rows × D × 2 (+ 8 bytes per tile of metadata).
 #include "rarc_common.h"
 #include <stdio.h>
+#ifdef RARC_Q8_ABLATIONS
+#include <algorithm>
+#endif
 
 struct ScanQ8Params {
   const uint4* corpus;   // fp16 (FMT 0), fp8 (FMT 1) or int8-shadow (FMT 2) rows [ceil32(n_rows)][D], 16-byte chunks
@@ -54,6 +57,9 @@ struct ScanQ8Params {
   uint32_t seg;
   uint32_t kprime;
   uint32_t nq;
+  uint32_t t_dyn;         // dynamic tail: tiles [t_begin, t_dyn) are handed out statically, [t_dyn, n_tiles) by ticket (q8_tail_chunk)
+  uint32_t tail_r0;       // ... tile rounds of a chunk of the first level
+  uint32_t* tail_ctr;     // ... this launch's ticket counter (zero at launch); null: the whole range is static
   unsigned long long* dbg;  // tools/scan_q8_bench: {shader cycles, 100 MHz ticks} of workgroup 0; else null
 };
 
@@ -77,6 +83,9 @@ constexpr int Q8_WSTAGE = 768;            // staged (query, key) survivors per w
 constexpr int Q8_STAGE = 8 * Q8_WSTAGE;   // ... per workgroup
 constexpr int Q8_TB_SLOTS = 16;           // passing lanes per wave and tile handled by the transposed survivor walk
 constexpr int Q8_TB_STRIDE = 80;          // 16 int32 scores | threshold | scale | query + row-half
+constexpr int Q8_DBG_BYTES = 65536;       // p.dbg of the measurement builds: words 0-1 workgroup 0's totals, 8-1031 the timeline,
+constexpr int Q8_FIN_SLOT = 2048;         // from this word on (start, end) of every workgroup: 2 x RARC_MAX_WG words
+static_assert((Q8_FIN_SLOT + 2 * RARC_MAX_WG) * 8 <= Q8_DBG_BYTES, "finish stamps past the debug buffer");
 
 template <bool B>
 struct Q8Flag { static constexpr bool value = B; };
@@ -118,7 +127,8 @@ struct ScanQ8Lds {
   static constexpr int SKEY = HLAND + 1024;     // uint64 [Q8_STAGE]
   static constexpr int SQ = SKEY + 8 * Q8_STAGE;  // uint8 [Q8_STAGE]
   static constexpr int TB = (SQ + Q8_STAGE + 15) & ~15;  // per wave: Q8_TB_SLOTS x 80 B transposition slots (prune)
-  static constexpr int TOTAL = TB + Q8_WAVES * Q8_TB_SLOTS * Q8_TB_STRIDE;
+  static constexpr int TICK = TB + Q8_WAVES * Q8_TB_SLOTS * Q8_TB_STRIDE;  // uint32: the ticket thread 0 drew (dynamic tail)
+  static constexpr int TOTAL = TICK + 16;
 };
 
 // the tile's metadata word: low half = fp16 scale, high half = fp16 R_t (rounded up; +inf when out of range)
@@ -140,6 +150,53 @@ __device__ __forceinline__ int q8_all16(const q8_i32x16& a) {
   for (int i = 1; i < 16; ++i) x ^= a[i];
   return x;
 }
+
+// Dynamic tail: ticket k -> the range (tiles *t0, *t0 + stride, ... below *t_end) of chunk k.  The tail [t_dyn, n_tiles) is cut
+// into LEVELS of whole tile rounds (a round = one tile per workgroup slot, `stride` tiles); a level of r rounds is `stride` chunks,
+// one per slot, each r tiles at the launch's stride — so concurrent chunks read neighbouring tiles, as the static share does, and
+// the levels tile the tail without gap or overlap by construction.  Level 0 has r0 rounds, each further one half of the one
+// before, rounded down to whole units (`unit` = the rounds the loop consumes at once, 2 or 4) and not below Q8_TAIL_RMIN: few
+// large chunks while every workgroup still has far to go, small ones at the end, where the finishing times are decided.
+// A ticket whose first tile is past the end returns *t0 >= n_tiles; so does every later ticket (first tiles grow with k).
+constexpr uint32_t Q8_TAIL_RMIN = 8;   // rounds (a multiple of both units)
+__host__ __device__ inline void q8_tail_chunk(uint32_t k, uint32_t stride, uint32_t unit, uint32_t t_dyn, uint32_t r0,
+                                              uint32_t n_tiles, uint32_t* t0, uint32_t* t_end) {
+  const uint32_t level = k / stride, slot = k - level * stride;
+  uint32_t r = r0 < Q8_TAIL_RMIN ? Q8_TAIL_RMIN : r0, start = 0;   // rounds of this level, rounds before it
+  for (uint32_t i = 0; i < level && (uint64_t)t_dyn + (uint64_t)start * stride < n_tiles; ++i) {
+    start += r;
+    r = (r >> 1) / unit * unit;
+    if (r < Q8_TAIL_RMIN) r = Q8_TAIL_RMIN;
+  }
+  const uint64_t first = (uint64_t)t_dyn + (uint64_t)start * stride + slot, end = (uint64_t)t_dyn + (uint64_t)(start + r) * stride;
+  *t0 = first < n_tiles ? (uint32_t)first : n_tiles;
+  *t_end = end < n_tiles ? (uint32_t)end : n_tiles;
+}
+
+// Dynamic tail, the launcher's half: where the static share of a launch over tiles [t_begin, n_tiles) on `g` workgroups ends and
+// how large the first level's chunks are.  `pct` per cent of the launch's tile rounds (rounded down) are the tail; the static
+// share keeps whole units of rounds and at least one (so every workgroup's first tile exists and t_dyn - t_begin is a multiple
+// of unit x g).  No tail — returns false, *t_dyn = n_tiles — when the share is under one unit, when nothing is left behind the
+// static share, or when the launch reads fewer than min_bytes of rows per workgroup (rounds x tile_bytes).  r0 = half the
+// tail's rounds in whole units: the levels r0, r0/2, ... of q8_tail_chunk then sum to about the tail.
+inline bool q8_tail_plan(uint32_t t_begin, uint32_t n_tiles, uint32_t g, uint32_t unit, uint32_t pct, uint64_t tile_bytes,
+                         uint64_t min_bytes, uint32_t* t_dyn, uint32_t* r0) {
+  *t_dyn = n_tiles;
+  *r0 = 0;
+  if (g == 0 || unit == 0 || n_tiles <= t_begin) return false;
+  const uint32_t rounds = (uint32_t)(((uint64_t)(n_tiles - t_begin) + g - 1) / g);
+  const uint32_t share = (uint32_t)((uint64_t)rounds * (pct > 100u ? 100u : pct) / 100u);
+  if (share < unit || (uint64_t)rounds * tile_bytes < min_bytes) return false;
+  uint32_t stat = (rounds - share) / unit * unit;
+  if (stat < unit) stat = unit;
+  const uint64_t td = (uint64_t)t_begin + (uint64_t)stat * g;
+  if (td >= n_tiles) return false;
+  *t_dyn = (uint32_t)td;
+  *r0 = (uint32_t)((((uint64_t)(n_tiles - *t_dyn) + g - 1) / g / 2) / unit * unit);
+  return true;
+}
+// tile rounds the loop consumes at once: four with four fetch groups (NG == 4, rows up to Q8_DEEP_D dimensions), else two
+inline uint32_t q8_tail_unit(int d_pad) { return d_pad <= 384 ? 4u : 2u; }
 
 // ABL (tools/scan_q8_bench): 1 = no pruning, 2 = no global loads after the prologue, 4 = no MFMA,
 // 8 = no threshold refresh, 16 = no conversion, 32768 = fp8: converted but not written to LDS, 32 = prune fast path only, 64 = never flush,
@@ -253,7 +310,9 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
   // puts them in 16 distinct bank groups)
   const uint32_t aoff = M16 ? (lane & 15) * L::RS + 16 * rq : row * L::RS + 16 * h;
 
-  const uint32_t t0 = p.t_begin + blockIdx.x, stride = gridDim.x;
+  const uint32_t stride = gridDim.x;
+  // the range this workgroup is on: tiles t0, t0 + stride, ... below t_end.  First its static share, then chunks of the tail.
+  uint32_t t0 = p.t_begin + blockIdx.x, t_end = p.tail_ctr ? p.t_dyn : p.n_tiles;
   // the query this workgroup owns (publishes thresholds for), and the histogram word this lane
   // fetches each iteration: wave w covers bins [32w, 32w+32) (lanes 32-63 duplicate lanes 0-31)
   const bool has_own = blockIdx.x < p.nq;
@@ -270,7 +329,7 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
     uint32_t thr;
     uint32_t hw;
   };
-  auto clamp_tile = [&](uint32_t t) { return t < p.n_tiles ? t : 0u; };  // past the end: tile 0 (an L2 hit)
+  auto clamp_tile = [&](uint32_t t) { return t < t_end ? t : 0u; };  // past the end of the range: tile 0 (an L2 hit)
   // (small items first: if the register allocator decides to move one of these long-lived values
   // while it is still in flight, the wait it needs then is for the OLDEST entries of the newest group,
   // i.e. no more than the wait for the group about to be consumed anyway)
@@ -602,7 +661,12 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
   // cycles per tile were 1170 + 2.4 D, the constant being exposed latency — DESIGN.md, narrow rows)
   constexpr int NG = D <= Q8_DEEP_D ? 4 : (FMT != 0 ? (D <= 768 ? 2 : Q8_BIG_NG) : (D <= 896 ? 2 : 1));
   // ---- prologue: tile t0 straight into LDS buffer 0; tiles t0+stride, t0+2·stride in flight ----
-  // (the launch guarantees gridDim.x <= n_tiles, so tile t0 exists)
+  // (the launch guarantees gridDim.x <= n_tiles and a static share of at least one round, so tile t0 exists; a chunk of the
+  //  tail is entered only when its first tile does)
+  // owner lane: last threshold it published (starts from what the seed pass / the tightening pass left there)
+  float last_pub = has_own ? __uint_as_float(p.thr[own_q]) : -INFINITY;
+  uint32_t it = 0;
+  do {  // one trip per range: the static share, then one per chunk of the dynamic tail
   Fetch f[NG];
   fetch(f[0], t0, Q8Flag<true>{});
   convert_tile(f[0], 0);
@@ -644,8 +708,6 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
     fetch(f[0], clamp_tile(t0 + stride), Q8Flag<true>{});
   }
   __builtin_amdgcn_sched_barrier(0);
-  // owner lane: last threshold it published (starts from what the seed pass / the tightening pass left there)
-  float last_pub = has_own ? __uint_as_float(p.thr[own_q]) : -INFINITY;
   // Drain once before the loop.  Otherwise the loop header sees, from this path only, prologue loads in
   // flight, and the wait the compiler places there for them (an absolute "at most N outstanding") is
   // executed on every trip and empties the prefetch queue each time.  Costs one memory latency per launch.
@@ -654,7 +716,6 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
 
   i32x16 acc_b = {0};      // group B: scores of the tile whose pruning is still to come
   bool live_prev = false;  // group B: that tile exists
-  uint32_t it = 0;
   // one iteration = one tile; PAR (its parity) names the LDS buffer read and the fetch group consumed
 #define Q8_STAMP(slot)                                                                                        \
   if ((ABL & 1024) && blockIdx.x == 0 && it >= 1000 && it < 1016 && lane == 0)                                 \
@@ -734,16 +795,16 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
 #define Q8_STEP(OFF, PAR, GB, G, GP)                                                  \
     {                                                                                 \
       const uint32_t cur = base + (OFF) * stride;                                     \
-      const bool live = (OFF) == 0 || cur < p.n_tiles;                                \
+      const bool live = (OFF) == 0 || cur < t_end;                                \
       Q8_ITER(PAR, GB, G, GP)                                                         \
     }
 #define Q8_LOOP(GB)                                                                   \
   if constexpr (NG == 4) {                                                            \
-    for (uint32_t base = t0; base < p.n_tiles; base += 4 * stride) {                  \
+    for (uint32_t base = t0; base < t_end; base += 4 * stride) {                  \
       Q8_STEP(0, 0, GB, 1, 0) Q8_STEP(1, 1, GB, 2, 1) Q8_STEP(2, 0, GB, 3, 2) Q8_STEP(3, 1, GB, 0, 3) \
     }                                                                                 \
   } else {                                                                            \
-    for (uint32_t base = t0; base < p.n_tiles; base += 2 * stride) {                  \
+    for (uint32_t base = t0; base < t_end; base += 2 * stride) {                  \
       Q8_STEP(0, 0, GB, NG == 2 ? 1 : 0, 0) Q8_STEP(1, 1, GB, 0, NG == 2 ? 1 : 0)     \
     }                                                                                 \
   }
@@ -758,7 +819,23 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
 #undef Q8_RF
   // group B still owes the pruning of its last tile (the second half of the last pair: LDS buffer 1)
   if (grp_b && !(ABL & 1) && live_prev)
-    prune(acc_b, t0 + (((p.n_tiles - 1 - t0) / stride) | (NG == 4 ? 3u : 1u)) * stride, mcur[1].y, mcur[1].x);
+    prune(acc_b, t0 + (((t_end - 1 - t0) / stride) | (NG == 4 ? 3u : 1u)) * stride, mcur[1].y, mcur[1].x);
+  // Dynamic tail.  The workgroups do not run at one rate (profiles/q8tail_finish_spread.txt: the XCDs finish a static 100M-row
+  // scan up to 1.5 ms apart, a launch ends with its slowest workgroup), so the end of the launch's range is not dealt out
+  // in advance: whoever is done draws the next chunk.  A chunk is a range like the static share — same stride, whole units of
+  // tile rounds — and runs through the same prologue, loop and epilogue: no second copy of the loop, no new fetch site, and the
+  // loop's vector-memory sequence is what it was.  What a chunk costs is one exposed memory latency (the prologue's drain)
+  // and the ticket's round trip, which is why chunks start large and halve (q8_tail_chunk).  Which workgroup runs a tile
+  // decides only the private segment its survivors land in; cnt2 / s_cnt simply go on counting.
+  t0 = p.n_tiles;
+  if (p.tail_ctr) {                      // (kernel-uniform)
+    uint32_t* s_tick = (uint32_t*)(smem + L::TICK);
+    if (tid == 0) *s_tick = atomicAdd(p.tail_ctr, 1u);
+    __syncthreads();                     // (drains this thread's loads still in flight for the range just left: they are tile-0 dummies)
+    const uint32_t k = __builtin_amdgcn_readfirstlane(*s_tick);
+    q8_tail_chunk(k, stride, NG == 4 ? 4u : 2u, p.t_dyn, p.tail_r0, p.n_tiles, &t0, &t_end);
+  }
+  } while (t0 < p.n_tiles);
   flush();
   __syncthreads();
   if (tid < RARC_MAX_QUERIES) p.cnt2[(size_t)blockIdx.x * RARC_MAX_QUERIES + tid] = s_cnt[tid];
@@ -766,6 +843,16 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
     p.dbg[0] = __builtin_amdgcn_s_memtime() - dbg_c0;
     p.dbg[1] = __builtin_amdgcn_s_memrealtime() - dbg_r0;
   }
+#ifdef RARC_Q8_ABLATIONS
+  // measurement builds, RARC_Q8_FINISH (launch_scan_q8 below): EVERY workgroup's start and end on the 100 MHz clock (the one
+  // clock that is the same on all XCDs), behind the timeline's slots.  Thread 0's own stores are acknowledged first, so the
+  // end stamp is the end of this workgroup's work as the launch sees it.  The product instantiation does not contain this.
+  if (!(ABL & 1024) && p.dbg && tid == 0) {
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    p.dbg[Q8_FIN_SLOT + 2 * blockIdx.x] = dbg_r0;
+    p.dbg[Q8_FIN_SLOT + 2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
+  }
+#endif
 }
 
 // ---- host side -----------------------------------------------------------------------------------
@@ -775,6 +862,61 @@ int rarc_seed_launch(const void* corpus, const float* rowscale, int fmt, int64_t
                      const float* sub_b, const RarcWs& ws, hipStream_t s, int64_t rows_covered, const float* floor);  // scan_f16.hip
 int rarc_scan_f16_stage_launch(const uint16_t* corpus, int64_t n_rows, uint32_t stage_tiles, int d_pad, const uint16_t* q16,
                                const float* eps16, int nq, int kprime, const RarcWs& ws, int cap, int grid, hipStream_t s);  // scan_f16.hip
+
+#ifdef RARC_Q8_ABLATIONS
+// Measurement builds, RARC_Q8_FINISH=<file> (tools/q8_finish_spread.sh): how far apart the persistent workgroups of ONE launch
+// finish.  Runs the full kernel (ABL 0; this build's copy of it differs from the product's by the stamps in its epilogue),
+// waits for it, and appends one line per launch: its length from the first workgroup's start to the last one's end, the
+// finishing times (last - first), (last - median), (last - mean), the spread of the starts, and the median end of the
+// workgroups of each XCD (workgroup b runs on XCD b mod 8).  100 MHz ticks, printed in us.  Results are right.
+template <int D, int FMT>
+static int launch_scan_q8_finish(const ScanQ8Params& p, int grid, hipStream_t s, const char* path) {
+  constexpr size_t lds = ScanQ8Lds<D, (FMT != 0) || Q8_M16_FP16_ROWS>::TOTAL;
+  static unsigned long long* d_dbg = nullptr;
+  if (!d_dbg) RARC_HIP_CHECK(hipMalloc((void**)&d_dbg, Q8_DBG_BYTES));
+  RARC_REQUIRE(grid >= 1 && grid <= RARC_MAX_WG, RARC_E_HIP, "launch_scan_q8_finish: grid %d", grid);
+  RARC_HIP_CHECK(hipMemsetAsync(d_dbg, 0, Q8_DBG_BYTES, s));
+  ScanQ8Params pd = p;
+  pd.dbg = d_dbg;
+  hipEvent_t e0, e1;
+  const bool prof = rarc_prof_next(&e0, &e1);
+  if (prof) RARC_HIP_CHECK(hipEventRecord(e0, s));
+  hipLaunchKernelGGL((rarc_scan_q8_kernel<D, FMT, 0>), dim3(grid), dim3(Q8_THREADS), lds, s, pd);
+  RARC_HIP_CHECK(hipGetLastError());
+  if (prof) RARC_HIP_CHECK(hipEventRecord(e1, s));
+  RARC_HIP_CHECK(hipStreamSynchronize(s));
+  static unsigned long long h[2 * RARC_MAX_WG];
+  RARC_HIP_CHECK(hipMemcpy(h, d_dbg + Q8_FIN_SLOT, sizeof(unsigned long long) * 2 * grid, hipMemcpyDeviceToHost));
+  FILE* f = fopen(path, "a");
+  if (!f) return RARC_OK;
+  double st[RARC_MAX_WG], en[RARC_MAX_WG];
+  unsigned long long s0 = ~0ull;
+  for (int b = 0; b < grid; ++b) s0 = h[2 * b] < s0 ? h[2 * b] : s0;
+  for (int b = 0; b < grid; ++b) { st[b] = (double)(h[2 * b] - s0) * 0.01; en[b] = (double)(h[2 * b + 1] - s0) * 0.01; }
+  auto median = [](double* v, int n) { std::sort(v, v + n); return n ? 0.5 * (v[(n - 1) / 2] + v[n / 2]) : 0.0; };
+  double xs[8], xe[8];   // per XCD: median start, median end
+  for (int x = 0; x < 8; ++x) {
+    double a[RARC_MAX_WG / 8 + 1], e[RARC_MAX_WG / 8 + 1];
+    int n = 0;
+    for (int b = x; b < grid; b += 8, ++n) { a[n] = st[b]; e[n] = en[b]; }
+    xs[x] = median(a, n);
+    xe[x] = median(e, n);
+  }
+  double mean = 0;
+  for (int b = 0; b < grid; ++b) mean += en[b] / grid;
+  std::sort(st, st + grid);
+  const double med = median(en, grid), first = en[0], last = en[grid - 1], len = last;  // (the earliest start is 0)
+  fprintf(f, "launch tiles [%u, %u) grid %d: %.1f us | ends: last-first %.1f us (%.2f %%) last-median %.1f us (%.2f %%) last-mean %.1f us (%.2f %%)"
+          " | starts: last-first %.1f us | per XCD median end - first end:", p.t_begin, p.n_tiles, grid, len, last - first,
+          100 * (last - first) / len, last - med, 100 * (last - med) / len, last - mean, 100 * (last - mean) / len, st[grid - 1]);
+  for (int x = 0; x < 8; ++x) fprintf(f, " %.1f", xe[x] - first);
+  fprintf(f, " | per XCD median start:");
+  for (int x = 0; x < 8; ++x) fprintf(f, " %.1f", xs[x]);
+  fprintf(f, "\n");
+  fclose(f);
+  return RARC_OK;
+}
+#endif
 
 template <int D, int FMT, int ABL = 0>
 static int launch_scan_q8(const ScanQ8Params& p, int grid, hipStream_t s) {
@@ -790,6 +932,8 @@ static int launch_scan_q8(const ScanQ8Params& p, int grid, hipStream_t s) {
   if constexpr (ABL == 0 && ((D == 1024 && FMT == 1) || (D == 768 && FMT == 0) || (D == 768 && FMT == 2))) {
     static const int abl = getenv("RARC_Q8_ABL") ? atoi(getenv("RARC_Q8_ABL")) : 0;
     // the row stream's cache policy, A/B in one binary (tools/q8_abl.sh): plain row loads under the full kernel and under the skeleton
+    if (abl == 0)
+      if (const char* path = getenv("RARC_Q8_FINISH")) return launch_scan_q8_finish<D, FMT>(p, grid, s, path);
     if (abl == 262144) return launch_scan_q8<D, FMT, 262144>(p, grid, s);
     if (abl == 262149) return launch_scan_q8<D, FMT, 262149>(p, grid, s);
     if (abl == 1) return launch_scan_q8<D, FMT, 1>(p, grid, s);
@@ -902,6 +1046,9 @@ int rarc_scan_q8_launch(const void* corpus, const float* rowscale, int fmt, int6
   p.kprime = (uint32_t)kprime;
   p.nq = (uint32_t)nq;
   p.dbg = nullptr;
+  p.t_dyn = p.n_tiles;
+  p.tail_r0 = 0;
+  p.tail_ctr = nullptr;
 
   int dev = 0, cus = 256;
   RARC_HIP_CHECK(hipGetDevice(&dev));
@@ -915,6 +1062,33 @@ int rarc_scan_q8_launch(const void* corpus, const float* rowscale, int fmt, int6
   auto launch = [&](const ScanQ8Params& pp) {
     return fmt == 2 ? dispatch_scan_q8<2>(pp, d_pad, grid, s)
                     : fmt == 1 ? dispatch_scan_q8<1>(pp, d_pad, grid, s) : dispatch_scan_q8<0>(pp, d_pad, grid, s);
+  };
+  // Dynamic tail (q8_tail_chunk, and the end of the kernel).  RARC_SCAN_Q8_TAIL = the share of every launch's tile rounds, in
+  // per cent, that is handed out by ticket instead of in advance; 0 = everything static, as before.  The default covers the
+  // spread a static 100M x 768 scan shows between its first and last workgroup (6.5-7 % of a launch,
+  // profiles/q8tail_finish_spread.txt) with room to spare; profiles/q8tail_share_sweep.txt is the sweep.  Read per call.
+  // The static share keeps whole units of rounds (cuts and t_dyn stay multiples of `pair`) and at least one, and the ticket
+  // counter of launch i is word RARC_WS_TAIL_FLAG + i of the workspace flags, which the seed pass below zeroes on this stream
+  // before every scan: no launch of its own.
+  // Only launches of RARC_SCAN_Q8_TAIL_MIN MiB of rows per workgroup or more get a tail (default 32 = 683 tile rounds of 768-dim
+  // fp16 rows, a launch of about 1.4 ms; tests set 0).  Shorter launches have nothing to recover (5-17 us of spread on the first
+  // two launches of the headline's cascade, less than the chunks' restarts cost), and a small shard keeps the static map, under
+  // which the fill of the private segments — and with it what the sticky growth of the candidate capacity has learned
+  // (engine.py) — is the same from one search to the next.
+  // Both switches are read on EVERY call, unlike RARC_SCAN_SPLIT / RARC_HYBRID below: they exist for the A/B against the static
+  // hand-out and for bisection in one process (and the tests flip them between two searches of one index).  Neither changes
+  // an answer, only who scans which tile; nothing in the product sets them.
+  int tail_pct = 16;
+  if (const char* e = getenv("RARC_SCAN_Q8_TAIL")) tail_pct = atoi(e);
+  tail_pct = tail_pct < 0 ? 0 : (tail_pct > 100 ? 100 : tail_pct);
+  int tail_min_mib = 32;
+  if (const char* e = getenv("RARC_SCAN_Q8_TAIL_MIN")) tail_min_mib = atoi(e);
+  const uint64_t tile_bytes = 32ull * (uint64_t)d_pad * (fmt == 0 ? 2u : 1u);
+  static_assert(Q8_DEEP_D == 384, "q8_tail_unit");
+  auto set_tail = [&](ScanQ8Params& pp, int launch_idx) {
+    const bool tail = q8_tail_plan(pp.t_begin, pp.n_tiles, (uint32_t)grid, q8_tail_unit(d_pad), (uint32_t)tail_pct, tile_bytes,
+                                   (uint64_t)(tail_min_mib > 0 ? tail_min_mib : 0) << 20, &pp.t_dyn, &pp.tail_r0);
+    pp.tail_ctr = tail ? ws.flags + RARC_WS_TAIL_FLAG + launch_idx : nullptr;
   };
   // Split scan.  While it follows the k-th best APPROXIMATE score the threshold sits two error bounds below it
   // (one because that score only bounds the true k-th best score L from below by eps8, one because a row as good
@@ -978,6 +1152,7 @@ int rarc_scan_q8_launch(const void* corpus, const float* rowscale, int fmt, int6
       pi.resume = 1u;
       pi.hot_margin = 0.f;
       *hybrid_out = 1;
+      set_tail(pi, 0);
       return launch(pi);
     }
   }
@@ -988,9 +1163,30 @@ int rarc_scan_q8_launch(const void* corpus, const float* rowscale, int fmt, int6
     pi.resume = i > 0 ? 1u : 0u;
     // (after a pass the tightened threshold is no longer "k-th approximate score - 2 eps8": count everything)
     pi.hot_margin = i > 0 ? 0.f : 1.0f;
+    set_tail(pi, i);
     if ((rc = launch(pi)) != RARC_OK) return rc;
     if (i < n_cuts && (rc = tighten(tighten_ctx, grid, 1)) != RARC_OK) return rc;
     begin = pi.n_tiles;
   }
   return RARC_OK;
+}
+
+// ---- test hooks of the dynamic tail: host code only, touch no device (tests/test_q8_tail_host.py) -------------------------
+extern "C" int rarc_debug_q8_tail_plan(uint32_t t_begin, uint32_t n_tiles, uint32_t grid, int d_pad, int fmt, int pct, int min_mib,
+                                       uint32_t* t_dyn, uint32_t* r0, uint32_t* unit) {
+  RARC_REQUIRE(t_dyn && r0 && unit, RARC_E_INVALID, "rarc_debug_q8_tail_plan: null pointer");
+  RARC_REQUIRE(d_pad > 0 && fmt >= 0 && fmt <= 2, RARC_E_INVALID, "rarc_debug_q8_tail_plan: d_pad %d, row format %d", d_pad, fmt);
+  *unit = q8_tail_unit(d_pad);
+  q8_tail_plan(t_begin, n_tiles, grid, *unit, (uint32_t)(pct < 0 ? 0 : pct), 32ull * (uint64_t)d_pad * (fmt == 0 ? 2u : 1u),
+               (uint64_t)(min_mib > 0 ? min_mib : 0) << 20, t_dyn, r0);
+  return RARC_OK;
+}
+extern "C" int rarc_debug_q8_tail_chunks(uint32_t k_first, uint32_t n, uint32_t stride, uint32_t unit, uint32_t t_dyn, uint32_t r0,
+                                         uint32_t n_tiles, uint32_t* t0, uint32_t* t_end) {
+  RARC_REQUIRE(t0 && t_end && stride > 0 && unit > 0, RARC_E_INVALID, "rarc_debug_q8_tail_chunks: null pointer, stride or unit 0");
+  for (uint32_t i = 0; i < n; ++i) q8_tail_chunk(k_first + i, stride, unit, t_dyn, r0, n_tiles, &t0[i], &t_end[i]);
+  return RARC_OK;
+}
+extern "C" int64_t rarc_debug_q8_tail_counter_offset(int launch) {
+  return launch >= 0 && launch < 4 ? (int64_t)(RARC_WS_FLAGS + 4 * (size_t)(RARC_WS_TAIL_FLAG + launch)) : -1;
 }

@@ -210,6 +210,10 @@ SIGNATURES = {
                                     c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "rarc_debug_wide_bounds": (c_int, [c_void_p, c_size_t, c_int, c_int, c_void_p, c_void_p]),
     "rarc_debug_query_scale8": (c_int, [c_float, ctypes.POINTER(c_float), ctypes.POINTER(c_float)]),
+    "rarc_debug_q8_tail_plan": (c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, c_int, c_int, c_int, c_int,
+                                        ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    "rarc_debug_q8_tail_chunks": (c_int, [ctypes.c_uint32] * 7 + [c_void_p, c_void_p]),
+    "rarc_debug_q8_tail_counter_offset": (c_int64, [c_int]),
     "rarc_search_rows_workspace_bytes": (c_size_t, [c_int, c_int]),
     "rarc_search_rows": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int64, c_void_p, c_int,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

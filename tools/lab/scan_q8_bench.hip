@@ -65,6 +65,7 @@ int main(int argc, char** argv) {
   p.n_rows = (uint32_t)N; p.n_tiles = (uint32_t)((N + 31) / 32); p.t_begin = 0; p.resume = 0; p.hot_margin = 1.0f;
   p.thr = (uint32_t*)ws.thr; p.hist = ws.hist; p.cnt2 = ws.cnt2; p.cand = ws.cand; p.seg = CAP / 256; p.kprime = KP; p.nq = NQ;
   p.binlo = ws.binlo; p.binscale = ws.binscale; p.bininv = ws.bininv;
+  p.t_dyn = p.n_tiles; p.tail_r0 = 0; p.tail_ctr = nullptr;   // (static hand-out)
   { unsigned long long* d; hipMalloc(&d, 65536); hipMemset(d, 0, 65536); p.dbg = d; }
   int grid = 256;
   const double gb = (double)N * D * 2 / 1e9;
