@@ -1522,31 +1522,16 @@ class FlatIndexF16:
     def search_filtered_device(self, queries, k: int, rowset: RowSet, strategy: str = "auto"):
         """search_filtered with the answer left on the device: (ids int64, scores fp32)."""
         t = self.torch
-        if k < 1:
-            raise ValueError("k must be >= 1")
-        if strategy not in ("auto", "subset", "overfetch"):
-            raise ValueError(f"unknown strategy: {strategy} ('auto', 'subset' or 'overfetch')")
-        self._refuse_filtered()
-        if k > B.WIDE_MAX_K:
-            raise B.RarcUnsupported(f"k={k} exceeds the limit of {B.WIDE_MAX_K} results per query")
-        if not isinstance(rowset, RowSet) or rowset._owner() is not self:
-            raise ValueError("search_filtered takes a RowSet made by this index's rowset()")
-        if rowset.version != self._rows_version():
-            raise B.RarcError("the index has changed since this RowSet was made (an add extends no filter, a delete renumbers "
-                              "rows): make a new one with rowset()")
+        self._check_filtered_call(k, strategy)
+        self._check_rowset(rowset, self._rows_version(), "search_filtered takes a RowSet made by this index's rowset()")
+        q = self._filtered_queries(queries)
         with t.cuda.device(self.device):
-            q = t.as_tensor(queries, dtype=t.float32).to(self.device).contiguous()
-            if q.ndim == 1:
-                q = q[None, :]
-            if q.ndim != 2 or q.shape[1] != self.dim:
-                raise ValueError(f"expected [nq][{self.dim}] queries, got {tuple(q.shape)}")
+            q = q.to(self.device).contiguous()
             nq, m = int(q.shape[0]), rowset.m
             if strategy == "auto":
                 strategy = self.filter_strategy(nq, k, m)
-            pad = float("inf" if self.metric == "l2" else "-inf")
-            out_ids = t.full((nq, k), -1, dtype=t.int64, device=self.device)
-            out_sc = t.full((nq, k), pad, dtype=t.float32, device=self.device)
-            if self.ntotal == 0 or nq == 0:           # the empty index answers padding; no kernel has anything to read
+            out_ids, out_sc, answered = self._filtered_outputs(nq, k)
+            if answered:
                 return out_ids, out_sc
             stats = self.filtered_stats
             n_batches = -(-nq // B.MAX_QUERIES)
@@ -1557,7 +1542,7 @@ class FlatIndexF16:
                 return out_ids, out_sc
             # over-fetch: ONE ordinary search for k' results (never a loop on k'), the strike, then the row-list search for
             # the queries whose k' results held too few allowed rows
-            kp = max(int(k), min(self._overfetch_k(k, m), self.FILTER_OVERFETCH_MAX_K, int(self.ntotal)))
+            kp = self._filter_kprime(k, m)
             ids, sc = self.search_device(q, kp)
             with self._lock:
                 count = t.empty(nq, dtype=t.int32, device=self.device)
@@ -1578,29 +1563,78 @@ class FlatIndexF16:
         """rarc_search_rows over the row list, 256 queries per call (caller holds the lock).  The queries go through
         rarc_prep_queries as for any search (normalised for metric "cosine"); nothing here reads their fp16 copy, so
         metric "ip" / "l2" take queries and rows of any finite scale."""
+        for s0 in range(0, q.shape[0], B.MAX_QUERIES):
+            qc = q[s0: s0 + B.MAX_QUERIES]
+            nq = int(qc.shape[0])
+            ws = self._rows_workspace(int(self.lib.rarc_search_rows_workspace_bytes(nq, k)))
+            fmt, l2, xn, stream, status = self._prep_row_queries(qc)
+            oi, osc = out_ids[s0: s0 + nq], out_sc[s0: s0 + nq]
+            B.check(self.lib.rarc_search_rows(self._rows.data_ptr(), fmt, self.ntotal, self.d_pad, self._qbuf["qblock"].data_ptr(),
+                                              nq, rowset.rows.data_ptr() if rowset.m else 0, rowset.m, k, self.id_base, xn, l2,
+                                              oi.data_ptr(), osc.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                    "rarc_search_rows")
+
+    # -- what search_filtered and search_filtered_many share -------------------------------------------------------------
+    def _check_filtered_call(self, k: int, strategy: str) -> None:
+        if k < 1:
+            raise ValueError("k must be >= 1")
+        if strategy not in ("auto", "subset", "overfetch"):
+            raise ValueError(f"unknown strategy: {strategy} ('auto', 'subset' or 'overfetch')")
+        self._refuse_filtered()
+        if k > B.WIDE_MAX_K:
+            raise B.RarcUnsupported(f"k={k} exceeds the limit of {B.WIDE_MAX_K} results per query")
+
+    def _filtered_queries(self, queries):
+        """float32 [nq][dim], wherever the caller's queries are."""
+        t = self.torch
+        q = t.as_tensor(queries, dtype=t.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if q.ndim != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"expected [nq][{self.dim}] queries, got {tuple(q.shape)}")
+        return q
+
+    def _check_rowset(self, rowset, version: int, takes: str, at: Optional[int] = None) -> None:
+        """A RowSet of this index, made at this version of its rows — or the caller's error, behind "rowsets[at]: " when the
+        RowSet is one of a list (the prefix is made for an error only: this runs once per query of a batch)."""
+        if isinstance(rowset, RowSet) and rowset._owner() is self and rowset.version == version:
+            return
+        prefix = "" if at is None else f"rowsets[{at}]: "
+        if not isinstance(rowset, RowSet) or rowset._owner() is not self:
+            raise ValueError(prefix + takes)
+        raise B.RarcError(f"{prefix}the index has changed since this RowSet was made (an add extends no filter, a delete "
+                          "renumbers rows): make a new one with rowset()")
+
+    def _filtered_outputs(self, nq: int, k: int):
+        """(out_ids, out_sc, answered): the answer as padding, and whether that IS the answer — the empty index and the empty
+        batch have nothing for a kernel to read."""
+        t = self.torch
+        pad = float("inf" if self.metric == "l2" else "-inf")
+        out_ids = t.full((nq, k), -1, dtype=t.int64, device=self.device)
+        out_sc = t.full((nq, k), pad, dtype=t.float32, device=self.device)
+        return out_ids, out_sc, self.ntotal == 0 or nq == 0
+
+    def _rows_workspace(self, nbytes: int):
+        """The workspace of rarc_search_rows / rarc_search_rows_grouped, grown to nbytes (caller holds the lock)."""
+        t = self.torch
+        if getattr(self, "_rows_ws", None) is None or self._rows_ws.numel() < nbytes:
+            self._rows_ws = None
+            self._rows_ws = t.empty(nbytes, dtype=t.uint8, device=self.device)
+        return self._rows_ws
+
+    def _prep_row_queries(self, qc):
+        """At most 256 queries through rarc_prep_queries into the query block (caller holds the lock); what the two row-list
+        searches hand the library besides: (fmt, l2, the rows' squared norms or 0, stream, status buffer)."""
         t = self.torch
         self._ensure_qbuf()
         norm = 1 if self.normalize else 0
         mn = max(self.max_norm, 1.0) if norm else self.max_norm
         stream = self._stream()
-        fmt = 2 if self.storage == "f32" else 0
-        l2 = self.metric == "l2"
+        l2 = 1 if self.metric == "l2" else 0
+        B.check(self.lib.rarc_prep_queries(qc.data_ptr(), qc.shape[1], int(qc.shape[0]), self.dim, self.d_pad, norm, mn, 0,
+                                           self._qbuf["qblock"].data_ptr(), stream), "rarc_prep_queries")
         status = t.empty(B.MAX_QUERIES, dtype=t.int32, device=self.device)
-        for s0 in range(0, q.shape[0], B.MAX_QUERIES):
-            qc = q[s0: s0 + B.MAX_QUERIES]
-            nq = int(qc.shape[0])
-            nbytes = int(self.lib.rarc_search_rows_workspace_bytes(nq, k))
-            if getattr(self, "_rows_ws", None) is None or self._rows_ws.numel() < nbytes:
-                self._rows_ws = None
-                self._rows_ws = t.empty(nbytes, dtype=t.uint8, device=self.device)
-            B.check(self.lib.rarc_prep_queries(qc.data_ptr(), qc.shape[1], nq, self.dim, self.d_pad, norm, mn, 0,
-                                               self._qbuf["qblock"].data_ptr(), stream), "rarc_prep_queries")
-            oi, osc = out_ids[s0: s0 + nq], out_sc[s0: s0 + nq]
-            B.check(self.lib.rarc_search_rows(self._rows.data_ptr(), fmt, self.ntotal, self.d_pad, self._qbuf["qblock"].data_ptr(),
-                                              nq, rowset.rows.data_ptr() if rowset.m else 0, rowset.m, k, self.id_base,
-                                              self._xn.data_ptr() if l2 else 0, 1 if l2 else 0, oi.data_ptr(), osc.data_ptr(),
-                                              status.data_ptr(), self._rows_ws.data_ptr(), self._rows_ws.numel(), stream),
-                    "rarc_search_rows")
+        return 2 if self.storage == "f32" else 0, l2, self._xn.data_ptr() if l2 else 0, stream, status
 
     # -- batched MMR over the resident rows (DESIGN 4.6b) -------------------------------------------------------------
     MMR_MAX_FETCH = 1024          # rarc_mmr_select_rows' candidates per query (MMR_MAX_N, csrc/fuse.hip)
@@ -1670,37 +1704,20 @@ class FlatIndexF16:
     def search_filtered_many_device(self, queries, k: int, rowsets, strategy: str = "auto"):
         """search_filtered_many with the answer left on the device: (ids int64, scores fp32)."""
         t = self.torch
-        if k < 1:
-            raise ValueError("k must be >= 1")
-        if strategy not in ("auto", "subset", "overfetch"):
-            raise ValueError(f"unknown strategy: {strategy} ('auto', 'subset' or 'overfetch')")
-        self._refuse_filtered()
-        if k > B.WIDE_MAX_K:
-            raise B.RarcUnsupported(f"k={k} exceeds the limit of {B.WIDE_MAX_K} results per query")
-        q = t.as_tensor(queries, dtype=t.float32)
-        if q.ndim == 1:
-            q = q[None, :]
-        if q.ndim != 2 or q.shape[1] != self.dim:
-            raise ValueError(f"expected [nq][{self.dim}] queries, got {tuple(q.shape)}")
+        self._check_filtered_call(k, strategy)
+        q = self._filtered_queries(queries)
         rowsets = list(rowsets)
         nq = int(q.shape[0])
         if len(rowsets) != nq:
             raise ValueError(f"search_filtered_many takes one RowSet (or None) per query: {nq} queries, {len(rowsets)} rowsets")
         version = self._rows_version()
         for i, rs in enumerate(rowsets):
-            if rs is None:
-                continue
-            if not isinstance(rs, RowSet) or rs._owner() is not self:
-                raise ValueError(f"rowsets[{i}]: search_filtered_many takes RowSets made by this index's rowset() (or None)")
-            if rs.version != version:
-                raise B.RarcError(f"rowsets[{i}]: the index has changed since this RowSet was made (an add extends no filter, a "
-                                  "delete renumbers rows): make a new one with rowset()")
+            if rs is not None:
+                self._check_rowset(rs, version, "search_filtered_many takes RowSets made by this index's rowset() (or None)", i)
         with t.cuda.device(self.device):
             q = q.to(self.device).contiguous()
-            pad = float("inf" if self.metric == "l2" else "-inf")
-            out_ids = t.full((nq, k), -1, dtype=t.int64, device=self.device)
-            out_sc = t.full((nq, k), pad, dtype=t.float32, device=self.device)
-            if self.ntotal == 0 or nq == 0:
+            out_ids, out_sc, answered = self._filtered_outputs(nq, k)
+            if answered:
                 return out_ids, out_sc
             self.filtered_stats["grouped_calls"] += 1
             lists: dict = {}            # the concatenated row lists of this call, by the RowSets they hold
@@ -1791,26 +1808,15 @@ class FlatIndexF16:
         d_lists = lists[key]
         up = self._upload_i64(np.concatenate([perm, tiles.reshape(-1)]))
         d_perm, d_tiles = up[:n], up[n:]
-        qs = q.index_select(0, d_perm)
-        norm = 1 if self.normalize else 0
-        mn = max(self.max_norm, 1.0) if norm else self.max_norm
-        stream = self._stream()
-        l2 = self.metric == "l2"
-        nbytes = int(self.lib.rarc_search_rows_grouped_workspace_bytes(n, k))
-        if getattr(self, "_rows_ws", None) is None or self._rows_ws.numel() < nbytes:
-            self._rows_ws = None
-            self._rows_ws = t.empty(nbytes, dtype=t.uint8, device=self.device)
-        status = t.empty(B.MAX_QUERIES, dtype=t.int32, device=self.device)
+        ws = self._rows_workspace(int(self.lib.rarc_search_rows_grouped_workspace_bytes(n, k)))
+        fmt, l2, xn, stream, status = self._prep_row_queries(q.index_select(0, d_perm))
         sub_ids = t.empty((n, k), dtype=t.int64, device=self.device)
         sub_sc = t.empty((n, k), dtype=t.float32, device=self.device)
-        B.check(self.lib.rarc_prep_queries(qs.data_ptr(), qs.shape[1], n, self.dim, self.d_pad, norm, mn, 0,
-                                           self._qbuf["qblock"].data_ptr(), stream), "rarc_prep_queries")
-        B.check(self.lib.rarc_search_rows_grouped(self._rows.data_ptr(), 2 if self.storage == "f32" else 0, self.ntotal, self.d_pad,
-                                                  self._qbuf["qblock"].data_ptr(), n, d_lists.data_ptr() if d_lists is not None else 0,
-                                                  d_tiles.data_ptr(), int(tiles.shape[0]), m_max, k, self.id_base,
-                                                  self._xn.data_ptr() if l2 else 0, 1 if l2 else 0, sub_ids.data_ptr(),
-                                                  sub_sc.data_ptr(), status.data_ptr(), self._rows_ws.data_ptr(),
-                                                  self._rows_ws.numel(), stream), "rarc_search_rows_grouped")
+        B.check(self.lib.rarc_search_rows_grouped(self._rows.data_ptr(), fmt, self.ntotal, self.d_pad, self._qbuf["qblock"].data_ptr(),
+                                                  n, d_lists.data_ptr() if d_lists is not None else 0, d_tiles.data_ptr(),
+                                                  int(tiles.shape[0]), m_max, k, self.id_base, xn, l2, sub_ids.data_ptr(),
+                                                  sub_sc.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                "rarc_search_rows_grouped")
         out_ids[d_perm], out_sc[d_perm] = sub_ids, sub_sc
 
     def neighbors_above(self, queries, threshold: float, k_cap: int = 64):

@@ -218,6 +218,106 @@ def test_engine_refusals(hip):
         idx.search_filtered(Q, 0, rs)
 
 
+# ------------------------------------------------------------------------------------------- the slab loop of rarc_search_rows
+# 256 queries make a slab of 32768 listed rows (csrc/subset.hip: sub_slab_rows): m = 32768 is one slab exactly, 32769 one slab
+# and one row, 70,001 three slabs — k keys carried from slab to slab through the select that only keeps them.  List positions
+# 32767 and 32768, the two sides of the first slab edge, hold bit-identical rows in the list of 32769 (rows A[32767], A[32768])
+# and in the list of every row (rows 32767, 32768); query 0 IS row 32767 and query 1 IS row A[32767], so the tie is at the top of
+# an answer and the id has to decide it across the edge.
+N_SLAB, D_SLAB, NQ_SLAB, EDGE = 70_001, 64, 256, 32768
+_SLAB: dict = {}
+
+
+def _slab_data():
+    """Rows, queries and the three row lists; made once, left unchanged."""
+    if not _SLAB:
+        rng = np.random.default_rng(4242)
+        X = rng.standard_normal((N_SLAB, D_SLAB)).astype(np.float32)
+        others = np.setdiff1d(np.arange(N_SLAB), [EDGE - 1, EDGE])
+        A = np.sort(rng.choice(others, EDGE + 1, replace=False)).astype(np.int64)
+        X[EDGE] = X[EDGE - 1]
+        X[A[EDGE]] = X[A[EDGE - 1]]
+        Q = rng.standard_normal((NQ_SLAB, D_SLAB)).astype(np.float32)
+        Q[0], Q[1] = X[EDGE - 1], X[A[EDGE - 1]]
+        _SLAB.update(X=X, Q=Q, lists={EDGE: A[:EDGE], EDGE + 1: A, N_SLAB: np.arange(N_SLAB, dtype=np.int64)}, index={}, ref={})
+    return _SLAB
+
+
+def _slab_index(hip, storage, metric):
+    S = _slab_data()
+    if (storage, metric) not in S["index"]:
+        idx = _index(hip, S["X"], storage, metric)
+        S["index"][(storage, metric)] = (idx, {m: idx.rowset(a) for m, a in S["lists"].items()})
+    return S["index"][(storage, metric)]
+
+
+def _slab_reference(oracle, storage, metric, m, k):
+    """subset_ref.search of the 256 queries over the list of m rows; computed once per list at the largest k asked of it (the
+    answer for a smaller k is its prefix).  The restatement scores every row it is given, so it is given the listed rows alone,
+    all of them allowed: position in the ascending list orders as the row number does, and the ids are mapped back."""
+    S = _slab_data()
+    key = (storage, metric, m)
+    if key not in S["ref"] or S["ref"][key][0].shape[1] < k:
+        normalize = metric == "cosine"
+        a = S["lists"][m]
+        rows = l2_ref.stored_rows(oracle, S["X"], storage, normalize)[a]
+        Dr, Ir = subset_ref.search(oracle, rows, S["Q"], k, np.arange(a.size), "l2" if metric == "l2" else "ip", normalize)
+        Ir = a[Ir]                                        # (k <= m: no padding)
+        Dr.setflags(write=False)
+        Ir.setflags(write=False)
+        S["ref"][key] = (Dr, Ir)
+    Dr, Ir = S["ref"][key]
+    return Dr[:, :k], Ir[:, :k]
+
+
+def _edge_tie_on_top(D, I, qi, lo, hi):
+    return I[qi, :2].tolist() == [int(lo), int(hi)] and _bits(D[qi, 0]) == _bits(D[qi, 1])
+
+
+@pytest.mark.parametrize("storage,metric", [("f16", "cosine"), ("f32", "l2")])
+@pytest.mark.parametrize("m", [EDGE, EDGE + 1, N_SLAB])
+def test_one_filter_slab_loop_matches_the_restatement(hip, oracle, storage, metric, m):
+    S = _slab_data()
+    idx, sets = _slab_index(hip, storage, metric)
+    D, I = idx.search_filtered(S["Q"], 10, sets[m], strategy="subset")
+    ref_D, ref_I = _slab_reference(oracle, storage, metric, m, 10)
+    print(f"slab loop {storage} {metric} m={m}: ids equal {np.array_equal(I, ref_I)}, score bits equal "
+          f"{np.array_equal(_bits(D), _bits(ref_D))}")
+    assert _same(D, I, ref_D, ref_I), (storage, metric, m)
+    A = S["lists"][EDGE + 1]
+    if m == EDGE + 1:
+        assert _edge_tie_on_top(D, I, 1, A[EDGE - 1], A[EDGE])
+    if m == N_SLAB:
+        assert _edge_tie_on_top(D, I, 0, EDGE - 1, EDGE) and _edge_tie_on_top(D, I, 1, A[EDGE - 1], A[EDGE])
+
+
+def test_one_filter_slab_loop_at_the_largest_k(hip, oracle):
+    """k = 8192 over three slabs: kept = k beside a full slab, the most keys the select ever holds."""
+    S = _slab_data()
+    idx, sets = _slab_index(hip, "f16", "cosine")
+    D, I = idx.search_filtered(S["Q"], 8192, sets[N_SLAB], strategy="subset")
+    ref_D, ref_I = _slab_reference(oracle, "f16", "cosine", N_SLAB, 8192)
+    print(f"slab loop k=8192: ids equal {np.array_equal(I, ref_I)}, score bits equal {np.array_equal(_bits(D), _bits(ref_D))}")
+    assert _same(D, I, ref_D, ref_I)
+    assert _edge_tie_on_top(D, I, 0, EDGE - 1, EDGE)
+
+
+@pytest.mark.parametrize("storage,metric", [("f16", "cosine"), ("f32", "l2")])
+def test_the_grouped_form_answers_as_the_one_filter_form(hip, storage, metric):
+    """csrc/subset.hip: "each query's answer is rarc_search_rows's for its list, bit for bit".  256 queries under one filter of
+    32769 rows cross a slab edge; the first 40 of them, each carrying that filter, have a slab of 209 k rows and a single round."""
+    S = _slab_data()
+    idx, sets = _slab_index(hip, storage, metric)
+    rs = sets[EDGE + 1]
+    D_one, I_one = idx.search_filtered(S["Q"], 10, rs, strategy="subset")
+    D_many, I_many = idx.search_filtered_many(S["Q"][:40], 10, [rs] * 40, strategy="subset")
+    assert D_many.shape == (40, 10) and _same(D_many, I_many, D_one[:40], I_one[:40])
+    A = S["lists"][EDGE + 1]
+    assert _edge_tie_on_top(D_many, I_many, 1, A[EDGE - 1], A[EDGE])
+    D_40, I_40 = idx.search_filtered(S["Q"][:40], 10, rs, strategy="subset")      # the one-filter form's single slab
+    assert _same(D_40, I_40, D_many, I_many)
+
+
 # ------------------------------------------------------------------------------------------------------------------ the store
 def _store(embedding=None, **kw):
     from rag_arc_amd.encapsulation.database.vector_db.hip_flat import HipFlatVectorStore
