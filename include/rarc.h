@@ -953,6 +953,50 @@ int rarc_ppr_chunks_topk(int64_t n_chunks, int nq, int top_k, void* d_cws, size_
 int rarc_ppr_chunks_limits(int* out4);
 
 /*
+ * k-hop neighbourhoods over the graph rarc_graph_csr wrote, for a batch of nq queries at once: which vertices lie within
+ * `hops` edges of a query's seeds, and how far each is — MATCH (s)-[*..h]-(v), as one bit-parallel multi-source breadth-first
+ * search.  The rule (restated by tests/khop_ref.py): edge weights are ignored; hop_q(v) is the fewest edges from
+ * any seed of q to v, a seed has hop 0, v is in q's neighbourhood iff hop_q(v) <= hops.  The state is one bit per (vertex,
+ * query, level), ceil(nq / 64) 64-bit words per vertex and level; every join is an OR or an integer sum — the same bits for
+ * any order of the edges and any batch, and row q of a batch equals the one-query call (csrc/khop.hip).
+ * Limits of every entry: 2 <= n < 2^31 - 1, 1 <= m < 2^30 (as rarc_graph_csr), 1 <= nq <= 256, 0 <= hops <= 8 (hops > 8:
+ * RARC_E_UNSUPPORTED); pointers aligned to their element, workspaces to 256 bytes; refused before any launch.
+ * d_ws: rarc_khop_workspace_bytes(n, m, nq, hops) bytes (0 for a refused shape); every entry of one search takes the same
+ * n, m, nq and hops.
+ *
+ * rarc_khop_seed — d_seeds int64 [nq][n_slots] (a vertex, or -1 = unused; 1 <= n_slots <= 64; a vertex may repeat, a row may
+ *   be empty; a vertex outside [0, n) is skipped).  Clears the state and writes level 0.
+ * rarc_khop_step — level `hop` (1 <= hop <= hops) becomes the neighbours of level hop - 1 that no earlier level holds; call it
+ *   once per hop, in order, after the seed.  d_grew_out: a uint32 that receives 1 if any query reached a new vertex, else 0,
+ *   or null.  Once it is 0 every later level is empty, and the remaining steps may be left out: the answer is the same.
+ *   A vertex of more than 64 neighbours (rarc_khop_limits) is split across the threads of a workgroup.
+ * rarc_khop_counts — d_out_counts int32 [nq][hops + 1]: the vertices at hop h exactly; never capped.
+ * rarc_khop_levels — d_out_levels uint8 [nq][n]: hop_q(v), or 255 for "not within hops".
+ * rarc_khop_list — per query the neighbourhood by (hop ascending, vertex ascending), its first min(size, max_vertices) entries
+ *   (1 <= max_vertices <= 65536; more: RARC_E_UNSUPPORTED): d_out_ids int64 [nq][max_vertices], d_out_hops int32
+ *   [nq][max_vertices], d_out_count int32 [nq]; slots past the count hold (-1, -1).
+ * rarc_khop_chunks — the neighbourhood pushed through a mention map (the CSR and the split list exactly as rarc_ppr_chunks
+ *   takes them, guarded the same way): S_q(c) = sum over c's mentions (e, w) with hop_q(e) <= hops of w * decay[hop_q(e)],
+ *   written as int64 [n_chunks][nq] into d_cws (rarc_ppr_chunks_workspace_bytes), where rarc_ppr_chunks_scores and
+ *   rarc_ppr_chunks_topk read it unchanged (score S / 2^28).  `decay`: a HOST array uint32 [hops + 1], every entry in
+ *   [0, 2^16]; with the mention weights of a chunk adding up to less than 2^12, S < 2^28.
+ * rarc_khop_limits — out5 = {largest hops, largest nq, largest n_slots, largest max_vertices, largest degree walked without a
+ *   split}.
+ */
+size_t rarc_khop_workspace_bytes(int64_t n, int64_t m, int nq, int hops);
+int rarc_khop_seed(int64_t n, int64_t m, const int64_t* d_seeds, int nq, int n_slots, int hops, void* d_ws, size_t ws_bytes, void* stream);
+int rarc_khop_step(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, int nq, int hops, int hop, void* d_ws, size_t ws_bytes,
+                   uint32_t* d_grew_out, void* stream);
+int rarc_khop_counts(int64_t n, int64_t m, int nq, int hops, void* d_ws, size_t ws_bytes, int32_t* d_out_counts, void* stream);
+int rarc_khop_levels(int64_t n, int64_t m, int nq, int hops, const void* d_ws, size_t ws_bytes, uint8_t* d_out_levels, void* stream);
+int rarc_khop_list(int64_t n, int64_t m, int nq, int hops, int max_vertices, void* d_ws, size_t ws_bytes, int64_t* d_out_ids,
+                   int32_t* d_out_hops, int32_t* d_out_count, void* stream);
+int rarc_khop_chunks(int64_t n, int64_t m, int nq, int hops, const uint32_t* decay, const void* d_ws, size_t ws_bytes,
+                     const int64_t* d_row_ptr, const int32_t* d_ent, const uint32_t* d_w, int64_t n_chunks, int64_t nnz,
+                     const int32_t* d_split, int64_t n_split, void* d_cws, size_t cws_bytes, void* stream);
+int rarc_khop_limits(int* out5);
+
+/*
  * Deleting rows of a resident index: stable in-place compaction.  The reference deletes by clearing the index and
  * embedding every surviving text again (encapsulation/database/vector_db/VectorStore_Faiss.py:374-415); the surviving
  * rows are in HBM already, so here they move down over the holes: row i of the result is the i-th surviving row.

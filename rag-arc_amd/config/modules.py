@@ -313,6 +313,9 @@ class HipGraphRetrieverConfig(AbstractConfig):
     damping: float = 0.85
     max_iterations: int = 20
     tolerance: float = 0.0
+    expansion: str = "ppr"             # "k_hop": rank by the mentions of the entities within `hops` edges
+    hops: int = 2
+    decay: Optional[List[int]] = None  # hops + 1 integers in [0, 2^16]; None: 4096 >> (2 h)
     device: int = 0
 
     def build(self) -> AbstractModule:
@@ -329,7 +332,8 @@ class HipGraphRetrieverConfig(AbstractConfig):
             pair_weights=data["pair_weights"] if "pair_weights" in data else None,
             mention_weights=data["mention_weights"] if "mention_weights" in data else None,
             ids=[str(i) for i in data["ids"]] if "ids" in data else None, metric=self.metric, device=self.device, k=self.k,
-            seeds_per_query=self.seeds_per_query, damping=self.damping, max_iterations=self.max_iterations, tolerance=self.tolerance)
+            seeds_per_query=self.seeds_per_query, damping=self.damping, max_iterations=self.max_iterations, tolerance=self.tolerance,
+            expansion=self.expansion, hops=self.hops, decay=self.decay)
         return BuiltModule(config=self, impl=retriever)
 
 

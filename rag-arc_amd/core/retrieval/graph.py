@@ -7,7 +7,11 @@ search, the PageRank, the projection and the top-k all run in librarc_hip.so wit
 (`EntityGraph.retrieve_chunks`); what comes back to the host is k (chunk, score) pairs per query.
 
 Each returned Document is a copy of the stored chunk with a `score` attribute (the exact fixed-point score S / 2^28), which is
-what `MultiPathRetriever` reads with getattr(d, "score", 1.0).  No CPU fallback: without a device the constructor raises."""
+what `MultiPathRetriever` reads with getattr(d, "score", 1.0).  No CPU fallback: without a device the constructor raises.
+
+`expansion="k_hop"` replaces the PageRank by a traversal: the chunks are ranked by their mentions of the entities within `hops`
+edges of the seeds, a mention one hop nearer counting `decay` times as much (`EntityGraph.expand_chunks`) — the
+expansion a Neo4j-backed local search writes MATCH (s)-[*..h]-(v).  The default, "ppr", is what it was."""
 import dataclasses
 import uuid
 from typing import Any, Dict, Iterable, List, Optional
@@ -20,9 +24,12 @@ from .base import BaseRetriever
 
 class HipGraphRetriever(BaseRetriever):
     def __init__(self, embedding, index, graph, mentions, docs: List[Document], k: int = 5, seeds_per_query: int = 5,
-                 damping: float = 0.85, max_iterations: int = 20, tolerance: float = 0.0, **kwargs):
+                 damping: float = 0.85, max_iterations: int = 20, tolerance: float = 0.0, expansion: str = "ppr", hops: int = 2,
+                 decay=None, **kwargs):
         super().__init__(**kwargs)
         self._validate_k(k)
+        if expansion not in ("ppr", "k_hop"):
+            raise ValueError(f"expansion must be 'ppr' or 'k_hop', got {expansion!r}")
         docs = list(docs)
         if int(index.ntotal) != graph.n:
             raise ValueError(f"the index holds {int(index.ntotal)} rows and the graph {graph.n} vertices: row i must be vertex i")
@@ -37,6 +44,12 @@ class HipGraphRetriever(BaseRetriever):
         self.k = k
         self.seeds_per_query, self.damping = int(seeds_per_query), float(damping)
         self.max_iterations, self.tolerance = int(max_iterations), float(tolerance)
+        self.expansion, self.hops, self.decay = expansion, int(hops), None
+        if expansion == "k_hop":                                                 # the refusals of expand_chunks, up front
+            from ...encapsulation.database.graph_db.neighbourhood import check_decay, check_hops
+
+            self.hops = check_hops(hops)
+            self.decay = check_decay(decay, self.hops)
 
     @staticmethod
     def _validate_k(k) -> None:
@@ -85,16 +98,22 @@ class HipGraphRetriever(BaseRetriever):
         return self.batch_invoke([query], **kwargs)[0]
 
     def batch_invoke(self, inputs: List[str], **kwargs: Any) -> List[List[Document]]:
-        """invoke() for a list of queries: one embedding batch, one search and one PageRank run per 256 queries.  Element i
-        equals invoke(inputs[i], **kwargs) — every query is ranked on its own, by integer arithmetic."""
+        """invoke() for a list of queries: one embedding batch, one search and one PageRank run (or one traversal, with
+        expansion="k_hop") per 256 queries.  Element i equals invoke(inputs[i], **kwargs) — every query is ranked on its own,
+        by integer arithmetic."""
         inputs = list(inputs)
         k = kwargs.get("k", self.k)
         self._validate_k(k)
         if not inputs:
             return []
-        ids, scores, counts = self.graph.retrieve_chunks(self.index, self._embed(inputs), self.mentions, seeds_per_query=self.seeds_per_query,
-                                                         top_k=min(k, len(self.docs)), damping=self.damping,
-                                                         max_iterations=self.max_iterations, tolerance=self.tolerance)
+        if self.expansion == "k_hop":
+            ids, scores, counts = self.graph.expand_chunks(self.index, self._embed(inputs), self.mentions, seeds_per_query=self.seeds_per_query,
+                                                           hops=self.hops, decay=self.decay, top_k=min(k, len(self.docs)))
+        else:
+            ids, scores, counts = self.graph.retrieve_chunks(self.index, self._embed(inputs), self.mentions,
+                                                             seeds_per_query=self.seeds_per_query, top_k=min(k, len(self.docs)),
+                                                             damping=self.damping, max_iterations=self.max_iterations,
+                                                             tolerance=self.tolerance)
         out: List[List[Document]] = []
         for q in range(len(inputs)):
             answer = []

@@ -1,0 +1,577 @@
+// khop.hip — k-hop neighbourhoods over the GRAPH blob rarc_graph_csr wrote, for a batch of queries at once: the
+// traversal a graph store is asked for with MATCH (s)-[*..h]-(v), as one bit-parallel multi-source breadth-first search.
+//
+// The rule (tests/khop_ref.py restates it in Python): edge weights are ignored; hop_q(v) is the fewest edges from any seed of
+// query q to v, a seed has hop 0, and v is in q's neighbourhood iff hop_q(v) <= hops (0 <= hops <= 8).
+//
+// The state is one bit per (vertex, query): W = ceil(nq / 64) 64-bit words per vertex, in `seen` (every level so far) and in
+// one array per level 0 .. hops.  With at most 64 queries a vertex's state is ONE word, and one word is what moves.
+//   seed   clears everything and sets bit q of level 0 and of seen at each of q's seeds (atomicOr: a repeated seed is idempotent)
+//   step   level[hop](v) = (OR over v's neighbours u of level[hop - 1](u)) & ~seen(v);   seen(v) |= level[hop](v)
+// The step is the pull form: only v's own lanes write v's words, the words they read (level[hop - 1]) are written by nobody in
+// that launch, and OR is idempotent and associative: the answer is the same bits for any order of the edges, any launch shape
+// and any batch.  Each hop is stepped once, in order 1, 2, .. after a seed; the `grew` word tells whether any query reached a new
+// vertex, and once it is 0 every later level is empty — it already is, because the seed cleared it.
+//
+// A lane whose word of seen(v) already holds every query of the batch reads no neighbour: late hops on a saturated graph cost
+// the read of seen and the write of an empty word.  KHOP_GROUP = 16 lanes share a vertex of up to KHOP_SPLIT_DEGREE = 64
+// neighbours, as 16 / WP neighbour slots x WP words (WP = the power of two >= W), joined by shuffle-ORs; a vertex of more
+// neighbours (the degree lists 2 and 3 of the blob) is split across the 256 threads of a workgroup, joined in LDS.
+//
+// The answers read the levels:
+//   counts  [q][h] = vertices at hop h exactly, never capped
+//   levels  uint8 [q][v] = hop_q(v), 255 for "not within hops"
+//   list    per query the neighbourhood by (hop ascending, vertex ascending), cut at max_vertices.  count / scan / write: a tile of
+//           KHOP_TILE vertices counts its bits per (level, query), a scan over the tiles turns the counts into offsets, and the
+//           tiles write at offset + rank inside the tile (ballot + popcount) — the position of an entry is a function of the
+//           levels alone
+//   chunks  S_q(c) = sum over c's mentions (e, w) with hop_q(e) <= hops of w * decay[hop_q(e)], an integer sum, written where
+//           rarc_ppr_chunks writes its S (chunk_ws.h): rarc_ppr_chunks_scores and rarc_ppr_chunks_topk read it unchanged, as
+//           S / 2^28.  w < 2^12 summed per chunk and decay <= 2^16 give S < 2^28.  The kernel guards itself as rarc_ppr_chunks
+//           does: a chunk's range is clamped to [0, nnz], an entry with e outside [0, n) or w outside [1, 2^12) contributes
+//           nothing, a listed chunk outside [0, n_chunks) is skipped, a chunk of more than 64 mentions that the list omits
+//           scores 0.  A lane is a query; the entries of a chunk are loaded once, one per lane, and handed round by readlane.
+//
+// The workspace is {grew u32 | level totals i32 [256][9]} | seen | level 0 .. hops | tile counts u32 [tiles][hops + 1][W * 64].
+#include "graph_csr.h"
+#include "chunk_ws.h"
+
+constexpr int KHOP_MAX_HOPS = 8;
+constexpr int KHOP_MAX_B = PPR_MAX_B;
+constexpr int KHOP_MAX_SEEDS = 64;
+constexpr int KHOP_MAX_VERTICES = 65536;
+constexpr int KHOP_SPLIT_DEGREE = LV_DEG_WAVE;              // a vertex of more neighbours is split across a workgroup
+constexpr int KHOP_GROUP = 16;                              // lanes that share a vertex of up to KHOP_SPLIT_DEGREE neighbours
+constexpr int KHOP_TILE = 1024;                             // vertices a wave counts and writes for the list
+constexpr uint32_t KHOP_MAX_DECAY = 1u << 16;
+constexpr size_t KHOP_CTL_BYTES = 256 + (size_t)KHOP_MAX_B * (KHOP_MAX_HOPS + 1) * 4;
+
+typedef unsigned long long u64;
+
+struct KhopWs {
+  uint32_t* grew;
+  int32_t* totals;                                          // [nq][hops + 1]
+  u64* seen;
+  u64* level;                                               // [hops + 1][n][W]
+  uint32_t* tiles;                                          // [tiles][hops + 1][W * 64]
+  size_t level_words;                                       // n * W
+  size_t clear_bytes;                                       // seen and every level, from `seen`
+  size_t bytes;
+};
+static inline int khop_words(int nq) { return (nq + 63) / 64; }
+__host__ __device__ static inline int64_t khop_tiles(int64_t n) { return (n + KHOP_TILE - 1) / KHOP_TILE; }
+static inline bool khop_shape_ok(int64_t n, int64_t m, int nq, int hops) {
+  return lv_shape_ok(n, m) && nq >= 1 && nq <= KHOP_MAX_B && hops >= 0 && hops <= KHOP_MAX_HOPS;
+}
+static KhopWs khop_carve(const void* base, int64_t n, int nq, int hops) {
+  char* b = (char*)base;
+  size_t o = 0;
+  KhopWs w;
+  auto take = [&](size_t bytes) { char* p = b + o; o += lv_align(bytes); return p; };
+  char* ctl = take(KHOP_CTL_BYTES);
+  w.grew = (uint32_t*)ctl;
+  w.totals = (int32_t*)(ctl + 256);
+  const int W = khop_words(nq);
+  w.level_words = (size_t)n * W;
+  const size_t state = lv_align(w.level_words * 8);         // (every array a multiple of 256 bytes: they are cleared as one)
+  w.seen = (u64*)take(state);
+  w.level = (u64*)take(state * (size_t)(hops + 1));
+  w.clear_bytes = state * (size_t)(hops + 2);
+  w.tiles = (uint32_t*)take((size_t)khop_tiles(n) * (size_t)(hops + 1) * W * 64 * 4);
+  w.bytes = o;
+  return w;
+}
+static inline u64* khop_level(const KhopWs& w, int h) { return w.level + (lv_align(w.level_words * 8) / 8) * (size_t)h; }
+
+// the queries of the batch that word `word` holds, as a mask
+__device__ __forceinline__ u64 khop_query_mask(int nq, int word) {
+  const int left = nq - word * 64;
+  return left <= 0 ? 0ull : (left >= 64 ? ~0ull : (1ull << left) - 1ull);
+}
+
+// ---- seeds ------------------------------------------------------------------------------------------------------------------------
+// one thread per (query, slot); a slot whose vertex lies outside [0, n) is unused
+__global__ __launch_bounds__(256) void khop_seed_kernel(const int64_t* __restrict__ seeds, int nq, int s, int64_t n, int W, u64* seen, u64* level0) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nq * s) return;
+  const int q = i / s;
+  const int64_t v = seeds[i];
+  if (v < 0 || v >= n) return;
+  const size_t at = (size_t)v * W + (q >> 6);
+  const u64 bit = 1ull << (q & 63);
+  atomicOr(&level0[at], bit);
+  atomicOr(&seen[at], bit);
+}
+
+// ---- the step -----------------------------------------------------------------------------------------------------------------------
+struct KhopStepArgs {
+  const int64_t* row_ptr;
+  const int32_t* adj;
+  const u64* prev;
+  u64* next;
+  u64* seen;
+  uint32_t* grew;
+  int64_t n;
+  int W;
+  int nq;
+};
+
+// WP: lanes per neighbour slot, one per word (the power of two >= W).  SPLIT: a workgroup per vertex of a degree list, its
+// waves joined in LDS; otherwise KHOP_GROUP lanes per vertex over every vertex, those of more than KHOP_SPLIT_DEGREE
+// neighbours left to the SPLIT launch
+template <int WP, bool SPLIT>
+__global__ __launch_bounds__(256) void khop_step_kernel(const KhopStepArgs p, const int32_t* __restrict__ list, const int64_t* __restrict__ list_count) {
+  constexpr int LANES = SPLIT ? 256 : KHOP_GROUP;
+  constexpr int NSLOT = LANES / WP;
+  constexpr int PER_BLOCK = SPLIT ? 1 : 256 / KHOP_GROUP;
+  __shared__ u64 s_part[SPLIT ? 4 * WP : 1];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int gl = tid % LANES;
+  const int word = gl % WP, slot = gl / WP;
+  const int W = p.W;
+  const u64 qmask = word < W ? khop_query_mask(p.nq, word) : 0ull;
+  int64_t items = p.n;
+  if (SPLIT) {
+    items = *list_count;
+    items = items < 0 ? 0 : (items > p.n ? p.n : items);
+  }
+  bool grew = false;
+  for (int64_t base = (int64_t)blockIdx.x * PER_BLOCK; base < items; base += (int64_t)gridDim.x * PER_BLOCK) {     // (workgroup-uniform)
+    const int64_t vi = base + (SPLIT ? 0 : tid / KHOP_GROUP);
+    bool live = vi < items;
+    int64_t v = 0, r0 = 0, deg = 0;
+    if (live) {
+      v = SPLIT ? (int64_t)list[vi] : vi;
+      live = v >= 0 && v < p.n;
+      v = live ? v : 0;
+      r0 = p.row_ptr[v];
+      deg = p.row_ptr[v + 1] - r0;
+      if (!SPLIT && deg > KHOP_SPLIT_DEGREE) live = false;
+    }
+    const size_t at = (size_t)v * W + word;
+    u64 sv = 0, need = 0;
+    if (live && qmask) {
+      sv = p.seen[at];
+      need = ~sv & qmask;
+    }
+    u64 acc = 0;
+    if (need) {                                                        // a word that holds every query already reads no neighbour
+#pragma unroll 4
+      for (int64_t e = slot; e < deg; e += NSLOT) {
+        const int32_t u = p.adj[r0 + e];
+        acc |= p.prev[(size_t)u * W + word];
+      }
+    }
+#pragma unroll
+    for (int d = WP; d < (SPLIT ? 64 : KHOP_GROUP); d <<= 1) acc |= (u64)__shfl_xor((long long)acc, d, 64);
+    if (SPLIT) {                                                       // the waves of the workgroup: ORs in LDS
+      if (lane < WP) s_part[wave * WP + lane] = acc;
+      __syncthreads();
+      if (tid < WP) acc = (s_part[tid] | s_part[WP + tid]) | (s_part[2 * WP + tid] | s_part[3 * WP + tid]);
+      __syncthreads();
+    }
+    if (slot == 0 && live && qmask) {
+      const u64 nw = acc & need;
+      p.next[at] = nw;
+      if (nw) {
+        p.seen[at] = sv | nw;
+        grew = true;
+      }
+    }
+  }
+  if (__builtin_amdgcn_ballot_w64(grew) && lane == 0) atomicOr(p.grew, 1u);
+}
+
+// ---- counting: shared by the counts and the list --------------------------------------------------------------------------------
+// lane b's counter gains the number of lanes whose x has bit b
+__device__ __forceinline__ uint32_t khop_count_bits(u64 x, int lane, uint32_t cnt) {
+  if (__builtin_amdgcn_ballot_w64(x != 0) == 0) return cnt;
+#pragma unroll 8
+  for (int b = 0; b < 64; ++b) {
+    const u64 mask = __builtin_amdgcn_ballot_w64((x >> b) & 1ull);
+    cnt += lane == b ? (uint32_t)__builtin_popcountll(mask) : 0u;
+  }
+  return cnt;
+}
+
+// a wave per (tile, level, word): tiles[tile][h][word * 64 + b] = vertices of the tile at hop h for query word * 64 + b
+__global__ __launch_bounds__(256) void khop_tile_count_kernel(const u64* __restrict__ level, size_t level_stride, int64_t n, int W, int H,
+                                                              uint32_t* tiles) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t items = khop_tiles(n) * H * W;
+  for (int64_t item = (int64_t)blockIdx.x * 4 + wave; item < items; item += (int64_t)gridDim.x * 4) {
+    const int word = (int)(item % W);
+    const int h = (int)((item / W) % H);
+    const int64_t tile = item / ((int64_t)W * H);
+    const u64* lv = level + level_stride * (size_t)h;
+    uint32_t cnt = 0;
+    for (int c = 0; c < KHOP_TILE / 64; ++c) {
+      const int64_t v = tile * KHOP_TILE + c * 64 + lane;
+      cnt = khop_count_bits(v < n ? lv[(size_t)v * W + word] : 0ull, lane, cnt);
+    }
+    tiles[((size_t)tile * H + h) * ((size_t)W * 64) + word * 64 + lane] = cnt;
+  }
+}
+
+// a thread per (level, query): the counts of the tiles become exclusive offsets, in place; totals[q][h] = their sum
+__global__ __launch_bounds__(256) void khop_tile_scan_kernel(int64_t n_tiles, int W, int H, int nq, uint32_t* tiles, int32_t* totals) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= H * nq) return;
+  const int h = i / nq, q = i % nq;
+  const size_t stride = (size_t)H * W * 64;
+  uint32_t* at = tiles + (size_t)h * W * 64 + q;
+  uint32_t run = 0;
+  for (int64_t t = 0; t < n_tiles; ++t) {
+    const uint32_t c = at[(size_t)t * stride];
+    at[(size_t)t * stride] = run;
+    run += c;
+  }
+  totals[(size_t)q * H + h] = (int32_t)run;
+}
+
+// a wave per (tile, word): the entries of its vertices, level by level, at offset + rank; block 0 also writes the counts
+__global__ __launch_bounds__(256) void khop_list_kernel(const u64* __restrict__ level, size_t level_stride, int64_t n, int W, int H, int nq,
+                                                        const uint32_t* __restrict__ tiles, const int32_t* __restrict__ totals, uint32_t max_vertices,
+                                                        int64_t* out_ids, int32_t* out_hops, int32_t* out_count) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (blockIdx.x == 0) {
+    for (int q = threadIdx.x; q < nq; q += 256) {
+      int64_t size = 0;
+      for (int h = 0; h < H; ++h) size += totals[(size_t)q * H + h];
+      out_count[q] = (int32_t)(size < (int64_t)max_vertices ? size : (int64_t)max_vertices);
+    }
+  }
+  const u64 below = (1ull << lane) - 1ull;
+  const int64_t items = khop_tiles(n) * W;
+  for (int64_t item = (int64_t)blockIdx.x * 4 + wave; item < items; item += (int64_t)gridDim.x * 4) {
+    const int word = (int)(item % W);
+    const int64_t tile = item / W;
+    const int q = word * 64 + lane;                                    // the query whose cursor this lane keeps
+    uint32_t before = 0;                                               // entries of q's list at the levels below h
+    for (int h = 0; h < H; ++h) {
+      uint32_t cursor = max_vertices;
+      if (q < nq) {
+        const uint32_t off = before + tiles[((size_t)tile * H + h) * ((size_t)W * 64) + q];
+        cursor = off < max_vertices ? off : max_vertices;
+        const uint32_t total = (uint32_t)totals[(size_t)q * H + h];      // (< 2^31, and `before` stays <= max_vertices: no wrap)
+        before = before + total < max_vertices ? before + total : max_vertices;
+      }
+      if (__builtin_amdgcn_ballot_w64(cursor < max_vertices) == 0) continue;   // every list of this word is full before this tile
+      const u64* lv = level + level_stride * (size_t)h;
+      for (int c = 0; c < KHOP_TILE / 64; ++c) {
+        const int64_t v = tile * KHOP_TILE + c * 64 + lane;
+        const u64 x = v < n ? lv[(size_t)v * W + word] : 0ull;
+        if (__builtin_amdgcn_ballot_w64(x != 0) == 0) continue;
+        for (int b = 0; b < 64; ++b) {                                 // (b is wave-uniform)
+          const bool mine = (x >> b) & 1ull;
+          const u64 mask = __builtin_amdgcn_ballot_w64(mine);
+          if (!mask) continue;
+          const uint32_t cb = (uint32_t)__shfl((int)cursor, b, 64);
+          const uint32_t pos = cb + (uint32_t)__builtin_popcountll(mask & below);
+          if (mine && pos < max_vertices && word * 64 + b < nq) {
+            const size_t o = (size_t)(word * 64 + b) * max_vertices + pos;
+            out_ids[o] = v;
+            out_hops[o] = h;
+          }
+          if (lane == b) {
+            const uint32_t nc = cursor + (uint32_t)__builtin_popcountll(mask);
+            cursor = nc < max_vertices ? nc : max_vertices;
+          }
+        }
+      }
+    }
+  }
+}
+
+// ---- the dense answer ---------------------------------------------------------------------------------------------------------------
+// a wave per (64 vertices, word), a lane a vertex.  The levels of a (vertex, query) are disjoint, so the hop is read off four
+// bit planes (plane k = the OR of the levels whose number has bit k) and `in` = the OR of all: no per-lane table
+__global__ __launch_bounds__(256) void khop_levels_kernel(const u64* __restrict__ level, size_t level_stride, int64_t n, int W, int H, int nq,
+                                                          uint8_t* out) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t items = ((n + 63) / 64) * W;
+  for (int64_t item = (int64_t)blockIdx.x * 4 + wave; item < items; item += (int64_t)gridDim.x * 4) {
+    const int word = (int)(item % W);
+    const int64_t v = (item / W) * 64 + lane;
+    u64 in = 0, p0 = 0, p1 = 0, p2 = 0, p3 = 0;
+    if (v < n) {
+      for (int h = 0; h < H; ++h) {
+        const u64 x = level[level_stride * (size_t)h + (size_t)v * W + word];
+        in |= x;
+        p0 |= (h & 1) ? x : 0ull;
+        p1 |= (h & 2) ? x : 0ull;
+        p2 |= (h & 4) ? x : 0ull;
+        p3 |= (h & 8) ? x : 0ull;
+      }
+    }
+    const int nb = nq - word * 64 < 64 ? nq - word * 64 : 64;
+    if (v < n) {
+      for (int b = 0; b < nb; ++b) {
+        const uint32_t d = (uint32_t)((p0 >> b) & 1ull) | (uint32_t)((p1 >> b) & 1ull) << 1 | (uint32_t)((p2 >> b) & 1ull) << 2 |
+                           (uint32_t)((p3 >> b) & 1ull) << 3;
+        out[(size_t)(word * 64 + b) * (size_t)n + (size_t)v] = (uint8_t)(((in >> b) & 1ull) ? d : 255u);
+      }
+    }
+  }
+}
+
+// ---- chunks -------------------------------------------------------------------------------------------------------------------------
+struct KhopChunkArgs {
+  const int64_t* row_ptr;
+  const int32_t* ent;
+  const uint32_t* w;
+  const u64* level;
+  u64* s;
+  size_t level_stride;
+  int64_t n;
+  int64_t n_chunks;
+  int64_t nnz;
+  int W;
+  int H;
+  int nq;
+  uint32_t decay[KHOP_MAX_HOPS + 1];
+};
+
+// a wave per (chunk, word), a lane a query; SPLIT: a workgroup per listed chunk, its waves take 64 mentions each in turn and
+// are joined by integer adds in LDS
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void khop_chunks_kernel(const KhopChunkArgs a, const int32_t* __restrict__ list, int64_t list_count) {
+  __shared__ u64 s_part[SPLIT ? 4 * 64 : 1];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int W = a.W;
+  const int64_t items = (SPLIT ? list_count : a.n_chunks) * W;
+  const int64_t first = SPLIT ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + wave;
+  const int64_t stride = SPLIT ? (int64_t)gridDim.x : (int64_t)gridDim.x * 4;
+  for (int64_t item = first; item < items; item += stride) {
+    const int word = (int)(item % W);
+    const int64_t ci = item / W;
+    const int64_t c = SPLIT ? (int64_t)list[ci] : ci;
+    if (SPLIT && (c < 0 || c >= a.n_chunks)) continue;                 // (workgroup-uniform: every thread reads the same entry)
+    int64_t r0 = a.row_ptr[c], r1 = a.row_ptr[c + 1];
+    r0 = r0 < 0 ? 0 : (r0 > a.nnz ? a.nnz : r0);
+    r1 = r1 < r0 ? r0 : (r1 > a.nnz ? a.nnz : r1);
+    const int64_t deg = r1 - r0;
+    const int q = word * 64 + lane;
+    u64 acc = 0;
+    if (SPLIT || deg <= KHOP_SPLIT_DEGREE) {
+      for (int64_t i0 = SPLIT ? wave * 64 : 0; i0 < deg; i0 += SPLIT ? 256 : 64) {
+        // this lane's mention: its entity's row of the levels, or -1 for an entry outside the rule, and its weight
+        int32_t row = -1;
+        uint32_t wt = 0;
+        if (i0 + lane < deg) {
+          const int32_t e = a.ent[r0 + i0 + lane];
+          const uint32_t w = a.w[r0 + i0 + lane];
+          if (e >= 0 && (int64_t)e < a.n && w >= 1u && w < (1u << PPR_CHUNK_WEIGHT_BITS)) {
+            row = e;
+            wt = w;
+          }
+        }
+        const int cnt = deg - i0 < 64 ? (int)(deg - i0) : 64;
+        for (int i = 0; i < cnt; ++i) {                                // (i is wave-uniform: every lane takes mention i)
+          const int32_t e = __shfl(row, i, 64);
+          const uint32_t w = (uint32_t)__shfl((int)wt, i, 64);
+          if (e < 0) continue;
+          const u64* at = a.level + (size_t)e * W + word;
+          uint32_t dec = 0;
+#pragma unroll
+          for (int h = 0; h <= KHOP_MAX_HOPS; ++h)
+            if (h < a.H) dec += ((at[a.level_stride * (size_t)h] >> lane) & 1ull) ? a.decay[h] : 0u;
+          acc += (u64)w * dec;
+        }
+      }
+    }
+    if (SPLIT) {
+      s_part[wave * 64 + lane] = acc;
+      __syncthreads();
+      if (wave == 0) acc = (s_part[lane] + s_part[64 + lane]) + (s_part[128 + lane] + s_part[192 + lane]);
+      __syncthreads();
+    }
+    if (q < a.nq && (!SPLIT || wave == 0)) a.s[(size_t)c * a.nq + q] = acc;     // (a chunk left to the SPLIT launch: 0 until that overwrites it)
+  }
+}
+
+// ---- C ABI ------------------------------------------------------------------------------------------------------------------------
+extern "C" int rarc_khop_limits(int* out5) {
+  RARC_REQUIRE(out5, RARC_E_INVALID, "rarc_khop_limits: null pointer");
+  out5[0] = KHOP_MAX_HOPS;
+  out5[1] = KHOP_MAX_B;
+  out5[2] = KHOP_MAX_SEEDS;
+  out5[3] = KHOP_MAX_VERTICES;
+  out5[4] = KHOP_SPLIT_DEGREE;
+  return RARC_OK;
+}
+
+extern "C" size_t rarc_khop_workspace_bytes(int64_t n, int64_t m, int nq, int hops) {
+  if (!khop_shape_ok(n, m, nq, hops)) return 0;
+  return khop_carve(nullptr, n, nq, hops).bytes;
+}
+
+#define KHOP_ALIGNED(P, A) (((uintptr_t)(P) & (uintptr_t)((A)-1)) == 0)
+#define KHOP_SHAPE_CHECKS(NAME)                                                                                                          \
+  RARC_REQUIRE(lv_shape_ok(n, m), RARC_E_INVALID, NAME ": n=%lld m=%lld out of range (2 <= n < 2^31 - 1, 1 <= m < 2^30)", (long long)n,  \
+               (long long)m);                                                                                                            \
+  RARC_REQUIRE(nq >= 1 && nq <= KHOP_MAX_B, RARC_E_INVALID, NAME ": %d queries out of range (1 <= B <= %d per call)", nq, KHOP_MAX_B);   \
+  RARC_REQUIRE(hops >= 0, RARC_E_INVALID, NAME ": hops=%d out of range (0 <= hops <= %d)", hops, KHOP_MAX_HOPS);                         \
+  RARC_REQUIRE(hops <= KHOP_MAX_HOPS, RARC_E_UNSUPPORTED, NAME ": hops=%d: at most %d levels are kept (0 <= hops <= %d)", hops,          \
+               KHOP_MAX_HOPS, KHOP_MAX_HOPS);                                                                                            \
+  RARC_REQUIRE(KHOP_ALIGNED(d_ws, 256), RARC_E_INVALID, NAME ": the workspace is not 256-byte aligned");                                 \
+  const KhopWs ws = khop_carve(d_ws, n, nq, hops);                                                                                       \
+  RARC_REQUIRE(ws_bytes >= ws.bytes, RARC_E_WORKSPACE, NAME ": workspace of %zu bytes, %zu needed", ws_bytes, ws.bytes);                 \
+  const int W = khop_words(nq), H = hops + 1;                                                                                            \
+  const size_t level_stride = lv_align(ws.level_words * 8) / 8;                                                                          \
+  (void)W;                                                                                                                               \
+  (void)H;                                                                                                                               \
+  (void)level_stride
+
+extern "C" int rarc_khop_seed(int64_t n, int64_t m, const int64_t* d_seeds, int nq, int n_slots, int hops, void* d_ws, size_t ws_bytes,
+                              void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_seeds && d_ws, RARC_E_INVALID, "rarc_khop_seed: null pointer");
+  RARC_REQUIRE(KHOP_ALIGNED(d_seeds, 8), RARC_E_INVALID, "rarc_khop_seed: the seeds are not 8-byte aligned");
+  KHOP_SHAPE_CHECKS("rarc_khop_seed");
+  RARC_REQUIRE(n_slots >= 1 && n_slots <= KHOP_MAX_SEEDS, RARC_E_INVALID, "rarc_khop_seed: %d seed slots out of range (1 <= s <= %d)", n_slots,
+               KHOP_MAX_SEEDS);
+  hipStream_t s = (hipStream_t)stream;
+  RARC_HIP_CHECK(hipMemsetAsync(ws.grew, 0, KHOP_CTL_BYTES, s));
+  RARC_HIP_CHECK(hipMemsetAsync(ws.seen, 0, ws.clear_bytes, s));
+  hipLaunchKernelGGL(khop_seed_kernel, dim3((nq * n_slots + 255) / 256), dim3(256), 0, s, d_seeds, nq, n_slots, n, W, ws.seen, khop_level(ws, 0));
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+template <int WP>
+static void khop_launch_step(const KhopStepArgs& p, const LvGraph& g, int64_t n, int64_t m, hipStream_t s) {
+  hipLaunchKernelGGL((khop_step_kernel<WP, false>), dim3(lv_grid(n, 256 / KHOP_GROUP, 16384)), dim3(256), 0, s, p, (const int32_t*)nullptr,
+                     (const int64_t*)nullptr);
+  const int64_t dmax = lv_max_degree(n, m);              // no vertex of this graph has more neighbours: skip the lists that must be empty
+  if (dmax > LV_DEG_WAVE)
+    hipLaunchKernelGGL((khop_step_kernel<WP, true>), dim3(lv_grid(n, 1, 2048)), dim3(256), 0, s, p, (const int32_t*)g.list[2],
+                       (const int64_t*)&g.hdr[LV_H_LIST + 2]);
+  if (dmax > LV_DEG_LDS)
+    hipLaunchKernelGGL((khop_step_kernel<WP, true>), dim3(lv_grid(n / LV_DEG_LDS + 1, 1, 2048)), dim3(256), 0, s, p, (const int32_t*)g.list[3],
+                       (const int64_t*)&g.hdr[LV_H_LIST + 3]);
+}
+
+extern "C" int rarc_khop_step(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, int nq, int hops, int hop, void* d_ws,
+                              size_t ws_bytes, uint32_t* d_grew_out, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_graph && d_ws, RARC_E_INVALID, "rarc_khop_step: null pointer");
+  RARC_REQUIRE(KHOP_ALIGNED(d_graph, 256), RARC_E_INVALID, "rarc_khop_step: the graph is not 256-byte aligned");
+  RARC_REQUIRE(KHOP_ALIGNED(d_grew_out, 4), RARC_E_INVALID, "rarc_khop_step: the grew word is not 4-byte aligned");
+  KHOP_SHAPE_CHECKS("rarc_khop_step");
+  RARC_REQUIRE(hop >= 1 && hop <= hops, RARC_E_INVALID, "rarc_khop_step: hop %d out of range (1 <= hop <= hops = %d)", hop, hops);
+  const LvGraph g = lv_graph_carve(d_graph, n, m);
+  RARC_REQUIRE(graph_bytes >= g.bytes, RARC_E_WORKSPACE, "rarc_khop_step: graph workspace of %zu bytes, %zu needed", graph_bytes, g.bytes);
+  hipStream_t s = (hipStream_t)stream;
+  KhopStepArgs p;
+  p.row_ptr = g.row_ptr;
+  p.adj = g.adj;
+  p.prev = khop_level(ws, hop - 1);
+  p.next = khop_level(ws, hop);
+  p.seen = ws.seen;
+  p.grew = ws.grew;
+  p.n = n;
+  p.W = W;
+  p.nq = nq;
+  RARC_HIP_CHECK(hipMemsetAsync(ws.grew, 0, 4, s));
+  if (W > 2) khop_launch_step<4>(p, g, n, m, s);
+  else if (W > 1) khop_launch_step<2>(p, g, n, m, s);
+  else khop_launch_step<1>(p, g, n, m, s);
+  RARC_HIP_CHECK(hipGetLastError());
+  if (d_grew_out) RARC_HIP_CHECK(hipMemcpyAsync(d_grew_out, ws.grew, 4, hipMemcpyDeviceToDevice, s));
+  return RARC_OK;
+}
+
+// tile counts -> offsets and totals: the first two passes of the list, and all of the counts
+static void khop_rank(const KhopWs& ws, size_t level_stride, int64_t n, int W, int H, int nq, hipStream_t s) {
+  hipLaunchKernelGGL(khop_tile_count_kernel, dim3(lv_grid(khop_tiles(n) * H * W, 4, 16384)), dim3(256), 0, s, (const u64*)ws.level, level_stride, n,
+                     W, H, ws.tiles);
+  hipLaunchKernelGGL(khop_tile_scan_kernel, dim3((H * nq + 255) / 256), dim3(256), 0, s, khop_tiles(n), W, H, nq, ws.tiles, ws.totals);
+}
+
+extern "C" int rarc_khop_counts(int64_t n, int64_t m, int nq, int hops, void* d_ws, size_t ws_bytes, int32_t* d_out_counts, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_ws && d_out_counts, RARC_E_INVALID, "rarc_khop_counts: null pointer");
+  RARC_REQUIRE(KHOP_ALIGNED(d_out_counts, 4), RARC_E_INVALID, "rarc_khop_counts: the counts are not 4-byte aligned");
+  KHOP_SHAPE_CHECKS("rarc_khop_counts");
+  hipStream_t s = (hipStream_t)stream;
+  khop_rank(ws, level_stride, n, W, H, nq, s);
+  RARC_HIP_CHECK(hipGetLastError());
+  RARC_HIP_CHECK(hipMemcpyAsync(d_out_counts, ws.totals, (size_t)nq * H * 4, hipMemcpyDeviceToDevice, s));
+  return RARC_OK;
+}
+
+extern "C" int rarc_khop_levels(int64_t n, int64_t m, int nq, int hops, const void* d_ws, size_t ws_bytes, uint8_t* d_out_levels, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_ws && d_out_levels, RARC_E_INVALID, "rarc_khop_levels: null pointer");
+  KHOP_SHAPE_CHECKS("rarc_khop_levels");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(khop_levels_kernel, dim3(lv_grid(((n + 63) / 64) * W, 4, 16384)), dim3(256), 0, s, (const u64*)ws.level, level_stride, n, W, H,
+                     nq, d_out_levels);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+extern "C" int rarc_khop_list(int64_t n, int64_t m, int nq, int hops, int max_vertices, void* d_ws, size_t ws_bytes, int64_t* d_out_ids,
+                              int32_t* d_out_hops, int32_t* d_out_count, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_ws && d_out_ids && d_out_hops && d_out_count, RARC_E_INVALID, "rarc_khop_list: null pointer");
+  RARC_REQUIRE(KHOP_ALIGNED(d_out_ids, 8) && KHOP_ALIGNED(d_out_hops, 4) && KHOP_ALIGNED(d_out_count, 4), RARC_E_INVALID,
+               "rarc_khop_list: an output is not aligned to its element (ids 8 bytes, hops and counts 4)");
+  KHOP_SHAPE_CHECKS("rarc_khop_list");
+  RARC_REQUIRE(max_vertices >= 1, RARC_E_INVALID, "rarc_khop_list: max_vertices=%d out of range (1 <= max_vertices <= %d)", max_vertices,
+               KHOP_MAX_VERTICES);
+  RARC_REQUIRE(max_vertices <= KHOP_MAX_VERTICES, RARC_E_UNSUPPORTED,
+               "rarc_khop_list: max_vertices=%d: a list holds at most %d vertices (rarc_khop_levels has no such limit)", max_vertices,
+               KHOP_MAX_VERTICES);
+  hipStream_t s = (hipStream_t)stream;
+  RARC_HIP_CHECK(hipMemsetAsync(d_out_ids, 0xFF, (size_t)nq * max_vertices * 8, s));        // (-1, -1) past the count
+  RARC_HIP_CHECK(hipMemsetAsync(d_out_hops, 0xFF, (size_t)nq * max_vertices * 4, s));
+  khop_rank(ws, level_stride, n, W, H, nq, s);
+  hipLaunchKernelGGL(khop_list_kernel, dim3(lv_grid(khop_tiles(n) * W, 4, 16384)), dim3(256), 0, s, (const u64*)ws.level, level_stride, n, W, H, nq,
+                     (const uint32_t*)ws.tiles, (const int32_t*)ws.totals, (uint32_t)max_vertices, d_out_ids, d_out_hops, d_out_count);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+extern "C" int rarc_khop_chunks(int64_t n, int64_t m, int nq, int hops, const uint32_t* decay, const void* d_ws, size_t ws_bytes,
+                                const int64_t* d_row_ptr, const int32_t* d_ent, const uint32_t* d_w, int64_t n_chunks, int64_t nnz,
+                                const int32_t* d_split, int64_t n_split, void* d_cws, size_t cws_bytes, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(decay && d_ws && d_row_ptr && d_ent && d_w && d_cws && (d_split || n_split == 0), RARC_E_INVALID, "rarc_khop_chunks: null pointer");
+  RARC_REQUIRE(KHOP_ALIGNED(d_row_ptr, 8) && KHOP_ALIGNED(d_ent, 4) && KHOP_ALIGNED(d_w, 4) && KHOP_ALIGNED(d_split, 4), RARC_E_INVALID,
+               "rarc_khop_chunks: a mention array is not aligned to its element (row_ptr 8 bytes, entities, weights and the split list 4)");
+  KHOP_SHAPE_CHECKS("rarc_khop_chunks");
+  RARC_REQUIRE(n_chunks >= 1 && n_chunks < PPR_CHUNK_N_LIMIT, RARC_E_INVALID, "rarc_khop_chunks: n_chunks=%lld out of range (1 <= n_chunks < 2^31 - 1)",
+               (long long)n_chunks);
+  RARC_REQUIRE(KHOP_ALIGNED(d_cws, 256), RARC_E_INVALID, "rarc_khop_chunks: the chunk workspace is not 256-byte aligned");
+  const PprChunkWs cws = ppr_chunk_carve(d_cws, n_chunks, nq);
+  RARC_REQUIRE(cws_bytes >= cws.bytes, RARC_E_WORKSPACE, "rarc_khop_chunks: chunk workspace of %zu bytes, %zu needed", cws_bytes, cws.bytes);
+  RARC_REQUIRE(nnz >= 1, RARC_E_INVALID, "rarc_khop_chunks: nnz=%lld mentions out of range (nnz >= 1)", (long long)nnz);
+  RARC_REQUIRE(n_split >= 0 && n_split <= n_chunks, RARC_E_INVALID, "rarc_khop_chunks: %lld split chunks out of range (0 <= n_split <= n_chunks)",
+               (long long)n_split);
+  KhopChunkArgs a;
+  for (int h = 0; h <= KHOP_MAX_HOPS; ++h) {                           // `decay` is a host array of hops + 1 words
+    a.decay[h] = h < H ? decay[h] : 0u;
+    RARC_REQUIRE(a.decay[h] <= KHOP_MAX_DECAY, RARC_E_INVALID, "rarc_khop_chunks: decay[%d]=%u out of range (0 <= decay <= 2^16 = %u)", h,
+                 a.decay[h], KHOP_MAX_DECAY);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  a.row_ptr = d_row_ptr;
+  a.ent = d_ent;
+  a.w = d_w;
+  a.level = ws.level;
+  a.s = cws.s;
+  a.level_stride = level_stride;
+  a.n = n;
+  a.n_chunks = n_chunks;
+  a.nnz = nnz;
+  a.W = W;
+  a.H = H;
+  a.nq = nq;
+  hipLaunchKernelGGL(khop_chunks_kernel<false>, dim3(lv_grid(n_chunks * W, 4, 16384)), dim3(256), 0, s, a, (const int32_t*)nullptr, (int64_t)0);
+  if (n_split > 0)
+    hipLaunchKernelGGL(khop_chunks_kernel<true>, dim3(lv_grid(n_split * W, 1, 2048)), dim3(256), 0, s, a, d_split, n_split);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}

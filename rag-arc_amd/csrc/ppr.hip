@@ -36,9 +36,9 @@
 // The last section projects the state through a mention map onto chunks (rarc_ppr_chunks*): its rule, its
 // bounds and its guards are stated there.
 #include "graph_csr.h"
+#include "chunk_ws.h"
 #include "canon_topk.h"
 
-constexpr int PPR_MAX_B = 256;
 constexpr int PPR_MAX_SEEDS = 64;
 constexpr int PPR_MAX_K = 8192;
 constexpr int PPR_VERTEX_PARALLEL_MAX_B = 32;
@@ -504,30 +504,8 @@ extern "C" int rarc_ppr_topk(int64_t n, int64_t m, int nq, int top_k, int cur, v
 // The chunk workspace is {positive counts u32 [256]} | S u64 [n_chunks][B] | keys u64 [B][n_chunks]: the PPR workspace is only
 // read, so stepping — and rarc_ppr_topk — may go on afterwards.
 constexpr int PPR_CHUNK_SPLIT_DEGREE = LV_DEG_WAVE;
-constexpr int PPR_CHUNK_WEIGHT_BITS = 12;
 constexpr int PPR_CHUNK_SCORE_SHIFT = PPR_ONE_SHIFT - PPR_CHUNK_WEIGHT_BITS;
-constexpr int64_t PPR_CHUNK_N_LIMIT = LV_N_LIMIT;             // n_chunks < 2^31 - 1: a chunk id is an int32 in the split list
-constexpr size_t PPR_CHUNK_CTL_BYTES = 1024;                // positive u32 [256]
-
-struct PprChunkWs {
-  uint32_t* positive;
-  u64* s;
-  u64* keys;
-  size_t bytes;
-};
-static inline bool ppr_chunk_shape_ok(int64_t n_chunks, int nq) { return n_chunks >= 1 && n_chunks < PPR_CHUNK_N_LIMIT && nq >= 1 && nq <= PPR_MAX_B; }
-static PprChunkWs ppr_chunk_carve(const void* base, int64_t n_chunks, int nq) {
-  char* b = (char*)base;
-  size_t o = 0;
-  PprChunkWs w;
-  auto take = [&](size_t bytes) { char* p = b + o; o += lv_align(bytes); return p; };
-  w.positive = (uint32_t*)take(PPR_CHUNK_CTL_BYTES);
-  const size_t state = (size_t)n_chunks * (size_t)nq * 8;
-  w.s = (u64*)take(state);
-  w.keys = (u64*)take(state);
-  w.bytes = o;
-  return w;
-}
+// (the workspace is carved by chunk_ws.h, which csrc/khop.hip shares: it writes S from hop levels instead)
 
 struct PprChunkArgs {
   const int64_t* row_ptr;

@@ -338,6 +338,46 @@ class EntityGraph:
         with self.torch.cuda.device(self.device):
             return self._ranked(sd, wd, a, tol, max_iterations, int(top_k), as_device, mentions=mentions)
 
+    # ---------------------------------------------------------------------------------------------------------------- traversal
+    def neighbourhood(self, seeds, hops: int = 2, max_vertices=None, as_device: bool = False, early_stop: bool = False):
+        """The vertices within `hops` edges of each query's seeds, and how far each is (graph_db/neighbourhood.py).
+        seeds: as personalized_pagerank takes them (no weights: a seed has hop 0); a query may have none.  0 <= hops <= 8.
+        -> uint8 [B][n]: hop_q(v), 255 for "not within hops"; or with max_vertices (1 .. 65536) the tuple (ids int64 [B][max],
+        hops int32 [B][max], counts int32 [B], hop_counts int32 [B][hops + 1]): each neighbourhood by (hop ascending, vertex
+        ascending), cut at max_vertices, (-1, -1) past the count; hop_counts[q][h] = the vertices at hop h exactly, never cut.
+        early_stop=True reads one word after every step and stops stepping once no query reached a new vertex: the same answer.
+        ValueError for a seed outside [0, n), more than 64 seeds or negative hops; RarcUnsupported for hops > 8 or
+        max_vertices > 65536."""
+        from . import neighbourhood as K
+
+        return K.neighbourhood(self, seeds, hops=hops, max_vertices=max_vertices, as_device=as_device, early_stop=early_stop)
+
+    def expand(self, index, queries, seeds_per_query: int = 5, hops: int = 2, max_vertices=None, as_device: bool = False,
+               early_stop: bool = False):
+        """neighbourhood for embedded queries: each query's seeds are the index's own top-`seeds_per_query` ids (row i of `index`
+        is the embedding of vertex i), taken on the device — nothing leaves HBM between the search and the traversal."""
+        from . import neighbourhood as K
+
+        return K.expand(self, index, queries, seeds_per_query=seeds_per_query, hops=hops, max_vertices=max_vertices, as_device=as_device,
+                        early_stop=early_stop)
+
+    def neighbourhood_chunks(self, mentions, seeds, hops: int = 2, decay=None, top_k=None, as_device: bool = False, early_stop: bool = False):
+        """neighbourhood, ending in chunks: S(c) = sum over c's mentions (e, w) with hop(e) <= hops of w * decay[hop(e)].
+        decay: hops + 1 integers in [0, 2^16]; by default 4096 >> (2 h), a mention one hop nearer counts four times as much.
+        -> float64 [B][n_chunks] scores (S / 2^28, exact), or with top_k (ids, scores, counts) as rank_chunks returns them:
+        (score descending, chunk ascending), a chunk of score 0 never returned."""
+        from . import neighbourhood as K
+
+        return K.neighbourhood_chunks(self, mentions, seeds, hops=hops, decay=decay, top_k=top_k, as_device=as_device, early_stop=early_stop)
+
+    def expand_chunks(self, index, queries, mentions, seeds_per_query: int = 5, hops: int = 2, decay=None, top_k: int = 10,
+                      as_device: bool = False, early_stop: bool = False):
+        """expand, ending in chunks -> (ids, scores, counts) as neighbourhood_chunks(top_k=top_k)."""
+        from . import neighbourhood as K
+
+        return K.expand_chunks(self, index, queries, mentions, seeds_per_query=seeds_per_query, hops=hops, decay=decay, top_k=top_k,
+                               as_device=as_device, early_stop=early_stop)
+
 
 def personalized_pagerank(n: int, pairs, seeds, weights=None, device: int = 0, **kw):
     """The one-shot form: EntityGraph(n, pairs, weights, device).personalized_pagerank(seeds, **kw)."""

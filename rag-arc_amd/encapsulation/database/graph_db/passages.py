@@ -117,9 +117,9 @@ class MentionMap:
             raise B.RarcUnsupported(f"top_k over n_chunks={self.n_chunks}: the top-k key carries the chunk in 24 bits, n_chunks < 2^24 = "
                                     f"{MAX_TOPK_CHUNKS}; ask for the scores (top_k=None) instead")
 
-    def project(self, n: int, m: int, nq: int, cur: int, ws, top_k):
-        """The tail of one launch batch: the PPR state in `ws` (a device uint8 tensor, rarc_ppr_workspace_bytes) -> device tensors,
-        scores float64 [nq][n_chunks] or (ids, scores, counts)"""
+    def workspace(self, nq: int):
+        """-> (pointer, bytes) of the chunk workspace for a launch batch of nq queries: whoever writes the chunk state S (rarc_ppr_chunks,
+        rarc_khop_chunks) writes it there, and `ranked` reads it"""
         t, lib, nc = self.torch, self.lib, self.n_chunks
         need = int(lib.rarc_ppr_chunks_workspace_bytes(nc, nq))
         if need == 0:
@@ -127,11 +127,29 @@ class MentionMap:
         if self._cws is None or self._cws.numel() < need:
             self._cws = None
             self._cws = t.empty(need, dtype=t.uint8, device=self.device)
-        cws, cb = self._cws.data_ptr(), self._cws.numel()
+        return self._cws.data_ptr(), self._cws.numel()
+
+    def split_list(self):
+        """-> (pointer or None, length) of the list of chunks of more than `split_degree` mentions"""
+        return (self._split.data_ptr() if self._split is not None else None), self.n_split
+
+    def project(self, n: int, m: int, nq: int, cur: int, ws, top_k):
+        """The tail of one launch batch: the PPR state in `ws` (a device uint8 tensor, rarc_ppr_workspace_bytes) -> device tensors,
+        scores float64 [nq][n_chunks] or (ids, scores, counts)"""
+        t, lib, nc = self.torch, self.lib, self.n_chunks
+        cws, cb = self.workspace(nq)
         stream = t.cuda.current_stream(self.device).cuda_stream
+        split, n_split = self.split_list()
         B.check(lib.rarc_ppr_chunks(n, m, nq, cur, ws.data_ptr(), ws.numel(), self._row_ptr.data_ptr(), self._ent.data_ptr(), self._w.data_ptr(),
-                                    nc, self.nnz, self._split.data_ptr() if self._split is not None else None, self.n_split, cws, cb, stream),
+                                    nc, self.nnz, split, n_split, cws, cb, stream),
                 "rarc_ppr_chunks")
+        return self.ranked(nq, top_k)
+
+    def ranked(self, nq: int, top_k):
+        """The chunk state S of the workspace -> device tensors: scores float64 [nq][n_chunks] (S / 2^28), or (ids, scores, counts)"""
+        t, lib, nc = self.torch, self.lib, self.n_chunks
+        cws, cb = self.workspace(nq)
+        stream = t.cuda.current_stream(self.device).cuda_stream
         if top_k is None:
             out = t.empty((nq, nc), dtype=t.float64, device=self.device)
             B.check(lib.rarc_ppr_chunks_scores(nc, nq, cws, cb, out.data_ptr(), stream), "rarc_ppr_chunks_scores")

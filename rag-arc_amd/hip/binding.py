@@ -253,6 +253,15 @@ SIGNATURES = {
     "rarc_ppr_chunks_scores": (c_int, [c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "rarc_ppr_chunks_topk": (c_int, [c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rarc_ppr_chunks_limits": (c_int, [ctypes.POINTER(c_int)]),
+    "rarc_khop_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    "rarc_khop_seed": (c_int, [c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "rarc_khop_step": (c_int, [c_void_p, c_size_t, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "rarc_khop_counts": (c_int, [c_int64, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "rarc_khop_levels": (c_int, [c_int64, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "rarc_khop_list": (c_int, [c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_khop_chunks": (c_int, [c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int64,
+                                 c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "rarc_khop_limits": (c_int, [ctypes.POINTER(c_int)]),
     "rarc_compact_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
     "rarc_vmem_create": (c_int, [c_int, c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_void_p)]),
     "rarc_vmem_grow": (c_int, [c_void_p, c_size_t]),
