@@ -997,6 +997,30 @@ int rarc_khop_chunks(int64_t n, int64_t m, int nq, int hops, const uint32_t* dec
 int rarc_khop_limits(int* out5);
 
 /*
+ * k-hop subgraphs: the relations inside each query's neighbourhood — MATCH (a)-[r]-(b) WHERE a, b IN nodes — from the state
+ * rarc_khop_seed and rarc_khop_step left in d_ws, which is only read: the other k-hop answers follow from the same traversal.
+ * The rule (restated by tests/subgraph_ref.py): d_rel is the CALLER's relation table, int64 [r][2] rows (a, b) in
+ * any orientation; a pair may repeat and a may equal b.  Row e has level max(hop_q(a), hop_q(b)) and belongs to q's subgraph iff
+ * that is <= hops; a row with an end outside [0, n) belongs to none.  The graph's CSR is not read, and the table enters only
+ * through its row numbers, which are what the answer holds.  n, m, nq, hops, d_ws: as the traversal's, refused the same way.
+ * Limits: 1 <= r < 2^31 - 1; 1 <= max_edges <= 65536 (more: RARC_E_UNSUPPORTED); d_rel and the ids 8-byte aligned, the other
+ * outputs 4, the workspaces 256; refused before any launch.
+ *
+ * rarc_khop_edges_workspace_bytes — the size of d_ews, the tile counts of the rows (0 for a refused shape); the k-hop
+ *   workspace and its size do not change.
+ * rarc_khop_edges — d_out_level_counts int32 [nq][hops + 1]: the rows at level h exactly, never capped.  Per query the rows by
+ *   (level ascending, row ascending), the first min(size, max_edges) of them: d_out_ids int64 [nq][max_edges] (row numbers of
+ *   d_rel), d_out_levels int32 [nq][max_edges], d_out_count int32 [nq]; slots past the count hold (-1, -1).  d_out_ids,
+ *   d_out_levels and d_out_count may be null together: then only the level counts are written (no list is placed).
+ * rarc_khop_edges_limits — out2 = {largest max_edges, rows per tile of the count / scan / write passes}.
+ */
+size_t rarc_khop_edges_workspace_bytes(int64_t r, int nq, int hops);
+int rarc_khop_edges(int64_t n, int64_t m, int nq, int hops, const void* d_ws, size_t ws_bytes, const int64_t* d_rel, int64_t r, int max_edges,
+                    void* d_ews, size_t ews_bytes, int64_t* d_out_ids, int32_t* d_out_levels, int32_t* d_out_count,
+                    int32_t* d_out_level_counts, void* stream);
+int rarc_khop_edges_limits(int* out2);
+
+/*
  * Deleting rows of a resident index: stable in-place compaction.  The reference deletes by clearing the index and
  * embedding every surviving text again (encapsulation/database/vector_db/VectorStore_Faiss.py:374-415); the surviving
  * rows are in HBM already, so here they move down over the holes: row i of the result is the i-th surviving row.

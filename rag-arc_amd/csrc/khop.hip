@@ -31,6 +31,11 @@
 //           does: a chunk's range is clamped to [0, nnz], an entry with e outside [0, n) or w outside [1, 2^12) contributes
 //           nothing, a listed chunk outside [0, n_chunks) is skipped, a chunk of more than 64 mentions that the list omits
 //           scores 0.  A lane is a query; the entries of a chunk are loaded once, one per lane, and handed round by readlane.
+//   edges   the relations inside the neighbourhood (tests/subgraph_ref.py restates it): the caller's table of
+//           r rows (a, b), any orientation, repeats and a == b allowed; row e has level max(hop_q(a), hop_q(b)) and is in q's
+//           subgraph iff that is <= hops.  With S_h(x) the OR of levels 0 .. h of x, the rows at level h exactly are
+//           E_h = S_h(a) & S_h(b) & ~(S_{h-1}(a) & S_{h-1}(b)); a row with an end outside [0, n) is in no subgraph.  The same
+//           count / scan / write over tiles of KHOP_TILE rows, the counts in a workspace of their own; the CSR is not read
 //
 // The workspace is {grew u32 | level totals i32 [256][9]} | seen | level 0 .. hops | tile counts u32 [tiles][hops + 1][W * 64].
 #include "graph_csr.h"
@@ -40,9 +45,10 @@ constexpr int KHOP_MAX_HOPS = 8;
 constexpr int KHOP_MAX_B = PPR_MAX_B;
 constexpr int KHOP_MAX_SEEDS = 64;
 constexpr int KHOP_MAX_VERTICES = 65536;
+constexpr int KHOP_MAX_EDGES = 65536;
 constexpr int KHOP_SPLIT_DEGREE = LV_DEG_WAVE;              // a vertex of more neighbours is split across a workgroup
 constexpr int KHOP_GROUP = 16;                              // lanes that share a vertex of up to KHOP_SPLIT_DEGREE neighbours
-constexpr int KHOP_TILE = 1024;                             // vertices a wave counts and writes for the list
+constexpr int KHOP_TILE = 1024;                             // vertices, or relation rows, a wave counts and writes for a list
 constexpr uint32_t KHOP_MAX_DECAY = 1u << 16;
 constexpr size_t KHOP_CTL_BYTES = 256 + (size_t)KHOP_MAX_B * (KHOP_MAX_HOPS + 1) * 4;
 
@@ -82,6 +88,23 @@ static KhopWs khop_carve(const void* base, int64_t n, int nq, int hops) {
   return w;
 }
 static inline u64* khop_level(const KhopWs& w, int h) { return w.level + (lv_align(w.level_words * 8) / 8) * (size_t)h; }
+
+// the edge workspace: level totals i32 [256][9] | tile counts u32 [tiles of r rows][hops + 1][W * 64]
+struct KhopEdgeWs {
+  int32_t* totals;
+  uint32_t* tiles;
+  size_t bytes;
+};
+static inline bool khop_rows_ok(int64_t r) { return r >= 1 && r < LV_N_LIMIT; }
+static KhopEdgeWs khop_edge_carve(const void* base, int64_t r, int nq, int hops) {
+  char* b = (char*)base;
+  KhopEdgeWs w;
+  w.totals = (int32_t*)b;
+  const size_t o = lv_align((size_t)KHOP_MAX_B * (KHOP_MAX_HOPS + 1) * 4);
+  w.tiles = (uint32_t*)(b + o);
+  w.bytes = o + lv_align((size_t)khop_tiles(r) * (size_t)(hops + 1) * khop_words(nq) * 64 * 4);
+  return w;
+}
 
 // the queries of the batch that word `word` holds, as a mask
 __device__ __forceinline__ u64 khop_query_mask(int nq, int word) {
@@ -229,10 +252,87 @@ __global__ __launch_bounds__(256) void khop_tile_scan_kernel(int64_t n_tiles, in
   totals[(size_t)q * H + h] = (int32_t)run;
 }
 
-// a wave per (tile, word): the entries of its vertices, level by level, at offset + rank; block 0 also writes the counts
+// the caller's relation table and the `seen` words of the traversal it is read against
+struct KhopRelations {
+  const int64_t* rows;                                                 // [r][2]
+  const u64* seen;
+  int64_t r;
+};
+
+// the level words of the rows of the relation table: E_h of a row from the cumulative ORs of its two ends.  For most rows
+// seen(a) & seen(b) is 0 and no level is loaded
+struct KhopEdgeBits {
+  const int64_t* __restrict__ rel;
+  const u64* __restrict__ seen;
+  const u64* __restrict__ level;
+  size_t level_stride;
+  int64_t r;
+  int64_t n;
+  // the queries of `word` that reach both ends of row e at all, and where the ends' words lie; 0 for a row past the table or
+  // with an end outside [0, n)
+  __device__ __forceinline__ u64 within(int64_t e, int word, int W, size_t& ia, size_t& ib) const {
+    ia = ib = 0;
+    if (e >= r) return 0ull;
+    const int64_t a = rel[2 * e], b = rel[2 * e + 1];
+    if (a < 0 || a >= n || b < 0 || b >= n) return 0ull;
+    ia = (size_t)a * W + word;
+    ib = (size_t)b * W + word;
+    return seen[ia] & seen[ib];
+  }
+  __device__ __forceinline__ u64 word(int64_t e, int h, int word, int W) const {
+    size_t ia, ib;
+    if (within(e, word, W, ia, ib) == 0) return 0ull;
+    u64 sa = 0, sb = 0;
+    for (int k = 0; k < h; ++k) {
+      sa |= level[level_stride * (size_t)k + ia];
+      sb |= level[level_stride * (size_t)k + ib];
+    }
+    const u64 below = sa & sb;                                         // both ends within h - 1
+    sa |= level[level_stride * (size_t)h + ia];
+    sb |= level[level_stride * (size_t)h + ib];
+    return sa & sb & ~below;
+  }
+};
+
+// a wave per (tile of relation rows, word): every level of a row in one walk up its ends' cumulative ORs;
+// tiles[tile][h][word * 64 + b] = rows of the tile at level h for query word * 64 + b
+__global__ __launch_bounds__(256) void khop_edge_count_kernel(const KhopEdgeBits src, int W, int H, uint32_t* tiles) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t items = khop_tiles(src.r) * W;
+  for (int64_t item = (int64_t)blockIdx.x * 4 + wave; item < items; item += (int64_t)gridDim.x * 4) {
+    const int word = (int)(item % W);
+    const int64_t tile = item / W;
+    uint32_t cnt[KHOP_MAX_HOPS + 1] = {};                              // (indexed by unrolled loops only: registers)
+    for (int c = 0; c < KHOP_TILE / 64; ++c) {
+      size_t ia, ib;
+      const u64 in = src.within(tile * KHOP_TILE + c * 64 + lane, word, W, ia, ib);
+      if (__builtin_amdgcn_ballot_w64(in != 0) == 0) continue;
+      u64 sa = 0, sb = 0, below = 0;
+#pragma unroll
+      for (int h = 0; h <= KHOP_MAX_HOPS; ++h) {
+        if (h < H) {                                                   // (wave-uniform)
+          if (in) {
+            sa |= src.level[src.level_stride * (size_t)h + ia];
+            sb |= src.level[src.level_stride * (size_t)h + ib];
+          }
+          const u64 both = sa & sb;
+          cnt[h] = khop_count_bits(both & ~below, lane, cnt[h]);
+          below = both;
+        }
+      }
+    }
+#pragma unroll
+    for (int h = 0; h <= KHOP_MAX_HOPS; ++h)
+      if (h < H) tiles[((size_t)tile * H + h) * ((size_t)W * 64) + word * 64 + lane] = cnt[h];
+  }
+}
+
+// a wave per (tile, word): the entries of its items, level by level, at offset + rank; block 0 also writes the counts.
+// EDGES: the items are the rows of `rel` and a row's level word is derived from its ends'; otherwise they are the vertices
+template <bool EDGES>
 __global__ __launch_bounds__(256) void khop_list_kernel(const u64* __restrict__ level, size_t level_stride, int64_t n, int W, int H, int nq,
                                                         const uint32_t* __restrict__ tiles, const int32_t* __restrict__ totals, uint32_t max_vertices,
-                                                        int64_t* out_ids, int32_t* out_hops, int32_t* out_count) {
+                                                        int64_t* out_ids, int32_t* out_hops, int32_t* out_count, const KhopRelations rel) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (blockIdx.x == 0) {
     for (int q = threadIdx.x; q < nq; q += 256) {
@@ -242,7 +342,8 @@ __global__ __launch_bounds__(256) void khop_list_kernel(const u64* __restrict__ 
     }
   }
   const u64 below = (1ull << lane) - 1ull;
-  const int64_t items = khop_tiles(n) * W;
+  const KhopEdgeBits rows = {rel.rows, rel.seen, level, level_stride, rel.r, n};
+  const int64_t items = khop_tiles(EDGES ? rel.r : n) * W;
   for (int64_t item = (int64_t)blockIdx.x * 4 + wave; item < items; item += (int64_t)gridDim.x * 4) {
     const int word = (int)(item % W);
     const int64_t tile = item / W;
@@ -260,7 +361,9 @@ __global__ __launch_bounds__(256) void khop_list_kernel(const u64* __restrict__ 
       const u64* lv = level + level_stride * (size_t)h;
       for (int c = 0; c < KHOP_TILE / 64; ++c) {
         const int64_t v = tile * KHOP_TILE + c * 64 + lane;
-        const u64 x = v < n ? lv[(size_t)v * W + word] : 0ull;
+        u64 x;
+        if constexpr (EDGES) x = rows.word(v, h, word, W);
+        else x = v < n ? lv[(size_t)v * W + word] : 0ull;
         if (__builtin_amdgcn_ballot_w64(x != 0) == 0) continue;
         for (int b = 0; b < 64; ++b) {                                 // (b is wave-uniform)
           const bool mine = (x >> b) & 1ull;
@@ -528,9 +631,58 @@ extern "C" int rarc_khop_list(int64_t n, int64_t m, int nq, int hops, int max_ve
   RARC_HIP_CHECK(hipMemsetAsync(d_out_ids, 0xFF, (size_t)nq * max_vertices * 8, s));        // (-1, -1) past the count
   RARC_HIP_CHECK(hipMemsetAsync(d_out_hops, 0xFF, (size_t)nq * max_vertices * 4, s));
   khop_rank(ws, level_stride, n, W, H, nq, s);
-  hipLaunchKernelGGL(khop_list_kernel, dim3(lv_grid(khop_tiles(n) * W, 4, 16384)), dim3(256), 0, s, (const u64*)ws.level, level_stride, n, W, H, nq,
-                     (const uint32_t*)ws.tiles, (const int32_t*)ws.totals, (uint32_t)max_vertices, d_out_ids, d_out_hops, d_out_count);
+  hipLaunchKernelGGL(khop_list_kernel<false>, dim3(lv_grid(khop_tiles(n) * W, 4, 16384)), dim3(256), 0, s, (const u64*)ws.level, level_stride, n, W, H,
+                     nq, (const uint32_t*)ws.tiles, (const int32_t*)ws.totals, (uint32_t)max_vertices, d_out_ids, d_out_hops, d_out_count,
+                     KhopRelations{nullptr, nullptr, 0});
   RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+extern "C" int rarc_khop_edges_limits(int* out2) {
+  RARC_REQUIRE(out2, RARC_E_INVALID, "rarc_khop_edges_limits: null pointer");
+  out2[0] = KHOP_MAX_EDGES;
+  out2[1] = KHOP_TILE;
+  return RARC_OK;
+}
+
+extern "C" size_t rarc_khop_edges_workspace_bytes(int64_t r, int nq, int hops) {
+  if (!khop_rows_ok(r) || nq < 1 || nq > KHOP_MAX_B || hops < 0 || hops > KHOP_MAX_HOPS) return 0;
+  return khop_edge_carve(nullptr, r, nq, hops).bytes;
+}
+
+extern "C" int rarc_khop_edges(int64_t n, int64_t m, int nq, int hops, const void* d_ws, size_t ws_bytes, const int64_t* d_rel, int64_t r,
+                               int max_edges, void* d_ews, size_t ews_bytes, int64_t* d_out_ids, int32_t* d_out_levels, int32_t* d_out_count,
+                               int32_t* d_out_level_counts, void* stream) {
+  RARC_RANGE();
+  const bool listed = d_out_ids || d_out_levels || d_out_count;        // all three, or the level counts alone
+  RARC_REQUIRE(d_ws && d_rel && d_ews && d_out_level_counts && (!listed || (d_out_ids && d_out_levels && d_out_count)), RARC_E_INVALID,
+               "rarc_khop_edges: null pointer");
+  RARC_REQUIRE(KHOP_ALIGNED(d_rel, 8) && KHOP_ALIGNED(d_out_ids, 8) && KHOP_ALIGNED(d_out_levels, 4) && KHOP_ALIGNED(d_out_count, 4) &&
+                   KHOP_ALIGNED(d_out_level_counts, 4),
+               RARC_E_INVALID, "rarc_khop_edges: an array is not aligned to its element (relations and ids 8 bytes, levels and counts 4)");
+  KHOP_SHAPE_CHECKS("rarc_khop_edges");
+  RARC_REQUIRE(khop_rows_ok(r), RARC_E_INVALID, "rarc_khop_edges: r=%lld relation rows out of range (1 <= r < 2^31 - 1)", (long long)r);
+  RARC_REQUIRE(max_edges >= 1, RARC_E_INVALID, "rarc_khop_edges: max_edges=%d out of range (1 <= max_edges <= %d)", max_edges, KHOP_MAX_EDGES);
+  RARC_REQUIRE(max_edges <= KHOP_MAX_EDGES, RARC_E_UNSUPPORTED,
+               "rarc_khop_edges: max_edges=%d: a list holds at most %d relations (the level counts say how many there are)", max_edges,
+               KHOP_MAX_EDGES);
+  RARC_REQUIRE(KHOP_ALIGNED(d_ews, 256), RARC_E_INVALID, "rarc_khop_edges: the edge workspace is not 256-byte aligned");
+  const KhopEdgeWs ews = khop_edge_carve(d_ews, r, nq, hops);
+  RARC_REQUIRE(ews_bytes >= ews.bytes, RARC_E_WORKSPACE, "rarc_khop_edges: edge workspace of %zu bytes, %zu needed", ews_bytes, ews.bytes);
+  hipStream_t s = (hipStream_t)stream;
+  const KhopEdgeBits src = {d_rel, ws.seen, ws.level, level_stride, r, n};
+  const int64_t tiles = khop_tiles(r);
+  hipLaunchKernelGGL(khop_edge_count_kernel, dim3(lv_grid(tiles * W, 4, 16384)), dim3(256), 0, s, src, W, H, ews.tiles);
+  hipLaunchKernelGGL(khop_tile_scan_kernel, dim3((H * nq + 255) / 256), dim3(256), 0, s, tiles, W, H, nq, ews.tiles, ews.totals);
+  if (listed) {
+    RARC_HIP_CHECK(hipMemsetAsync(d_out_ids, 0xFF, (size_t)nq * max_edges * 8, s));            // (-1, -1) past the count
+    RARC_HIP_CHECK(hipMemsetAsync(d_out_levels, 0xFF, (size_t)nq * max_edges * 4, s));
+    hipLaunchKernelGGL(khop_list_kernel<true>, dim3(lv_grid(tiles * W, 4, 16384)), dim3(256), 0, s, (const u64*)ws.level, level_stride, n, W, H, nq,
+                       (const uint32_t*)ews.tiles, (const int32_t*)ews.totals, (uint32_t)max_edges, d_out_ids, d_out_levels, d_out_count,
+                       KhopRelations{d_rel, ws.seen, r});
+  }
+  RARC_HIP_CHECK(hipGetLastError());
+  RARC_HIP_CHECK(hipMemcpyAsync(d_out_level_counts, ews.totals, (size_t)nq * H * 4, hipMemcpyDeviceToDevice, s));
   return RARC_OK;
 }
 

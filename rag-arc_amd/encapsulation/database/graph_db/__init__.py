@@ -6,10 +6,10 @@ build: personalized PageRank from the entities a query links to, pushed through 
 MATCH (s)-[*..h]-(v): the entities within h hops of a query's entities (neighbourhood.py).  The graph database itself is out of
 scope."""
 from .communities import entity_clusters, louvain_communities
-from .neighbourhood import k_hop
+from .neighbourhood import RelationList, k_hop, k_hop_subgraph
 from .pagerank import EntityGraph, personalized_pagerank
 from .passages import MentionMap
 from .similarity import knn_graph, similar_pairs
 
 __all__ = ["similar_pairs", "knn_graph", "louvain_communities", "entity_clusters", "EntityGraph", "personalized_pagerank", "MentionMap",
-           "k_hop"]
+           "k_hop", "k_hop_subgraph", "RelationList"]

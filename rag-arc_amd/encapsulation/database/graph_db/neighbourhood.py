@@ -12,18 +12,24 @@ one bit-parallel multi-source breadth-first search next to the CSR `rarc_graph_c
 
 `EntityGraph.neighbourhood(seeds)` traverses from given seeds, `.expand(index, queries)` takes the seeds from a `FlatIndexF16`
 search without leaving HBM, and `.neighbourhood_chunks` / `.expand_chunks` push the neighbourhood through a `MentionMap` onto
-the chunks a retriever returns, a mention one hop nearer counting four times as much by default.
+the chunks a retriever returns, a mention one hop nearer counting four times as much by default.  `.subgraph` /
+`.neighbourhood_edges` / `.expand_subgraph` add the third thing a local search collects, MATCH (a)-[r]-(b) WHERE a, b IN nodes:
+the rows of a `RelationList` (the caller's typed relations, or the graph's own pairs) whose two ends both lie in the
+neighbourhood, from the same traversal.
 
 The rule is defined in integers (restated by tests/khop_ref.py): the answer is the same bits for any order of the
 edges and any batch, and row q of a batch equals the one-query call.  No CPU fallback: without a device this raises."""
 from __future__ import annotations
 
+import collections
 import ctypes
 
 import numpy as np
 
 from ....hip import binding as B
 
+MAX_LIST_EDGES = 65536         # the longest relation list per query; edge_level_counts is never cut
+MAX_RELATIONS = (1 << 31) - 1  # rows of a relation table: r < 2^31 - 1
 MAX_HOPS = 8                   # levels 0 .. 8 are kept
 MAX_SEEDS = 64                 # seed slots per query
 MAX_BATCH = 256                # queries per launch; larger batches are cut here
@@ -215,6 +221,181 @@ def expand_chunks(graph, index, queries, mentions, seeds_per_query: int = 5, hop
     sd, _ = graph._index_seeds(index, queries, seeds_per_query)
     with graph.torch.cuda.device(graph.device):
         return _batched(graph, sd, as_device, lambda part: _chunks(graph, mentions, part, hops, decay, int(top_k), early_stop))
+
+
+# ---- subgraphs: the relations inside the neighbourhood (restated by tests/subgraph_ref.py) --------------------------------
+def edges_limits() -> dict:
+    """The limits of rarc_khop_edges: the longest list per query, and the rows a tile of its count / scan / write passes holds."""
+    out = (ctypes.c_int * 2)()
+    B.check(B.load_library().rarc_khop_edges_limits(out), "rarc_khop_edges_limits")
+    return {"max_edges": out[0], "tile": out[1]}
+
+
+def check_max_edges(max_edges) -> int:
+    """ValueError for max_edges < 1, RarcUnsupported, naming the limit, above 65536"""
+    if int(max_edges) != max_edges or int(max_edges) < 1:
+        raise ValueError(f"max_edges must be an integer >= 1, got {max_edges!r}")
+    if int(max_edges) > MAX_LIST_EDGES:
+        raise B.RarcUnsupported(f"max_edges={int(max_edges)}: a list holds at most 2^16 = {MAX_LIST_EDGES} relations; edge_level_counts says how "
+                                f"many there are")
+    return int(max_edges)
+
+
+class RelationList:
+    """A relation table over the entities of a graph, resident on the device: r rows (a, b) in any orientation, repeats and
+    a == b allowed.  Nothing is normalised — a subgraph answers in row numbers of this table, where the caller keeps each
+    relation's type and description.  A row with an end outside [0, n_entities) is part of no subgraph.
+    pairs: an [r][2] integer array-like, uploaded once, or an int64 device tensor [r][2], used where it is.
+    weights: one number per row, of any numeric type; only gathered for the rows an answer returns."""
+
+    def __init__(self, n_entities: int, pairs, weights=None, device: int = 0):
+        import torch
+
+        on_device = isinstance(pairs, torch.Tensor) and pairs.is_cuda
+        if on_device:
+            if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int64:
+                raise ValueError(f"expected an int64 [r][2] tensor of relations, got {pairs.dtype} {tuple(pairs.shape)}")
+            r = int(pairs.shape[0])
+        else:
+            arr = np.asarray(pairs.cpu().numpy() if isinstance(pairs, torch.Tensor) else pairs)
+            if arr.ndim != 2 or arr.shape[1] != 2:
+                raise ValueError(f"expected [r][2] relations, got an array of shape {arr.shape}")
+            if not np.issubdtype(arr.dtype, np.integer):
+                raise ValueError(f"relations must be integers, got {arr.dtype}")
+            r = int(arr.shape[0])
+        if r < 1:
+            raise ValueError("a relation list needs at least 1 row")
+        if r >= MAX_RELATIONS:
+            raise B.RarcUnsupported(f"RelationList of {r} rows: the kernels take r < 2^31 - 1")
+        w = None
+        if weights is not None:
+            w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(weights)))
+            if tuple(w.shape) != (r,) or w.dtype == torch.bool or w.is_complex():
+                raise ValueError(f"expected {r} numeric weights, got {w.dtype} {tuple(w.shape)}")
+        if not torch.cuda.is_available():
+            raise B.RarcError("no ROCm device visible: the HIP backend has no CPU fallback")
+        self.n_entities, self.r = int(n_entities), r
+        self.device = torch.device("cuda", device)
+        if on_device and pairs.device != self.device:
+            raise ValueError(f"the relations live on {pairs.device} and device={device} was asked for")
+        with torch.cuda.device(self.device):
+            self._pairs = pairs.contiguous() if on_device else torch.from_numpy(np.ascontiguousarray(arr.astype(np.int64))).to(self.device)
+            self._weights = None if w is None else w.to(self.device)
+
+
+def check_relations(graph, relations):
+    """ValueError for anything but None or a RelationList over the graph's vertices on the graph's device"""
+    if relations is None:
+        return
+    if not isinstance(relations, RelationList):
+        raise ValueError("relations must be a RelationList (or None for the graph's own pair list)")
+    if relations.n_entities != graph.n:
+        raise ValueError(f"the relation list is over {relations.n_entities} entities and the graph has {graph.n} vertices: entity i must be "
+                         f"vertex i")
+    if relations.device != graph.device:
+        raise ValueError(f"the relation list lives on {relations.device} and the graph on {graph.device}")
+
+
+EDGE_FIELDS = ("edge_ids", "edge_ends", "edge_levels", "edge_counts", "edge_level_counts", "edge_weights")
+SubgraphEdges = collections.namedtuple("SubgraphEdges", EDGE_FIELDS, defaults=(None,))
+Subgraph = collections.namedtuple("Subgraph", ("vertex_ids", "vertex_hops", "vertex_counts", "hop_counts") + EDGE_FIELDS, defaults=(None,))
+
+
+def _own_relations(graph):
+    """the graph's own normalised pair list (every pair i < j, once) and its weights, as a RelationList that adopts them"""
+    rel = getattr(graph, "_own_relation_list", None)
+    if rel is None:
+        w = graph._pair_weights
+        w = None if w is None else w.to(graph.torch.int64) & 0xFFFFFFFF                      # (the uint32 weights, kept as their int32 bits)
+        graph._own_relation_list = rel = RelationList(graph.n, graph._pairs, weights=w, device=graph.device.index)
+    return rel
+
+
+def _edges(graph, rel, nq, hops, max_edges, ws, wb):
+    """the relations inside the neighbourhoods the traversal left in (ws, wb) -> device tensors, in the order of EDGE_FIELDS"""
+    t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
+    need = int(lib.rarc_khop_edges_workspace_bytes(rel.r, nq, hops))
+    if need == 0:
+        raise B.RarcError(f"neighbourhood_edges: {rel.r} relations, {nq} queries, hops={hops} refused by rarc_khop_edges_workspace_bytes")
+    ews = getattr(graph, "_khop_ews", None)
+    if ews is None or ews.numel() < need:
+        graph._khop_ews = None
+        graph._khop_ews = ews = t.empty(need, dtype=t.uint8, device=graph.device)
+    ids = t.empty((nq, max_edges), dtype=t.int64, device=graph.device)
+    lv = t.empty((nq, max_edges), dtype=t.int32, device=graph.device)
+    cnt = t.empty(nq, dtype=t.int32, device=graph.device)
+    lc = t.empty((nq, hops + 1), dtype=t.int32, device=graph.device)
+    stream = t.cuda.current_stream(graph.device).cuda_stream
+    B.check(lib.rarc_khop_edges(n, m, nq, hops, ws, wb, rel._pairs.data_ptr(), rel.r, max_edges, ews.data_ptr(), ews.numel(), ids.data_ptr(),
+                                lv.data_ptr(), cnt.data_ptr(), lc.data_ptr(), stream), "rarc_khop_edges")
+    rows = ids.clamp(min=0)                                                                  # the few returned rows: gathered here
+    ends = t.where((ids >= 0).unsqueeze(-1), rel._pairs[rows], t.full_like(rel._pairs[:1], -1))
+    out = (ids, ends, lv, cnt, lc)
+    if rel._weights is not None:
+        out += (t.where(ids >= 0, rel._weights[rows], t.zeros_like(rel._weights[:1])),)
+    return out
+
+
+def _subgraph(graph, rel, sd, hops, max_vertices, max_edges, early_stop):
+    """one launch batch, one traversal -> the vertex list (unless max_vertices is None) followed by the edge list"""
+    t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
+    nq = int(sd.shape[0])
+    ws, wb = traverse(graph, sd, hops, early_stop)
+    if max_vertices is None:
+        return _edges(graph, rel, nq, hops, max_edges, ws, wb)
+    ids = t.empty((nq, max_vertices), dtype=t.int64, device=graph.device)
+    hp = t.empty((nq, max_vertices), dtype=t.int32, device=graph.device)
+    cnt = t.empty(nq, dtype=t.int32, device=graph.device)
+    hc = t.empty((nq, hops + 1), dtype=t.int32, device=graph.device)
+    stream = t.cuda.current_stream(graph.device).cuda_stream
+    B.check(lib.rarc_khop_list(n, m, nq, hops, max_vertices, ws, wb, ids.data_ptr(), hp.data_ptr(), cnt.data_ptr(), stream), "rarc_khop_list")
+    B.check(lib.rarc_khop_counts(n, m, nq, hops, ws, wb, hc.data_ptr(), stream), "rarc_khop_counts")
+    return (ids, hp, cnt, hc) + _edges(graph, rel, nq, hops, max_edges, ws, wb)
+
+
+def neighbourhood_edges(graph, seeds, hops: int = 2, max_edges: int = 16384, relations=None, as_device: bool = False, early_stop: bool = False):
+    hops, max_edges = check_hops(hops), check_max_edges(max_edges)
+    check_relations(graph, relations)
+    with graph.torch.cuda.device(graph.device):
+        rel = _own_relations(graph) if relations is None else relations
+        sd = _device_seeds(graph, seeds)
+        return SubgraphEdges(*_batched(graph, sd, as_device, lambda part: _subgraph(graph, rel, part, hops, None, max_edges, early_stop)))
+
+
+def subgraph(graph, seeds, hops: int = 2, max_vertices: int = 4096, max_edges: int = 16384, relations=None, as_device: bool = False,
+             early_stop: bool = False):
+    hops, max_edges = check_hops(hops, max_vertices), check_max_edges(max_edges)
+    check_relations(graph, relations)
+    with graph.torch.cuda.device(graph.device):
+        rel = _own_relations(graph) if relations is None else relations
+        sd = _device_seeds(graph, seeds)
+        return Subgraph(*_batched(graph, sd, as_device, lambda part: _subgraph(graph, rel, part, hops, int(max_vertices), max_edges, early_stop)))
+
+
+def expand_subgraph(graph, index, queries, seeds_per_query: int = 5, hops: int = 2, max_vertices: int = 4096, max_edges: int = 16384,
+                    relations=None, as_device: bool = False, early_stop: bool = False):
+    hops, max_edges = check_hops(hops, max_vertices), check_max_edges(max_edges)
+    check_relations(graph, relations)
+    graph._check_index(index, seeds_per_query)
+    sd, _ = graph._index_seeds(index, queries, seeds_per_query)
+    with graph.torch.cuda.device(graph.device):
+        rel = _own_relations(graph) if relations is None else relations
+        return Subgraph(*_batched(graph, sd, as_device, lambda part: _subgraph(graph, rel, part, hops, int(max_vertices), max_edges, early_stop)))
+
+
+def k_hop_subgraph(n: int, pairs, seeds, hops: int = 2, device: int = 0, **kw):
+    """The one-shot form: EntityGraph(n, pairs, device=device).subgraph(seeds, hops, **kw).  The arguments are checked before the
+    graph is built: a bad seed, hops, max_vertices, max_edges or relation list raises with no device visible."""
+    from .pagerank import EntityGraph
+
+    check_hops(hops, kw.get("max_vertices", 4096))
+    check_max_edges(kw.get("max_edges", 16384))
+    rel = kw.get("relations")
+    if rel is not None and (not isinstance(rel, RelationList) or rel.n_entities != int(n)):
+        raise ValueError(f"relations must be a RelationList over the graph's {int(n)} vertices (or None for the graph's own pair list)")
+    if not hasattr(seeds, "is_cuda"):
+        host_seeds(int(n), seeds)
+    return EntityGraph(n, pairs, device=device).subgraph(seeds, hops=hops, **kw)
 
 
 def k_hop(n: int, pairs, seeds, hops: int = 2, device: int = 0, **kw):

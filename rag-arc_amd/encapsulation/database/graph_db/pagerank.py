@@ -123,7 +123,8 @@ class EntityGraph:
             stream = torch.cuda.current_stream(self.device).cuda_stream
             B.check(self.lib.rarc_graph_csr(p.data_ptr(), wd.data_ptr() if wd is not None else None, None, n, m, self._graph.data_ptr(),
                                             self._graph.numel(), stream), "rarc_graph_csr")
-            torch.cuda.current_stream(self.device).synchronize()        # (p and wd may be freed: the CSR has its own copy)
+            torch.cuda.current_stream(self.device).synchronize()
+        self._pairs, self._pair_weights = p, wd                         # kept for subgraph(relations=None): 16 bytes an edge
         self._ws = None
 
     # ---------------------------------------------------------------------------------------------------------------- arguments
@@ -377,6 +378,40 @@ class EntityGraph:
 
         return K.expand_chunks(self, index, queries, mentions, seeds_per_query=seeds_per_query, hops=hops, decay=decay, top_k=top_k,
                                as_device=as_device, early_stop=early_stop)
+
+    def subgraph(self, seeds, hops: int = 2, max_vertices: int = 4096, max_edges: int = 16384, relations=None, as_device: bool = False,
+                 early_stop: bool = False):
+        """The neighbourhood and the relations inside it, from one traversal.
+        relations: a RelationList over this graph's vertices — the caller's table, rows (a, b) in any orientation, repeats and
+        a == b allowed — or None for the graph's own normalised pair list.  A row's level is max(hop(a), hop(b)); it is listed
+        iff that is <= hops.
+        -> the named tuple (vertex_ids, vertex_hops, vertex_counts, hop_counts) as neighbourhood(max_vertices=...) returns them,
+        then edge_ids int64 [B][max_edges] (row numbers of the relation list), edge_ends int64 [B][max_edges][2], edge_levels
+        int32 [B][max_edges], edge_counts int32 [B], edge_level_counts int32 [B][hops + 1], and edge_weights [B][max_edges] when
+        the list has weights (0 past the count): each list by (level ascending, row ascending), cut at max_edges (1 .. 65536),
+        -1 past the count; edge_level_counts[q][h] = the rows at level h exactly, never cut.
+        ValueError for max_edges < 1 or a relation list over other entities or on another device; RarcUnsupported for
+        max_edges > 65536."""
+        from . import neighbourhood as K
+
+        return K.subgraph(self, seeds, hops=hops, max_vertices=max_vertices, max_edges=max_edges, relations=relations, as_device=as_device,
+                          early_stop=early_stop)
+
+    def neighbourhood_edges(self, seeds, hops: int = 2, max_edges: int = 16384, relations=None, as_device: bool = False,
+                            early_stop: bool = False):
+        """The edge part of subgraph alone -> the named tuple (edge_ids, edge_ends, edge_levels, edge_counts, edge_level_counts,
+        edge_weights or None)."""
+        from . import neighbourhood as K
+
+        return K.neighbourhood_edges(self, seeds, hops=hops, max_edges=max_edges, relations=relations, as_device=as_device, early_stop=early_stop)
+
+    def expand_subgraph(self, index, queries, seeds_per_query: int = 5, hops: int = 2, max_vertices: int = 4096, max_edges: int = 16384,
+                        relations=None, as_device: bool = False, early_stop: bool = False):
+        """subgraph for embedded queries: the seeds are the index's own top-`seeds_per_query` ids, as expand takes them."""
+        from . import neighbourhood as K
+
+        return K.expand_subgraph(self, index, queries, seeds_per_query=seeds_per_query, hops=hops, max_vertices=max_vertices, max_edges=max_edges,
+                                 relations=relations, as_device=as_device, early_stop=early_stop)
 
 
 def personalized_pagerank(n: int, pairs, seeds, weights=None, device: int = 0, **kw):

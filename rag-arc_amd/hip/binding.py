@@ -262,6 +262,10 @@ SIGNATURES = {
     "rarc_khop_chunks": (c_int, [c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int64,
                                  c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
     "rarc_khop_limits": (c_int, [ctypes.POINTER(c_int)]),
+    "rarc_khop_edges_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "rarc_khop_edges": (c_int, [c_int64, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_khop_edges_limits": (c_int, [ctypes.POINTER(c_int)]),
     "rarc_compact_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
     "rarc_vmem_create": (c_int, [c_int, c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_void_p)]),
     "rarc_vmem_grow": (c_int, [c_void_p, c_size_t]),
