@@ -1021,6 +1021,58 @@ int rarc_khop_edges(int64_t n, int64_t m, int nq, int hops, const void* d_ws, si
 int rarc_khop_edges_limits(int* out2);
 
 /*
+ * Entity merging: step 4 of the reference's de-duplication (Base_Neo4j.py:714-890, _merge_clusters) — every class of a labelling
+ * becomes one entity, and the pair list, the mention CSR and the relation table are contracted onto the survivors without
+ * leaving the device.  The rule (restated by tests/merge_ref.py) is in integers; every result is the same bits for
+ * any order of the pairs and mentions, and from run to run (csrc/merge.hip).  Pointers aligned to their element, workspaces to
+ * 256 bytes, each *_workspace_bytes returning 0 for a refused shape; everything is refused before any launch.
+ *
+ * rarc_sort_reduce — np.unique + bincount: d_keys uint64 [count], of which only the low key_bits bits are used (a higher bit must
+ *   be 0); d_values uint32 [count], or null = every value is 1.  1 <= key_bits <= 62, 1 <= count < 2^31.  d_out_keys uint64
+ *   [count]: the distinct keys ascending; d_out_sums uint64 [count]: the sum of the values of each (64 bits: nothing wraps);
+ *   d_out2 int64 [2] = {distinct keys, largest sum}; slots past the distinct keys are unspecified.  An LSD radix sort over
+ *   ceil(key_bits / 8) passes, stable, then a segmented sum.  The inputs are only read.
+ * rarc_sort_reduce_limits — out4 = {keys per tile, bits per pass, largest key_bits, log2 of the count limit}.
+ * rarc_merge_plan — d_labels int64 [n]: any labelling with values in [0, n) (a label outside makes its vertex a class of its own);
+ *   d_richness uint32 [n] or null (all 0).  1 <= n < 2^31 - 1.  The primary of a class is its member of largest richness, among
+ *   equals the smallest index; the primaries are numbered 0 .. n_c - 1 in ascending index.  d_primary int64 [n]: old -> its
+ *   primary; d_new_id int64 [n]: old -> new; d_kept int64 [n]: its first n_c entries are new -> old; d_removed int64 [n]: its
+ *   first n - n_c entries are the others, ascending; d_out_count int64 [1] = n_c.
+ * rarc_merge_pairs — d_pairs int64 [m][2], d_weights uint32 [m] or null (unit), 1 <= m < 2^31; d_new_id int64 [n] as the plan
+ *   wrote it.  Both ends are mapped; a pair whose ends land on one entity is left out and counted; the others become (min, max),
+ *   equal pairs merge, their weights add.  d_out_pairs int64 [m][2] by (i, j) ascending, d_out_weights uint32 [m] (the low 32
+ *   bits of each sum: the largest sum is reported); d_out5 int64 [5] = {pairs written, largest summed weight, pairs left out,
+ *   their total weight, pairs skipped for an end outside [0, n)}.
+ * rarc_merge_mentions — the CSR by chunk exactly as rarc_ppr_chunks takes it (guarded the same way: ranges clamped to [0, nnz], an
+ *   entity outside [0, n) or a weight of 0 skipped and counted), 1 <= n_chunks < 2^31 - 1, 1 <= nnz < 2^31.  Entities are mapped,
+ *   equal (chunk, entity) merge, their weights add.  d_out_row_ptr int64 [n_chunks + 1], d_out_ent int32 [nnz] (each row by
+ *   entity ascending), d_out_w uint32 [nnz], d_out_split int32 [n_chunks]: the chunks of more than 64 mentions
+ *   (rarc_ppr_chunks_limits), ascending; d_out6 int64 [6] = {mentions written, largest summed weight, 0, 0, mentions skipped,
+ *   chunks in the split list}.  A largest weight >= 2^12 is the caller's to refuse before it uses the result.
+ * rarc_merge_relations — d_rel int64 [r][2] as rarc_khop_edges takes it, 1 <= r < 2^31 - 1.  Rows keep their identity and order:
+ *   a row is left out iff its ends were DIFFERENT entities that land on ONE (a == b stays), or an end lies outside [0, n).
+ *   d_out_rel int64 [r][2]: the mapped ends of the rows that stay; d_out_rows int64 [r]: the old row of each; d_out3 int64 [3] =
+ *   {rows written, rows left out as internal, rows left out for an end out of range}.
+ */
+size_t rarc_sort_reduce_workspace_bytes(int64_t count);
+int rarc_sort_reduce(const uint64_t* d_keys, const uint32_t* d_values, int64_t count, int key_bits, void* d_ws, size_t ws_bytes,
+                     uint64_t* d_out_keys, uint64_t* d_out_sums, int64_t* d_out2, void* stream);
+int rarc_sort_reduce_limits(int* out4);
+size_t rarc_merge_plan_workspace_bytes(int64_t n);
+int rarc_merge_plan(const int64_t* d_labels, const uint32_t* d_richness, int64_t n, void* d_ws, size_t ws_bytes, int64_t* d_primary,
+                    int64_t* d_new_id, int64_t* d_kept, int64_t* d_removed, int64_t* d_out_count, void* stream);
+size_t rarc_merge_pairs_workspace_bytes(int64_t m);
+int rarc_merge_pairs(const int64_t* d_pairs, const uint32_t* d_weights, int64_t m, const int64_t* d_new_id, int64_t n, void* d_ws,
+                     size_t ws_bytes, int64_t* d_out_pairs, uint32_t* d_out_weights, int64_t* d_out5, void* stream);
+size_t rarc_merge_mentions_workspace_bytes(int64_t n_chunks, int64_t nnz);
+int rarc_merge_mentions(const int64_t* d_row_ptr, const int32_t* d_ent, const uint32_t* d_w, int64_t n_chunks, int64_t nnz,
+                        const int64_t* d_new_id, int64_t n, void* d_ws, size_t ws_bytes, int64_t* d_out_row_ptr, int32_t* d_out_ent,
+                        uint32_t* d_out_w, int32_t* d_out_split, int64_t* d_out6, void* stream);
+size_t rarc_merge_relations_workspace_bytes(int64_t r);
+int rarc_merge_relations(const int64_t* d_rel, int64_t r, const int64_t* d_new_id, int64_t n, void* d_ws, size_t ws_bytes,
+                         int64_t* d_out_rel, int64_t* d_out_rows, int64_t* d_out3, void* stream);
+
+/*
  * Deleting rows of a resident index: stable in-place compaction.  The reference deletes by clearing the index and
  * embedding every surviving text again (encapsulation/database/vector_db/VectorStore_Faiss.py:374-415); the surviving
  * rows are in HBM already, so here they move down over the holes: row i of the result is the i-th surviving row.

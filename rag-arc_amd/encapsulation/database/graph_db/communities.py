@@ -156,13 +156,22 @@ def entity_clusters(embeddings, threshold: float = 0.95, max_iterations: int = 1
     indices, each ascending, only those of at least min_size rows, ordered by size descending and then by smallest member.
     as_labels=True returns labels int64 [n] instead (labels[i] = the smallest row of i's community).
     embeddings: [n][d] array-like of floats or a torch tensor (used where it is).  The pairs never leave the device."""
+    min_size = int(min_size)
+    if int(max_iterations) >= 1 and int(max_levels) >= 1 and min_size < 1:
+        raise ValueError("min_size must be at least 1")
+    n, labels = _embedding_labels(embeddings, threshold, max_iterations, max_levels, device)
+    labels = np.arange(n, dtype=np.int64) if labels is None else labels.cpu().numpy()
+    return labels if as_labels else clusters_of(labels, min_size)
+
+
+def _embedding_labels(embeddings, threshold, max_iterations, max_levels, device):
+    """entity_clusters up to the labels -> (n, labels int64 [n] on the device, or None where nothing was clustered: fewer than 2
+    rows, or no pair reached the threshold); `deduplicate_entities` goes on from them where they are"""
     import torch
 
-    max_iterations, max_levels, min_size = int(max_iterations), int(max_levels), int(min_size)
+    max_iterations, max_levels = int(max_iterations), int(max_levels)
     if max_iterations < 1 or max_levels < 1:
         raise ValueError("max_iterations and max_levels must be at least 1")
-    if min_size < 1:
-        raise ValueError("min_size must be at least 1")
     if not 0.0 < float(threshold) <= 1.0:
         raise ValueError("threshold must lie in (0, 1]")
     if not torch.cuda.is_available():
@@ -175,7 +184,7 @@ def entity_clusters(embeddings, threshold: float = 0.95, max_iterations: int = 1
         arr = np.asarray(embeddings, dtype=np.float32)
         if arr.ndim != 2:
             if arr.size == 0:
-                return np.zeros(0, np.int64) if as_labels else []
+                return 0, None
             raise ValueError(f"expected [n][d] embeddings, got an array of shape {arr.shape}")
         x = torch.from_numpy(np.ascontiguousarray(arr)).to(dev)
     if x.ndim != 2:
@@ -183,11 +192,10 @@ def entity_clusters(embeddings, threshold: float = 0.95, max_iterations: int = 1
     n, d = int(x.shape[0]), int(x.shape[1])
     if n >= 2 and not 1 <= d <= S.MAX_DIM:
         raise B.RarcError(f"embeddings of {d} dimensions: the all-pairs kernel takes 1..{S.MAX_DIM}")
-    labels = np.arange(n, dtype=np.int64)
     if n >= 2:
         with torch.cuda.device(dev):
             pairs, _, found = S._pairs_on_device(lib, x.contiguous(), float(threshold), dev)
             _check_counts(n, found, max_iterations, max_levels)
             if found:
-                labels = _cluster_on_device(lib, pairs, n, found, max_iterations, max_levels, dev).cpu().numpy()
-    return labels if as_labels else clusters_of(labels, min_size)
+                return n, _cluster_on_device(lib, pairs, n, found, max_iterations, max_levels, dev)
+    return n, None

@@ -127,6 +127,53 @@ class EntityGraph:
         self._pairs, self._pair_weights = p, wd                         # kept for subgraph(relations=None): 16 bytes an edge
         self._ws = None
 
+    @classmethod
+    def from_device(cls, n: int, pairs, weights=None):
+        """Adopts buffers that are on a device already (graph_db/merge.py builds a merged graph this way): `pairs` an int64 device
+        tensor [m][2], every pair 0 <= i < j < n, each once, and `weights` None (unit) or a device tensor [m] of int32 holding
+        uint32 bits (what rarc_merge_pairs writes), each >= 1.  Nothing passes through the host but the two words of the checks:
+        the same limits as the constructor's, refused the same way."""
+        import torch
+
+        n = int(n)
+        if not (isinstance(pairs, torch.Tensor) and pairs.is_cuda and pairs.ndim == 2 and pairs.shape[1] == 2 and pairs.dtype == torch.int64):
+            raise ValueError("expected an int64 [m][2] device tensor of pairs")
+        m = int(pairs.shape[0])
+        if weights is not None and not (isinstance(weights, torch.Tensor) and weights.device == pairs.device and weights.dtype == torch.int32
+                                        and tuple(weights.shape) == (m,)):
+            raise ValueError(f"edge weights must be an int32 device tensor [{m}] (uint32 bits) beside the pairs")
+        if n < 2:
+            raise ValueError("a graph needs at least 2 vertices")
+        if m < 1:
+            raise ValueError("a graph needs at least 1 edge")
+        if m >= MAX_EDGES or n >= MAX_VERTICES:
+            raise B.RarcUnsupported(f"EntityGraph(n={n}, {m} edges): the kernels take n < 2^31 - 1 vertices and m < 2^30 edges")
+        self = cls.__new__(cls)
+        self.torch, self.lib = torch, B.load_library()
+        self.n, self.m = n, m
+        self.device = pairs.device
+        with torch.cuda.device(self.device):
+            p = pairs.contiguous()
+            wd = None if weights is None else weights.contiguous()
+            ok = ((p[:, 0] >= 0) & (p[:, 0] < p[:, 1]) & (p[:, 1] < n)).all()
+            total = torch.tensor(m, device=self.device) if wd is None else (wd.to(torch.int64) & 0xFFFFFFFF).sum()
+            least = torch.tensor(1, device=self.device) if wd is None else (wd.to(torch.int64) & 0xFFFFFFFF).min()
+            ok, total, least = torch.stack([ok.to(torch.int64), total, least]).tolist()
+            if not ok:
+                raise ValueError(f"device pairs must satisfy 0 <= i < j < {n}")
+            if least < 1:
+                raise ValueError("edge weights must be integers in [1, 2^32)")
+            if total >= MAX_TOTAL_WEIGHT:
+                raise B.RarcUnsupported("the total edge weight must stay below 2^31 (every weighted degree then fits 32 bits)")
+            self._graph = torch.empty(int(self.lib.rarc_graph_csr_workspace_bytes(n, m)), dtype=torch.uint8, device=self.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            B.check(self.lib.rarc_graph_csr(p.data_ptr(), wd.data_ptr() if wd is not None else None, None, n, m, self._graph.data_ptr(),
+                                            self._graph.numel(), stream), "rarc_graph_csr")
+            torch.cuda.current_stream(self.device).synchronize()
+        self._pairs, self._pair_weights = p, wd
+        self._ws = None
+        return self
+
     # ---------------------------------------------------------------------------------------------------------------- arguments
     @staticmethod
     def _check_run(damping, max_iterations, tolerance, top_k, n):

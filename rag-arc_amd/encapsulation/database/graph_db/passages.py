@@ -108,6 +108,41 @@ class MentionMap:
         self.n_split = int(split.size)
         self._cws = None
 
+    @classmethod
+    def from_device_csr(cls, n_chunks: int, n_entities: int, row_ptr, entities, weights, split=None):
+        """Adopts a CSR that is on a device already, in the form `mention_csr` produces (graph_db/merge.py builds a merged map
+        this way): row_ptr int64 [n_chunks + 1], entities int32 [nnz] (each row ascending, no repeats), weights int32 [nnz]
+        holding uint32 bits in [1, 2^12), split int32: the chunks of more than `split_degree` mentions, or None for none.  The
+        producer answers for the contents; the kernels guard every index they read either way."""
+        import torch
+
+        n_chunks, n_entities = int(n_chunks), int(n_entities)
+        if n_chunks < 1:
+            raise ValueError("a mention map needs at least 1 chunk")
+        if n_chunks >= MAX_CHUNKS:
+            raise B.RarcUnsupported(f"MentionMap(n_chunks={n_chunks}): the kernels take n_chunks < 2^31 - 1")
+        if n_entities < 1:
+            raise ValueError("a mention map needs at least 1 entity")
+        nnz = int(entities.shape[0]) if isinstance(entities, torch.Tensor) and entities.ndim == 1 else None
+        want = ((row_ptr, torch.int64, n_chunks + 1), (entities, torch.int32, nnz), (weights, torch.int32, nnz))
+        for x, dtype, length in want + (((split, torch.int32, None),) if split is not None else ()):
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.device == row_ptr.device and x.ndim == 1 and x.dtype == dtype
+                    and (length is None or int(x.shape[0]) == length)):
+                raise ValueError("expected device tensors on one device: row_ptr int64 [n_chunks + 1], entities int32 [nnz], weights "
+                                 "int32 [nnz], split int32")
+        if int(entities.shape[0]) < 1:
+            raise ValueError("a mention map needs at least 1 mention (nnz >= 1)")
+        self = cls.__new__(cls)
+        self.torch, self.lib = torch, B.load_library()
+        self.n_chunks, self.n_entities, self.nnz = n_chunks, n_entities, int(entities.shape[0])
+        self.split_degree = limits()["split_degree"]
+        self.device = row_ptr.device
+        self._row_ptr, self._ent, self._w = row_ptr.contiguous(), entities.contiguous(), weights.contiguous()
+        self.n_split = 0 if split is None else int(split.shape[0])
+        self._split = split.contiguous() if self.n_split else None
+        self._cws = None
+        return self
+
     def check_top_k(self, top_k) -> None:
         if top_k is None:
             return

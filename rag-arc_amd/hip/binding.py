@@ -266,6 +266,18 @@ SIGNATURES = {
     "rarc_khop_edges": (c_int, [c_int64, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "rarc_khop_edges_limits": (c_int, [ctypes.POINTER(c_int)]),
+    "rarc_sort_reduce_workspace_bytes": (c_size_t, [c_int64]),
+    "rarc_sort_reduce": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_sort_reduce_limits": (c_int, [ctypes.POINTER(c_int)]),
+    "rarc_merge_plan_workspace_bytes": (c_size_t, [c_int64]),
+    "rarc_merge_plan": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_merge_pairs_workspace_bytes": (c_size_t, [c_int64]),
+    "rarc_merge_pairs": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_merge_mentions_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "rarc_merge_mentions": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_merge_relations_workspace_bytes": (c_size_t, [c_int64]),
+    "rarc_merge_relations": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rarc_compact_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
     "rarc_vmem_create": (c_int, [c_int, c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_void_p)]),
     "rarc_vmem_grow": (c_int, [c_void_p, c_size_t]),
