@@ -1021,6 +1021,35 @@ int rarc_khop_edges(int64_t n, int64_t m, int nq, int hops, const void* d_ws, si
 int rarc_khop_edges_limits(int* out2);
 
 /*
+ * Connecting paths: how the sources of one traversal are joined — MATCH p = allShortestPaths((a)-[*..L]-(b)) — from the state
+ * rarc_khop_seed and rarc_khop_step left in d_ws for ns sources stepped to hops = max_length, which is only read.  The rule
+ * (restated by tests/paths_ref.py): a source is a seed set as rarc_khop_seed takes it; for a pair p = (ia, ib) of
+ * source indices d_p = min over v of hop_ia(v) + hop_ib(v), and -1 where no vertex gives a value <= max_length or an index lies
+ * outside [0, ns); v is on p's paths at position i iff hop_ia(v) == i and hop_ib(v) == d_p - i.  ia == ib is allowed and a pair
+ * may repeat.  Every join is an AND, an OR, an integer min or count: the same bits for any order of the edges and any batch, and
+ * row p of a batch equals the one-pair call (csrc/khop.hip).
+ * Limits: n, m as the traversal's, 1 <= ns <= 256, 1 <= np <= 256, 0 <= max_length <= 8 (more: RARC_E_UNSUPPORTED); d_pairs and
+ * the distances 4-byte aligned, the workspaces 256; refused before any launch.
+ *
+ * rarc_khop_paths — d_pairs int32 [np][2] on the device; d_out_dist int32 [np] receives d_p.  d_pws, of
+ *   rarc_khop_workspace_bytes(n, m, np, max_length) bytes, becomes a k-hop state of np columns whose level i holds the vertices
+ *   at position i: rarc_khop_counts, rarc_khop_levels, rarc_khop_list and rarc_khop_chunks read it with nq = np and
+ *   hops = max_length, positions in the place of hops.
+ * rarc_khop_path_edges — the arguments, outputs and limits of rarc_khop_edges, d_ws being the PATH state and nq = np: a row
+ *   (a, b) of d_rel is at level i + 1 iff one end is on the pair's paths at position i and the other at position i + 1.  A row
+ *   between two vertices of one position, a row with a == b and a row with an end outside [0, n) are at no level; level 0 is
+ *   empty.  The table is trusted as it is for subgraphs: the CSR is not read.  d_ews: rarc_khop_edges_workspace_bytes(r, np,
+ *   max_length) bytes.
+ * rarc_khop_paths_limits — out3 = {largest max_length, largest ns, largest np}.
+ */
+int rarc_khop_paths(int64_t n, int64_t m, int ns, int np, int max_length, const void* d_ws, size_t ws_bytes, const int32_t* d_pairs,
+                    void* d_pws, size_t pws_bytes, int32_t* d_out_dist, void* stream);
+int rarc_khop_path_edges(int64_t n, int64_t m, int nq, int hops, const void* d_ws, size_t ws_bytes, const int64_t* d_rel, int64_t r,
+                         int max_edges, void* d_ews, size_t ews_bytes, int64_t* d_out_ids, int32_t* d_out_levels, int32_t* d_out_count,
+                         int32_t* d_out_level_counts, void* stream);
+int rarc_khop_paths_limits(int* out3);
+
+/*
  * Entity merging: step 4 of the reference's de-duplication (Base_Neo4j.py:714-890, _merge_clusters) — every class of a labelling
  * becomes one entity, and the pair list, the mention CSR and the relation table are contracted onto the survivors without
  * leaving the device.  The rule (restated by tests/merge_ref.py) is in integers; every result is the same bits for

@@ -37,6 +37,18 @@
 //           E_h = S_h(a) & S_h(b) & ~(S_{h-1}(a) & S_{h-1}(b)); a row with an end outside [0, n) is in no subgraph.  The same
 //           count / scan / write over tiles of KHOP_TILE rows, the counts in a workspace of their own; the CSR is not read
 //
+// Connecting paths (tests/paths_ref.py restates it): allShortestPaths between the sources of one traversal.  For a
+// pair p = (A, B) of its columns, d_p = min over v of hop_A(v) + hop_B(v) and v is on p's paths at position i iff hop_A(v) == i
+// and hop_B(v) == d_p - i.  The answer is written as a k-hop state of its own, a column a pair and a level a position, so every
+// reader above (counts, levels, list, chunks) takes it unchanged.
+//   dist        an integer atomicMin per pair of hop_A over the vertices that hold B's bit at level 0; 0xFFFFFFFF = -1 stays
+//               where nothing within the bound joins the two, or a pair names no column
+//   mark        a wave per vertex, a lane a pair: the vertex's (hops + 1) x W level words are loaded once, one per lane, and
+//               handed round by shuffles; the words of the path state are assembled with ballots.  The two columns of a pair
+//               sit at any bit of any word, so this is a test per pair, not an AND of words
+//   path edges  row (a, b) is at level i + 1 iff one end is at position i and the other at i + 1 — on the path state the two
+//               ends share a word, E_{i+1} = P_i(a) & P_{i+1}(b) | P_{i+1}(a) & P_i(b) — through the count / scan / write of `edges`
+//
 // The workspace is {grew u32 | level totals i32 [256][9]} | seen | level 0 .. hops | tile counts u32 [tiles][hops + 1][W * 64].
 #include "graph_csr.h"
 #include "chunk_ws.h"
@@ -279,9 +291,16 @@ struct KhopEdgeBits {
     ib = (size_t)b * W + word;
     return seen[ia] & seen[ib];
   }
+  template <bool PATHS>
   __device__ __forceinline__ u64 word(int64_t e, int h, int word, int W) const {
     size_t ia, ib;
     if (within(e, word, W, ia, ib) == 0) return 0ull;
+    if constexpr (PATHS) {                                             // consecutive positions, either way round
+      if (h == 0) return 0ull;
+      const u64* lo = level + level_stride * (size_t)(h - 1);
+      const u64* hi = level + level_stride * (size_t)h;
+      return (lo[ia] & hi[ib]) | (hi[ia] & lo[ib]);
+    }
     u64 sa = 0, sb = 0;
     for (int k = 0; k < h; ++k) {
       sa |= level[level_stride * (size_t)k + ia];
@@ -294,8 +313,30 @@ struct KhopEdgeBits {
   }
 };
 
-// a wave per (tile of relation rows, word): every level of a row in one walk up its ends' cumulative ORs;
+// a row's level words, level by level, from the words of its two ends.  Subgraphs: both ends within h and not both within
+// h - 1.  PATHS: one end at position h - 1 and the other at h
+template <bool PATHS>
+struct KhopRowWalk {
+  u64 a = 0, b = 0, below = 0;
+  __device__ __forceinline__ u64 next(u64 xa, u64 xb) {
+    if constexpr (PATHS) {
+      const u64 e = (a & xb) | (xa & b);
+      a = xa;
+      b = xb;
+      return e;
+    } else {
+      a |= xa;
+      b |= xb;
+      const u64 both = a & b, e = both & ~below;
+      below = both;
+      return e;
+    }
+  }
+};
+
+// a wave per (tile of relation rows, word): every level of a row in one walk up its ends' words;
 // tiles[tile][h][word * 64 + b] = rows of the tile at level h for query word * 64 + b
+template <bool PATHS>
 __global__ __launch_bounds__(256) void khop_edge_count_kernel(const KhopEdgeBits src, int W, int H, uint32_t* tiles) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t items = khop_tiles(src.r) * W;
@@ -307,17 +348,16 @@ __global__ __launch_bounds__(256) void khop_edge_count_kernel(const KhopEdgeBits
       size_t ia, ib;
       const u64 in = src.within(tile * KHOP_TILE + c * 64 + lane, word, W, ia, ib);
       if (__builtin_amdgcn_ballot_w64(in != 0) == 0) continue;
-      u64 sa = 0, sb = 0, below = 0;
+      KhopRowWalk<PATHS> walk;
 #pragma unroll
       for (int h = 0; h <= KHOP_MAX_HOPS; ++h) {
         if (h < H) {                                                   // (wave-uniform)
+          u64 xa = 0, xb = 0;
           if (in) {
-            sa |= src.level[src.level_stride * (size_t)h + ia];
-            sb |= src.level[src.level_stride * (size_t)h + ib];
+            xa = src.level[src.level_stride * (size_t)h + ia];
+            xb = src.level[src.level_stride * (size_t)h + ib];
           }
-          const u64 both = sa & sb;
-          cnt[h] = khop_count_bits(both & ~below, lane, cnt[h]);
-          below = both;
+          cnt[h] = khop_count_bits(walk.next(xa, xb), lane, cnt[h]);
         }
       }
     }
@@ -328,8 +368,9 @@ __global__ __launch_bounds__(256) void khop_edge_count_kernel(const KhopEdgeBits
 }
 
 // a wave per (tile, word): the entries of its items, level by level, at offset + rank; block 0 also writes the counts.
-// EDGES: the items are the rows of `rel` and a row's level word is derived from its ends'; otherwise they are the vertices
-template <bool EDGES>
+// EDGES: the items are the rows of `rel` and a row's level word is derived from its ends' (PATHS: by the rule of the connecting
+// paths); otherwise they are the vertices
+template <bool EDGES, bool PATHS = false>
 __global__ __launch_bounds__(256) void khop_list_kernel(const u64* __restrict__ level, size_t level_stride, int64_t n, int W, int H, int nq,
                                                         const uint32_t* __restrict__ tiles, const int32_t* __restrict__ totals, uint32_t max_vertices,
                                                         int64_t* out_ids, int32_t* out_hops, int32_t* out_count, const KhopRelations rel) {
@@ -362,7 +403,7 @@ __global__ __launch_bounds__(256) void khop_list_kernel(const u64* __restrict__ 
       for (int c = 0; c < KHOP_TILE / 64; ++c) {
         const int64_t v = tile * KHOP_TILE + c * 64 + lane;
         u64 x;
-        if constexpr (EDGES) x = rows.word(v, h, word, W);
+        if constexpr (EDGES) x = rows.template word<PATHS>(v, h, word, W);
         else x = v < n ? lv[(size_t)v * W + word] : 0ull;
         if (__builtin_amdgcn_ballot_w64(x != 0) == 0) continue;
         for (int b = 0; b < 64; ++b) {                                 // (b is wave-uniform)
@@ -490,6 +531,111 @@ __global__ __launch_bounds__(256) void khop_chunks_kernel(const KhopChunkArgs a,
       __syncthreads();
     }
     if (q < a.nq && (!SPLIT || wave == 0)) a.s[(size_t)c * a.nq + q] = acc;     // (a chunk left to the SPLIT launch: 0 until that overwrites it)
+  }
+}
+
+// ---- connecting paths ---------------------------------------------------------------------------------------------------------------
+// a thread per vertex: one that holds a level-0 bit of the traversal is an end of some source; for every pair whose B it ends,
+// its hop from A lowers the pair's distance.  A pair that names no column is skipped and keeps 0xFFFFFFFF.  The pairs are
+// staged in LDS once a workgroup (ia | ib << 8, or -1): an end of many sources walks them there, not in global memory
+__global__ __launch_bounds__(256) void khop_path_dist_kernel(const u64* __restrict__ level, size_t level_stride, int64_t n, int W, int H, int ns,
+                                                             const int32_t* __restrict__ pairs, int np, uint32_t* dist) {
+  static_assert(KHOP_MAX_B == 256, "one thread of the workgroup stages one pair");
+  __shared__ int32_t s_pair[KHOP_MAX_B];
+  int code = -1;
+  if ((int)threadIdx.x < np) {
+    const int ia = pairs[2 * threadIdx.x], ib = pairs[2 * threadIdx.x + 1];
+    if (ia >= 0 && ia < ns && ib >= 0 && ib < ns) code = ia | ib << 8;
+  }
+  s_pair[threadIdx.x] = code;
+  __syncthreads();
+  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (int64_t)gridDim.x * 256) {
+    const u64* at = level + (size_t)v * W;
+    u64 ends = 0;
+    for (int w = 0; w < W; ++w) ends |= at[w];
+    if (!ends) continue;
+    for (int p = 0; p < np; ++p) {
+      const int c = s_pair[p];
+      if (c < 0) continue;
+      const int ia = c & 255, ib = c >> 8;
+      if (!((at[ib >> 6] >> (ib & 63)) & 1ull)) continue;
+      for (int h = 0; h < H; ++h) {
+        if ((at[level_stride * (size_t)h + (ia >> 6)] >> (ia & 63)) & 1ull) {
+          atomicMin(&dist[p], (uint32_t)h);
+          break;
+        }
+      }
+    }
+  }
+}
+
+struct KhopPathArgs {
+  const u64* seen;                                                     // the traversal: ns columns, W words a vertex
+  const u64* level;
+  u64* pseen;                                                          // the path state: np columns, PW words a vertex
+  u64* plevel;
+  const int32_t* pairs;
+  const int32_t* dist;
+  size_t level_stride;
+  size_t plevel_stride;
+  int64_t n;
+  int W;
+  int PW;
+  int H;
+  int ns;
+  int np;
+};
+
+// a wave per vertex, a lane a pair, of each of the PW words of pairs in turn (the pairs are staged in LDS once a workgroup).
+// Lane k < H * W holds word k % W of level k / W of the vertex, and lane k < (H + 1) * PW collects word k % PW of the path
+// state's seen (k / PW == 0) or of position k / PW - 1.  The levels of a (vertex, column) are disjoint: hop_A is the one level
+// that holds A's bit, and B is looked up at d - hop_A alone
+__global__ __launch_bounds__(256) void khop_path_mark_kernel(const KhopPathArgs a) {
+  static_assert(KHOP_MAX_B == 256, "one thread of the workgroup stages one pair");
+  __shared__ int32_t s_code[KHOP_MAX_B];                               // ia | ib << 8 | d << 16 of a pair, or -1 for one without paths
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int W = a.W, PW = a.PW, H = a.H;
+  int code = -1;
+  if ((int)threadIdx.x < a.np) {
+    const int ia = a.pairs[2 * threadIdx.x], ib = a.pairs[2 * threadIdx.x + 1], d = a.dist[threadIdx.x];
+    if (ia >= 0 && ia < a.ns && ib >= 0 && ib < a.ns && d >= 0 && d < H) code = ia | ib << 8 | d << 16;
+  }
+  s_code[threadIdx.x] = code;
+  __syncthreads();
+  const bool loads = lane < H * W, stores = lane < (H + 1) * PW;
+  const size_t src = loads ? a.level_stride * (size_t)(lane / W) + (size_t)(lane % W) : 0;
+  u64* const dst = !stores ? nullptr : (lane < PW ? a.pseen + lane : a.plevel + a.plevel_stride * (size_t)(lane / PW - 1) + lane % PW);
+  for (int64_t v = (int64_t)blockIdx.x * 4 + wave; v < a.n; v += (int64_t)gridDim.x * 4) {     // (v is wave-uniform)
+    const u64 sv = lane < W ? a.seen[(size_t)v * W + lane] : 0ull;
+    u64 out = 0;
+    if (__builtin_amdgcn_ballot_w64(sv != 0) != 0) {                   // a vertex no source reached: zeros, its levels unread
+      const u64 x = loads ? a.level[src + (size_t)v * W] : 0ull;
+      for (int wp = 0; wp < PW; ++wp) {                                // (wave-uniform: every lane takes part in every shuffle)
+        const int c = s_code[wp * 64 + lane];
+        const int ia = c < 0 ? 0 : c & 255, ib = c < 0 ? 0 : (c >> 8) & 255, d = c >> 16;
+        int pos = -1;
+#pragma unroll
+        for (int h = 0; h <= KHOP_MAX_HOPS; ++h) {
+          if (h < H) {
+            const u64 xa = (u64)__shfl((long long)x, h * W + (ia >> 6), 64);
+            pos = ((xa >> (ia & 63)) & 1ull) ? h : pos;
+          }
+        }
+        const bool both = c >= 0 && pos >= 0 && pos <= d;
+        const u64 xb = (u64)__shfl((long long)x, (both ? d - pos : 0) * W + (ib >> 6), 64);
+        pos = both && ((xb >> (ib & 63)) & 1ull) ? pos : -1;
+        const u64 on = __builtin_amdgcn_ballot_w64(pos >= 0);
+        out = lane == wp ? on : out;
+#pragma unroll
+        for (int i = 0; i <= KHOP_MAX_HOPS; ++i) {
+          if (i < H) {
+            const u64 at = __builtin_amdgcn_ballot_w64(pos == i);
+            out = lane == (i + 1) * PW + wp ? at : out;
+          }
+        }
+      }
+    }
+    if (stores) dst[(size_t)v * PW] = out;
   }
 }
 
@@ -650,40 +796,107 @@ extern "C" size_t rarc_khop_edges_workspace_bytes(int64_t r, int nq, int hops) {
   return khop_edge_carve(nullptr, r, nq, hops).bytes;
 }
 
-extern "C" int rarc_khop_edges(int64_t n, int64_t m, int nq, int hops, const void* d_ws, size_t ws_bytes, const int64_t* d_rel, int64_t r,
-                               int max_edges, void* d_ews, size_t ews_bytes, int64_t* d_out_ids, int32_t* d_out_levels, int32_t* d_out_count,
-                               int32_t* d_out_level_counts, void* stream) {
-  RARC_RANGE();
-  const bool listed = d_out_ids || d_out_levels || d_out_count;        // all three, or the level counts alone
-  RARC_REQUIRE(d_ws && d_rel && d_ews && d_out_level_counts && (!listed || (d_out_ids && d_out_levels && d_out_count)), RARC_E_INVALID,
-               "rarc_khop_edges: null pointer");
-  RARC_REQUIRE(KHOP_ALIGNED(d_rel, 8) && KHOP_ALIGNED(d_out_ids, 8) && KHOP_ALIGNED(d_out_levels, 4) && KHOP_ALIGNED(d_out_count, 4) &&
-                   KHOP_ALIGNED(d_out_level_counts, 4),
-               RARC_E_INVALID, "rarc_khop_edges: an array is not aligned to its element (relations and ids 8 bytes, levels and counts 4)");
-  KHOP_SHAPE_CHECKS("rarc_khop_edges");
-  RARC_REQUIRE(khop_rows_ok(r), RARC_E_INVALID, "rarc_khop_edges: r=%lld relation rows out of range (1 <= r < 2^31 - 1)", (long long)r);
-  RARC_REQUIRE(max_edges >= 1, RARC_E_INVALID, "rarc_khop_edges: max_edges=%d out of range (1 <= max_edges <= %d)", max_edges, KHOP_MAX_EDGES);
-  RARC_REQUIRE(max_edges <= KHOP_MAX_EDGES, RARC_E_UNSUPPORTED,
-               "rarc_khop_edges: max_edges=%d: a list holds at most %d relations (the level counts say how many there are)", max_edges,
-               KHOP_MAX_EDGES);
-  RARC_REQUIRE(KHOP_ALIGNED(d_ews, 256), RARC_E_INVALID, "rarc_khop_edges: the edge workspace is not 256-byte aligned");
-  const KhopEdgeWs ews = khop_edge_carve(d_ews, r, nq, hops);
-  RARC_REQUIRE(ews_bytes >= ews.bytes, RARC_E_WORKSPACE, "rarc_khop_edges: edge workspace of %zu bytes, %zu needed", ews_bytes, ews.bytes);
-  hipStream_t s = (hipStream_t)stream;
+// the arguments of rarc_khop_edges and rarc_khop_path_edges, which are the same: leaves `ws`, `ews`, W, H, level_stride and `listed`
+#define KHOP_EDGE_CHECKS(NAME)                                                                                                           \
+  const bool listed = d_out_ids || d_out_levels || d_out_count; /* all three, or the level counts alone */                               \
+  RARC_REQUIRE(d_ws && d_rel && d_ews && d_out_level_counts && (!listed || (d_out_ids && d_out_levels && d_out_count)), RARC_E_INVALID,  \
+               NAME ": null pointer");                                                                                                   \
+  RARC_REQUIRE(KHOP_ALIGNED(d_rel, 8) && KHOP_ALIGNED(d_out_ids, 8) && KHOP_ALIGNED(d_out_levels, 4) && KHOP_ALIGNED(d_out_count, 4) &&  \
+                   KHOP_ALIGNED(d_out_level_counts, 4),                                                                                  \
+               RARC_E_INVALID, NAME ": an array is not aligned to its element (relations and ids 8 bytes, levels and counts 4)");        \
+  KHOP_SHAPE_CHECKS(NAME);                                                                                                               \
+  RARC_REQUIRE(khop_rows_ok(r), RARC_E_INVALID, NAME ": r=%lld relation rows out of range (1 <= r < 2^31 - 1)", (long long)r);           \
+  RARC_REQUIRE(max_edges >= 1, RARC_E_INVALID, NAME ": max_edges=%d out of range (1 <= max_edges <= %d)", max_edges, KHOP_MAX_EDGES);    \
+  RARC_REQUIRE(max_edges <= KHOP_MAX_EDGES, RARC_E_UNSUPPORTED,                                                                          \
+               NAME ": max_edges=%d: a list holds at most %d relations (the level counts say how many there are)", max_edges,            \
+               KHOP_MAX_EDGES);                                                                                                          \
+  RARC_REQUIRE(KHOP_ALIGNED(d_ews, 256), RARC_E_INVALID, NAME ": the edge workspace is not 256-byte aligned");                           \
+  const KhopEdgeWs ews = khop_edge_carve(d_ews, r, nq, hops);                                                                            \
+  RARC_REQUIRE(ews_bytes >= ews.bytes, RARC_E_WORKSPACE, NAME ": edge workspace of %zu bytes, %zu needed", ews_bytes, ews.bytes)
+
+// count / scan / write over the rows of the table, against the state in `ws`; PATHS: by the rule of the connecting paths
+template <bool PATHS>
+static int khop_edges_run(const KhopWs& ws, const KhopEdgeWs& ews, size_t level_stride, int64_t n, int nq, int W, int H, const int64_t* d_rel,
+                          int64_t r, int max_edges, bool listed, int64_t* d_out_ids, int32_t* d_out_levels, int32_t* d_out_count,
+                          int32_t* d_out_level_counts, hipStream_t s) {
   const KhopEdgeBits src = {d_rel, ws.seen, ws.level, level_stride, r, n};
   const int64_t tiles = khop_tiles(r);
-  hipLaunchKernelGGL(khop_edge_count_kernel, dim3(lv_grid(tiles * W, 4, 16384)), dim3(256), 0, s, src, W, H, ews.tiles);
+  hipLaunchKernelGGL(khop_edge_count_kernel<PATHS>, dim3(lv_grid(tiles * W, 4, 16384)), dim3(256), 0, s, src, W, H, ews.tiles);
   hipLaunchKernelGGL(khop_tile_scan_kernel, dim3((H * nq + 255) / 256), dim3(256), 0, s, tiles, W, H, nq, ews.tiles, ews.totals);
   if (listed) {
     RARC_HIP_CHECK(hipMemsetAsync(d_out_ids, 0xFF, (size_t)nq * max_edges * 8, s));            // (-1, -1) past the count
     RARC_HIP_CHECK(hipMemsetAsync(d_out_levels, 0xFF, (size_t)nq * max_edges * 4, s));
-    hipLaunchKernelGGL(khop_list_kernel<true>, dim3(lv_grid(tiles * W, 4, 16384)), dim3(256), 0, s, (const u64*)ws.level, level_stride, n, W, H, nq,
-                       (const uint32_t*)ews.tiles, (const int32_t*)ews.totals, (uint32_t)max_edges, d_out_ids, d_out_levels, d_out_count,
+    hipLaunchKernelGGL((khop_list_kernel<true, PATHS>), dim3(lv_grid(tiles * W, 4, 16384)), dim3(256), 0, s, (const u64*)ws.level, level_stride, n, W,
+                       H, nq, (const uint32_t*)ews.tiles, (const int32_t*)ews.totals, (uint32_t)max_edges, d_out_ids, d_out_levels, d_out_count,
                        KhopRelations{d_rel, ws.seen, r});
   }
   RARC_HIP_CHECK(hipGetLastError());
   RARC_HIP_CHECK(hipMemcpyAsync(d_out_level_counts, ews.totals, (size_t)nq * H * 4, hipMemcpyDeviceToDevice, s));
   return RARC_OK;
+}
+
+extern "C" int rarc_khop_edges(int64_t n, int64_t m, int nq, int hops, const void* d_ws, size_t ws_bytes, const int64_t* d_rel, int64_t r,
+                               int max_edges, void* d_ews, size_t ews_bytes, int64_t* d_out_ids, int32_t* d_out_levels, int32_t* d_out_count,
+                               int32_t* d_out_level_counts, void* stream) {
+  RARC_RANGE();
+  KHOP_EDGE_CHECKS("rarc_khop_edges");
+  return khop_edges_run<false>(ws, ews, level_stride, n, nq, W, H, d_rel, r, max_edges, listed, d_out_ids, d_out_levels, d_out_count,
+                               d_out_level_counts, (hipStream_t)stream);
+}
+
+// ---- connecting paths: the entries -------------------------------------------------------------------------------------------------
+extern "C" int rarc_khop_paths_limits(int* out3) {
+  RARC_REQUIRE(out3, RARC_E_INVALID, "rarc_khop_paths_limits: null pointer");
+  out3[0] = KHOP_MAX_HOPS;
+  out3[1] = KHOP_MAX_B;
+  out3[2] = KHOP_MAX_B;
+  return RARC_OK;
+}
+
+extern "C" int rarc_khop_paths(int64_t n, int64_t m, int ns, int np, int max_length, const void* d_ws, size_t ws_bytes, const int32_t* d_pairs,
+                               void* d_pws, size_t pws_bytes, int32_t* d_out_dist, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_ws && d_pairs && d_pws && d_out_dist, RARC_E_INVALID, "rarc_khop_paths: null pointer");
+  RARC_REQUIRE(KHOP_ALIGNED(d_pairs, 4) && KHOP_ALIGNED(d_out_dist, 4), RARC_E_INVALID,
+               "rarc_khop_paths: the pairs or the distances are not 4-byte aligned");
+  RARC_REQUIRE(np >= 1 && np <= KHOP_MAX_B, RARC_E_INVALID, "rarc_khop_paths: %d pairs out of range (1 <= np <= %d per call)", np, KHOP_MAX_B);
+  const int nq = ns, hops = max_length;                                // the traversal: ns columns stepped to max_length
+  KHOP_SHAPE_CHECKS("rarc_khop_paths");
+  RARC_REQUIRE(KHOP_ALIGNED(d_pws, 256), RARC_E_INVALID, "rarc_khop_paths: the path workspace is not 256-byte aligned");
+  const KhopWs pws = khop_carve(d_pws, n, np, hops);
+  RARC_REQUIRE(pws_bytes >= pws.bytes, RARC_E_WORKSPACE, "rarc_khop_paths: path workspace of %zu bytes, %zu needed", pws_bytes, pws.bytes);
+  hipStream_t s = (hipStream_t)stream;
+  RARC_HIP_CHECK(hipMemsetAsync(pws.grew, 0, KHOP_CTL_BYTES, s));
+  RARC_HIP_CHECK(hipMemsetAsync(d_out_dist, 0xFF, (size_t)np * 4, s));                         // -1 until a vertex joins the pair
+  hipLaunchKernelGGL(khop_path_dist_kernel, dim3(lv_grid(n, 256, 16384)), dim3(256), 0, s, (const u64*)ws.level, level_stride, n, W, H, ns, d_pairs,
+                     np, (uint32_t*)d_out_dist);
+  KhopPathArgs a;
+  a.seen = ws.seen;
+  a.level = ws.level;
+  a.pseen = pws.seen;
+  a.plevel = pws.level;
+  a.pairs = d_pairs;
+  a.dist = d_out_dist;
+  a.level_stride = level_stride;
+  a.plevel_stride = lv_align(pws.level_words * 8) / 8;
+  a.n = n;
+  a.W = W;
+  a.PW = khop_words(np);
+  a.H = H;
+  a.ns = ns;
+  a.np = np;
+  hipLaunchKernelGGL(khop_path_mark_kernel, dim3(lv_grid(n, 4, 16384)), dim3(256), 0, s, a);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+extern "C" int rarc_khop_path_edges(int64_t n, int64_t m, int nq, int hops, const void* d_ws, size_t ws_bytes, const int64_t* d_rel, int64_t r,
+                                    int max_edges, void* d_ews, size_t ews_bytes, int64_t* d_out_ids, int32_t* d_out_levels,
+                                    int32_t* d_out_count, int32_t* d_out_level_counts, void* stream) {
+  RARC_RANGE();
+  KHOP_EDGE_CHECKS("rarc_khop_path_edges");
+  return khop_edges_run<true>(ws, ews, level_stride, n, nq, W, H, d_rel, r, max_edges, listed, d_out_ids, d_out_levels, d_out_count,
+                              d_out_level_counts, (hipStream_t)stream);
 }
 
 extern "C" int rarc_khop_chunks(int64_t n, int64_t m, int nq, int hops, const uint32_t* decay, const void* d_ws, size_t ws_bytes,

@@ -15,7 +15,10 @@ search without leaving HBM, and `.neighbourhood_chunks` / `.expand_chunks` push 
 the chunks a retriever returns, a mention one hop nearer counting four times as much by default.  `.subgraph` /
 `.neighbourhood_edges` / `.expand_subgraph` add the third thing a local search collects, MATCH (a)-[r]-(b) WHERE a, b IN nodes:
 the rows of a `RelationList` (the caller's typed relations, or the graph's own pairs) whose two ends both lie in the
-neighbourhood, from the same traversal.
+neighbourhood, from the same traversal.  `.shortest_paths` / `.path_chunks` / `.connect` answer the other
+question a multi-hop query asks, MATCH p = allShortestPaths((a)-[*..L]-(b)): the vertices and relations on every shortest path
+between two sources of one traversal, written as a k-hop state of their own so that the lists, the relation rows and the chunk
+projection read it unchanged.
 
 The rule is defined in integers (restated by tests/khop_ref.py): the answer is the same bits for any order of the
 edges and any batch, and row q of a batch equals the one-query call.  No CPU fallback: without a device this raises."""
@@ -311,8 +314,9 @@ def _own_relations(graph):
     return rel
 
 
-def _edges(graph, rel, nq, hops, max_edges, ws, wb):
-    """the relations inside the neighbourhoods the traversal left in (ws, wb) -> device tensors, in the order of EDGE_FIELDS"""
+def _edges(graph, rel, nq, hops, max_edges, ws, wb, entry="rarc_khop_edges"):
+    """the relations inside the neighbourhoods the traversal left in (ws, wb) -> device tensors, in the order of EDGE_FIELDS;
+    entry="rarc_khop_path_edges": the relations on the paths of the path state in (ws, wb)"""
     t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
     need = int(lib.rarc_khop_edges_workspace_bytes(rel.r, nq, hops))
     if need == 0:
@@ -326,8 +330,8 @@ def _edges(graph, rel, nq, hops, max_edges, ws, wb):
     cnt = t.empty(nq, dtype=t.int32, device=graph.device)
     lc = t.empty((nq, hops + 1), dtype=t.int32, device=graph.device)
     stream = t.cuda.current_stream(graph.device).cuda_stream
-    B.check(lib.rarc_khop_edges(n, m, nq, hops, ws, wb, rel._pairs.data_ptr(), rel.r, max_edges, ews.data_ptr(), ews.numel(), ids.data_ptr(),
-                                lv.data_ptr(), cnt.data_ptr(), lc.data_ptr(), stream), "rarc_khop_edges")
+    B.check(getattr(lib, entry)(n, m, nq, hops, ws, wb, rel._pairs.data_ptr(), rel.r, max_edges, ews.data_ptr(), ews.numel(), ids.data_ptr(),
+                                lv.data_ptr(), cnt.data_ptr(), lc.data_ptr(), stream), entry)
     rows = ids.clamp(min=0)                                                                  # the few returned rows: gathered here
     ends = t.where((ids >= 0).unsqueeze(-1), rel._pairs[rows], t.full_like(rel._pairs[:1], -1))
     out = (ids, ends, lv, cnt, lc)
@@ -381,6 +385,209 @@ def expand_subgraph(graph, index, queries, seeds_per_query: int = 5, hops: int =
     with graph.torch.cuda.device(graph.device):
         rel = _own_relations(graph) if relations is None else relations
         return Subgraph(*_batched(graph, sd, as_device, lambda part: _subgraph(graph, rel, part, hops, int(max_vertices), max_edges, early_stop)))
+
+
+# ---- connecting paths: all shortest paths between sources (restated by tests/paths_ref.py) ------------------------------
+MAX_PAIRS = 256                # pairs per call, and sources per call: one launch batch each
+MAX_CONNECT_SEEDS = 23         # seeds_per_query of connect: 23 * 22 / 2 = 253 pairs of one query still fit one launch
+
+PATH_FIELDS = ("distances", "vertex_ids", "vertex_positions", "vertex_counts", "position_counts") + EDGE_FIELDS
+ShortestPaths = collections.namedtuple("ShortestPaths", PATH_FIELDS, defaults=(None,))
+Connection = collections.namedtuple("Connection", PATH_FIELDS + ("pair_query", "pair_ends"), defaults=(None, None, None))
+
+
+def paths_limits() -> dict:
+    """The limits of rarc_khop_paths: the longest path looked for, and the sources and pairs of one call."""
+    out = (ctypes.c_int * 3)()
+    B.check(B.load_library().rarc_khop_paths_limits(out), "rarc_khop_paths_limits")
+    return {"max_length": out[0], "max_sources": out[1], "max_pairs": out[2]}
+
+
+def check_length(max_length) -> int:
+    """ValueError for a negative max_length, RarcUnsupported, naming the limit, above 8"""
+    if int(max_length) != max_length or int(max_length) < 0:
+        raise ValueError(f"max_length must be an integer >= 0, got {max_length!r}")
+    if int(max_length) > MAX_HOPS:
+        raise B.RarcUnsupported(f"max_length={int(max_length)}: paths of at most {MAX_HOPS} edges are looked for (0 <= max_length <= {MAX_HOPS})")
+    return int(max_length)
+
+
+def check_path_caps(max_vertices, max_edges):
+    """-> (max_vertices, max_edges) as integers; a path answer is always a list: ValueError below 1, RarcUnsupported above 65536"""
+    if max_vertices is None:
+        raise ValueError("max_vertices must be an integer >= 1: the vertices on the paths are returned as a list")
+    if int(max_vertices) != max_vertices or int(max_vertices) < 1:
+        raise ValueError(f"max_vertices must be an integer >= 1, got {max_vertices!r}")
+    if int(max_vertices) > MAX_LIST_VERTICES:
+        raise B.RarcUnsupported(f"max_vertices={int(max_vertices)}: a list holds at most 2^16 = {MAX_LIST_VERTICES} vertices; position_counts "
+                                f"says how many lie on the paths")
+    return int(max_vertices), check_max_edges(max_edges)
+
+
+def host_sources(n: int, sources) -> np.ndarray:
+    """host_seeds for the sources of a path query; RarcUnsupported for more than 256 of them"""
+    sd = host_seeds(n, sources)
+    if sd.shape[0] > MAX_PAIRS:
+        raise B.RarcUnsupported(f"{sd.shape[0]} sources: one call takes at most {MAX_PAIRS}")
+    return sd
+
+
+def host_pairs(ns: int, pairs) -> np.ndarray:
+    """[np][2] source indices -> int32 [np][2].  ValueError for no pairs, another shape, or an index outside [0, ns);
+    RarcUnsupported for more than 256 pairs"""
+    p = np.asarray(pairs)
+    if p.ndim != 2 or p.shape[1] != 2 or p.shape[0] < 1:
+        raise ValueError(f"expected [np][2] pairs of source indices, np >= 1, got an array of shape {p.shape}")
+    if p.shape[0] > MAX_PAIRS:
+        raise B.RarcUnsupported(f"{p.shape[0]} pairs: one call takes at most {MAX_PAIRS}")
+    if not np.all(p == np.floor(p)) or p.min() < 0 or p.max() >= ns:
+        raise ValueError(f"a pair names a source outside [0, {ns})")
+    return np.ascontiguousarray(p.astype(np.int32))
+
+
+def _device_sources(graph, sources, pairs):
+    """sources as neighbourhood takes seeds, pairs [np][2] -> (device int64 [ns][s], device int32 [np][2]), checked"""
+    t = graph.torch
+    if isinstance(sources, t.Tensor):
+        sd = graph._seed_tensors(sources, None)[0]
+        if int(sd.shape[0]) > MAX_PAIRS:
+            raise B.RarcUnsupported(f"{int(sd.shape[0])} sources: one call takes at most {MAX_PAIRS}")
+    else:
+        sd = t.from_numpy(host_sources(graph.n, sources)).to(graph.device)
+    ns = int(sd.shape[0])
+    if isinstance(pairs, t.Tensor) and pairs.is_cuda:
+        if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1 or pairs.dtype not in (t.int32, t.int64):
+            raise ValueError(f"expected an int32 or int64 [np][2] tensor of pairs, np >= 1, got {pairs.dtype} {tuple(pairs.shape)}")
+        if int(pairs.shape[0]) > MAX_PAIRS:
+            raise B.RarcUnsupported(f"{int(pairs.shape[0])} pairs: one call takes at most {MAX_PAIRS}")
+        if not bool(((pairs >= 0) & (pairs < ns)).all().item()):
+            raise ValueError(f"a pair names a source outside [0, {ns})")
+        return sd, pairs.to(device=graph.device, dtype=t.int32).contiguous()
+    return sd, t.from_numpy(host_pairs(ns, pairs.cpu().numpy() if isinstance(pairs, t.Tensor) else pairs)).to(graph.device)
+
+
+def mark_paths(graph, sd, pd, length: int, early_stop: bool = False):
+    """One traversal of the sources `sd` to `length`, then rarc_khop_paths for the pairs `pd` -> (distances, a device int32
+    [np]; path workspace pointer, bytes): a k-hop state of np columns with positions for hops, for the k-hop readers"""
+    t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
+    ns, npairs = int(sd.shape[0]), int(pd.shape[0])
+    ws, wb = traverse(graph, sd, length, early_stop)
+    need = int(lib.rarc_khop_workspace_bytes(n, m, npairs, length))
+    if need == 0:
+        raise B.RarcError(f"shortest_paths: n={n}, m={m}, {npairs} pairs, max_length={length} refused by rarc_khop_workspace_bytes")
+    pws = getattr(graph, "_path_ws", None)
+    if pws is None or pws.numel() < need:
+        graph._path_ws = None
+        graph._path_ws = pws = t.empty(need, dtype=t.uint8, device=graph.device)
+    dist = t.empty(npairs, dtype=t.int32, device=graph.device)
+    stream = t.cuda.current_stream(graph.device).cuda_stream
+    B.check(lib.rarc_khop_paths(n, m, ns, npairs, length, ws, wb, pd.data_ptr(), pws.data_ptr(), pws.numel(), dist.data_ptr(), stream),
+            "rarc_khop_paths")
+    return dist, pws.data_ptr(), pws.numel()
+
+
+def _paths(graph, rel, sd, pd, length, max_vertices, max_edges, early_stop):
+    """one call -> device tensors in the order of PATH_FIELDS"""
+    t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
+    npairs = int(pd.shape[0])
+    dist, pws, pwb = mark_paths(graph, sd, pd, length, early_stop)
+    ids = t.empty((npairs, max_vertices), dtype=t.int64, device=graph.device)
+    pos = t.empty((npairs, max_vertices), dtype=t.int32, device=graph.device)
+    cnt = t.empty(npairs, dtype=t.int32, device=graph.device)
+    pc = t.empty((npairs, length + 1), dtype=t.int32, device=graph.device)
+    stream = t.cuda.current_stream(graph.device).cuda_stream
+    B.check(lib.rarc_khop_list(n, m, npairs, length, max_vertices, pws, pwb, ids.data_ptr(), pos.data_ptr(), cnt.data_ptr(), stream), "rarc_khop_list")
+    B.check(lib.rarc_khop_counts(n, m, npairs, length, pws, pwb, pc.data_ptr(), stream), "rarc_khop_counts")
+    return (dist, ids, pos, cnt, pc) + _edges(graph, rel, npairs, length, max_edges, pws, pwb, entry="rarc_khop_path_edges")
+
+
+def _host(out, as_device):
+    return out if as_device else tuple(x.cpu().numpy() for x in out)
+
+
+def shortest_paths(graph, sources, pairs, max_length: int = 4, max_vertices: int = 4096, max_edges: int = 16384, relations=None,
+                   as_device: bool = False, early_stop: bool = False):
+    length = check_length(max_length)
+    max_vertices, max_edges = check_path_caps(max_vertices, max_edges)
+    check_relations(graph, relations)
+    with graph.torch.cuda.device(graph.device):
+        sd, pd = _device_sources(graph, sources, pairs)
+        rel = _own_relations(graph) if relations is None else relations
+        return ShortestPaths(*_host(_paths(graph, rel, sd, pd, length, max_vertices, max_edges, early_stop), as_device))
+
+
+def path_chunks(graph, mentions, sources, pairs, max_length: int = 4, decay=None, top_k=None, as_device: bool = False,
+                early_stop: bool = False):
+    length = check_length(max_length)
+    decay = check_decay(decay, length)
+    _check_mentions(graph, mentions, top_k)
+    t, lib = graph.torch, graph.lib
+    with t.cuda.device(graph.device):
+        sd, pd = _device_sources(graph, sources, pairs)
+        npairs = int(pd.shape[0])
+        _, pws, pwb = mark_paths(graph, sd, pd, length, early_stop)
+        cws, cb = mentions.workspace(npairs)
+        split, n_split = mentions.split_list()
+        stream = t.cuda.current_stream(graph.device).cuda_stream
+        B.check(lib.rarc_khop_chunks(graph.n, graph.m, npairs, length, decay.ctypes.data, pws, pwb, mentions._row_ptr.data_ptr(),
+                                     mentions._ent.data_ptr(), mentions._w.data_ptr(), mentions.n_chunks, mentions.nnz, split, n_split, cws, cb,
+                                     stream), "rarc_khop_chunks")
+        out = mentions.ranked(npairs, None if top_k is None else int(top_k))
+        out = _host((out,) if top_k is None else out, as_device)
+        return out[0] if top_k is None else tuple(out)
+
+
+def connect(graph, index, queries, seeds_per_query: int = 5, max_length: int = 4, max_vertices: int = 4096, max_edges: int = 16384,
+            relations=None, as_device: bool = False, early_stop: bool = False):
+    length = check_length(max_length)
+    max_vertices, max_edges = check_path_caps(max_vertices, max_edges)
+    check_relations(graph, relations)
+    graph._check_index(index, seeds_per_query)
+    k = int(seeds_per_query)
+    if k < 2:
+        raise ValueError("connect pairs the seeds of a query: seeds_per_query must be at least 2")
+    if k > MAX_CONNECT_SEEDS:
+        raise B.RarcUnsupported(f"seeds_per_query={k}: the {k * (k - 1) // 2} pairs of one query exceed the {MAX_PAIRS} of one launch "
+                                f"(seeds_per_query <= {MAX_CONNECT_SEEDS})")
+    t = graph.torch
+    ids, _ = graph._index_seeds(index, queries, k)                                           # int64 [Q][k], on the device
+    i, j = np.triu_indices(k, 1)
+    per_query = np.stack([i, j], axis=1).astype(np.int32)                                    # every i < j of one query's seeds
+    step = min(MAX_PAIRS // k, MAX_PAIRS // len(per_query))                                  # queries per launch batch
+    with t.cuda.device(graph.device):
+        rel = _own_relations(graph) if relations is None else relations
+        parts = []
+        for q0 in range(0, int(ids.shape[0]), step):
+            part = ids[q0:q0 + step]
+            nq = int(part.shape[0])
+            local = (per_query[None] + (np.arange(nq, dtype=np.int32) * k)[:, None, None]).reshape(-1, 2)
+            pd = t.from_numpy(local).to(graph.device)
+            sd = part.reshape(-1, 1).contiguous()                                            # every seed a one-vertex source
+            pq = t.from_numpy(np.repeat(np.arange(q0, q0 + nq, dtype=np.int32), len(per_query))).to(graph.device)
+            ends = sd[:, 0][pd.to(t.int64)]
+            parts.append(_paths(graph, rel, sd, pd, length, max_vertices, max_edges, early_stop) + (pq, ends))
+        if rel._weights is None:                                                             # edge_weights stays None, before the two pair fields
+            parts = [p[:-2] + (None,) + p[-2:] for p in parts]
+        out = tuple(None if p0 is None else (p0 if len(parts) == 1 else t.cat([p[f] for p in parts])) for f, p0 in enumerate(parts[0]))
+        return Connection(*(out if as_device else tuple(None if x is None else x.cpu().numpy() for x in out)))
+
+
+def all_shortest_paths(n: int, edges, sources, pairs, device: int = 0, **kw):
+    """The one-shot form: EntityGraph(n, edges, device=device).shortest_paths(sources, pairs, **kw).  The arguments are checked
+    before the graph is built: a bad source, pair, max_length, max_vertices, max_edges or relation list raises with no device
+    visible."""
+    from .pagerank import EntityGraph
+
+    check_length(kw.get("max_length", 4))
+    check_path_caps(kw.get("max_vertices", 4096), kw.get("max_edges", 16384))
+    rel = kw.get("relations")
+    if rel is not None and (not isinstance(rel, RelationList) or rel.n_entities != int(n)):
+        raise ValueError(f"relations must be a RelationList over the graph's {int(n)} vertices (or None for the graph's own pair list)")
+    if not hasattr(sources, "is_cuda"):
+        ns = host_sources(int(n), sources).shape[0]
+        if not hasattr(pairs, "is_cuda"):
+            host_pairs(ns, pairs)
+    return EntityGraph(n, edges, device=device).shortest_paths(sources, pairs, **kw)
 
 
 def k_hop_subgraph(n: int, pairs, seeds, hops: int = 2, device: int = 0, **kw):

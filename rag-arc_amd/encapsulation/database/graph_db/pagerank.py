@@ -460,6 +460,45 @@ class EntityGraph:
         return K.expand_subgraph(self, index, queries, seeds_per_query=seeds_per_query, hops=hops, max_vertices=max_vertices, max_edges=max_edges,
                                  relations=relations, as_device=as_device, early_stop=early_stop)
 
+    def shortest_paths(self, sources, pairs, max_length: int = 4, max_vertices: int = 4096, max_edges: int = 16384, relations=None,
+                       as_device: bool = False, early_stop: bool = False):
+        """How sources are connected: every shortest path of at most `max_length` edges between the two sources of each pair,
+        MATCH p = allShortestPaths((a)-[*..L]-(b)), from one traversal of all sources.
+        sources: 1 .. 256 seed sets as neighbourhood takes them (a set may be empty).  pairs: [np][2] indices into `sources`,
+        1 <= np <= 256; ia == ib and repeats are allowed.  0 <= max_length <= 8.
+        d = the fewest edges between any vertex of A and any of B, -1 if more than max_length; v is on the paths at position i
+        iff hop_A(v) == i and hop_B(v) == d - i; a row of `relations` is at level i + 1 iff it joins positions i and i + 1.
+        -> the named tuple (distances int32 [np], vertex_ids, vertex_positions, vertex_counts, position_counts) shaped as
+        neighbourhood(max_vertices=...) shapes its lists, then the edge fields exactly as neighbourhood_edges returns them.
+        ValueError for a seed outside [0, n), more than 64 seeds, a pair index outside [0, ns) or a negative length;
+        RarcUnsupported for max_length > 8, more than 256 sources or pairs, or a cap above 65536."""
+        from . import neighbourhood as K
+
+        return K.shortest_paths(self, sources, pairs, max_length=max_length, max_vertices=max_vertices, max_edges=max_edges,
+                                relations=relations, as_device=as_device, early_stop=early_stop)
+
+    def path_chunks(self, mentions, sources, pairs, max_length: int = 4, decay=None, top_k=None, as_device: bool = False,
+                    early_stop: bool = False):
+        """shortest_paths, ending in chunks: S_p(c) = sum over c's mentions (e, w) with e on p's paths of w * decay[position(e)],
+        decay of max_length + 1 entries -> scores float64 [np][n_chunks], or with top_k (ids, scores, counts), as
+        neighbourhood_chunks shapes them."""
+        from . import neighbourhood as K
+
+        return K.path_chunks(self, mentions, sources, pairs, max_length=max_length, decay=decay, top_k=top_k, as_device=as_device,
+                             early_stop=early_stop)
+
+    def connect(self, index, queries, seeds_per_query: int = 5, max_length: int = 4, max_vertices: int = 4096, max_edges: int = 16384,
+                relations=None, as_device: bool = False, early_stop: bool = False):
+        """shortest_paths between the entities a query links to: each query's seeds are the index's own top-`seeds_per_query`
+        ids, as expand takes them; every seed is a one-vertex source and the pairs are all i < j within a query (2 <=
+        seeds_per_query <= 23), cut into launches of at most 256 sources and pairs.
+        -> the fields of shortest_paths, one row per pair, then pair_query int32 [np] (the query of a pair) and pair_ends int64
+        [np][2] (its two seed vertices)."""
+        from . import neighbourhood as K
+
+        return K.connect(self, index, queries, seeds_per_query=seeds_per_query, max_length=max_length, max_vertices=max_vertices,
+                         max_edges=max_edges, relations=relations, as_device=as_device, early_stop=early_stop)
+
 
 def personalized_pagerank(n: int, pairs, seeds, weights=None, device: int = 0, **kw):
     """The one-shot form: EntityGraph(n, pairs, weights, device).personalized_pagerank(seeds, **kw)."""
