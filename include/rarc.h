@@ -1102,6 +1102,39 @@ int rarc_merge_relations(const int64_t* d_rel, int64_t r, const int64_t* d_new_i
                          int64_t* d_out_rel, int64_t* d_out_rows, int64_t* d_out3, void* stream);
 
 /*
+ * Connected components: which vertices of the graph rarc_graph_csr built are joined at all, how many pieces it has and how large
+ * they are — CALL gds.wcc.stream(graph) — next to the resident CSR.  The rule (restated by
+ * tests/components_ref.py): a parent word p[v] per vertex, p[v] = v at first.  A round starts from a star forest and hooks — for
+ * every adjacency entry (u, v), with ru = p[u] and rv = p[v] as they stood at the start of the round and rv < ru, p[ru] =
+ * min(p[ru], rv) — and then jumps: every vertex follows p to its root and stores it.  The first round whose hooks lower no
+ * parent ends the run; label(v) = p[v] is then the smallest vertex of v's component (the convention of rarc_louvain_labels).
+ * Every join is an integer min over a set: the state after every round, and so the number of rounds, is the same for any order
+ * of the edges and from run to run; no graph takes more than 2 ceil(log2 n) + 2 rounds (csrc/components.hip).
+ * Limits: n, m as rarc_graph_csr's; the workspace and the graph 256-byte aligned, the other pointers to their element; refused
+ * before any launch.
+ *
+ * rarc_components_workspace_bytes — the size of d_ws (0 for a refused shape); every entry of one run takes the same n, m, d_ws.
+ * rarc_components_init — p[v] = v.
+ * rarc_components_round — one hook and one jump over the CSR in d_graph.  d_changed int32 [1] on the device: 1 if a hook lowered
+ *   a parent, else 0 — then the labels are final and a further round changes nothing.  The loop is the caller's, one word a
+ *   round.  A vertex of at most 8 neighbours takes 8 lanes, one of at most 64 a quarter wave, a larger one a workgroup
+ *   (rarc_components_limits); a vertex issues one atomic min.
+ * rarc_components_finish — d_labels int64 [n] = p; d_dense int32 [n] or null: the rank of label(v) among the distinct labels,
+ *   ascending; d_sizes int64 [n] or null: its first n_components entries are the sizes by dense id; d_out3 int64 [3] =
+ *   {n_components, size of the largest component, its label — among equals the smallest}.  Reads the state as it is: before the
+ *   run has ended the labels are those of the forest so far.
+ * rarc_components_limits — out4 = {largest degree of the 8-lane form, of the quarter-wave form, of the first workgroup list, the
+ *   additive constant of the round bound}.
+ */
+size_t rarc_components_workspace_bytes(int64_t n, int64_t m);
+int rarc_components_init(int64_t n, int64_t m, void* d_ws, size_t ws_bytes, void* stream);
+int rarc_components_round(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, void* d_ws, size_t ws_bytes, int32_t* d_changed,
+                          void* stream);
+int rarc_components_finish(int64_t n, int64_t m, void* d_ws, size_t ws_bytes, int64_t* d_labels, int32_t* d_dense, int64_t* d_sizes,
+                           int64_t* d_out3, void* stream);
+int rarc_components_limits(int* out4);
+
+/*
  * Deleting rows of a resident index: stable in-place compaction.  The reference deletes by clearing the index and
  * embedding every surviving text again (encapsulation/database/vector_db/VectorStore_Faiss.py:374-415); the surviving
  * rows are in HBM already, so here they move down over the holes: row i of the result is the i-th surviving row.

@@ -6,8 +6,10 @@ build: personalized PageRank from the entities a query links to, pushed through 
 MATCH (s)-[*..h]-(v): the entities within h hops of a query's entities, and MATCH p = allShortestPaths((a)-[*..L]-(b)): how
 two of them are connected (neighbourhood.py); and the last step of the
 de-duplication, merging each cluster into one entity (Base_Neo4j.py:714-890), which contracts that graph where it lies
-(merge.py).  The graph database itself is out of scope."""
+(merge.py); and what gds.wcc answers about that graph, its connected components (components.py).  The graph database itself is
+out of scope."""
 from .communities import entity_clusters, louvain_communities
+from .components import Components, connected_components
 from .merge import MergedEntities, MergePlan, deduplicate_entities, merge_entities, merge_plan
 from .neighbourhood import RelationList, k_hop, k_hop_subgraph
 from .neighbourhood import all_shortest_paths as shortest_paths
@@ -17,4 +19,4 @@ from .similarity import knn_graph, similar_pairs
 
 __all__ = ["similar_pairs", "knn_graph", "louvain_communities", "entity_clusters", "EntityGraph", "personalized_pagerank", "MentionMap",
            "k_hop", "k_hop_subgraph", "shortest_paths", "RelationList", "merge_plan", "merge_entities", "deduplicate_entities", "MergePlan",
-           "MergedEntities"]
+           "MergedEntities", "connected_components", "Components"]

@@ -26,6 +26,14 @@ from . import similarity as S
 
 MAX_EDGES = 1 << 30            # csrc/louvain.hip: m < 2^30 and n < 2^31 - 1 keep every product of the rule inside int64
 MAX_VERTICES = (1 << 31) - 1
+METHODS = ("louvain", "components")
+
+
+def check_method(method) -> str:
+    """ValueError for anything but "louvain" or "components": raised before anything else is looked at"""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+    return method
 
 
 def bucket_limits() -> dict:
@@ -151,20 +159,23 @@ def clusters_of(labels: np.ndarray, min_size: int = 2) -> List[List[int]]:
 
 
 def entity_clusters(embeddings, threshold: float = 0.95, max_iterations: int = 10, max_levels: int = 10, min_size: int = 2,
-                    device: int = 0, as_labels: bool = False):
+                    device: int = 0, as_labels: bool = False, method: str = "louvain"):
     """The Louvain communities of the graph that joins every two embeddings whose cosine reaches `threshold`: lists of row
     indices, each ascending, only those of at least min_size rows, ordered by size descending and then by smallest member.
     as_labels=True returns labels int64 [n] instead (labels[i] = the smallest row of i's community).
-    embeddings: [n][d] array-like of floats or a torch tensor (used where it is).  The pairs never leave the device."""
+    embeddings: [n][d] array-like of floats or a torch tensor (used where it is).  The pairs never leave the device.
+    method="components" clusters by the connected components of that graph instead (graph_db/components.py): the rows that are
+    transitively near-duplicates, exact and without parameters — max_iterations and max_levels are checked and not used."""
+    check_method(method)
     min_size = int(min_size)
     if int(max_iterations) >= 1 and int(max_levels) >= 1 and min_size < 1:
         raise ValueError("min_size must be at least 1")
-    n, labels = _embedding_labels(embeddings, threshold, max_iterations, max_levels, device)
+    n, labels = _embedding_labels(embeddings, threshold, max_iterations, max_levels, device, method)
     labels = np.arange(n, dtype=np.int64) if labels is None else labels.cpu().numpy()
     return labels if as_labels else clusters_of(labels, min_size)
 
 
-def _embedding_labels(embeddings, threshold, max_iterations, max_levels, device):
+def _embedding_labels(embeddings, threshold, max_iterations, max_levels, device, method="louvain"):
     """entity_clusters up to the labels -> (n, labels int64 [n] on the device, or None where nothing was clustered: fewer than 2
     rows, or no pair reached the threshold); `deduplicate_entities` goes on from them where they are"""
     import torch
@@ -196,6 +207,10 @@ def _embedding_labels(embeddings, threshold, max_iterations, max_levels, device)
         with torch.cuda.device(dev):
             pairs, _, found = S._pairs_on_device(lib, x.contiguous(), float(threshold), dev)
             _check_counts(n, found, max_iterations, max_levels)
+            if found and method == "components":
+                from .components import labels_on_device
+
+                return n, labels_on_device(lib, pairs, n, found, dev)
             if found:
                 return n, _cluster_on_device(lib, pairs, n, found, max_iterations, max_levels, dev)
     return n, None

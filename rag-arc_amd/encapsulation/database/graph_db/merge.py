@@ -292,13 +292,16 @@ def merge_entities(plan_or_labels, graph=None, mentions=None, relations=None, ri
 
 
 def deduplicate_entities(embeddings, threshold: float = 0.95, richness=None, graph=None, mentions=None, relations=None,
-                         max_iterations: int = 10, max_levels: int = 10, device: int = 0, as_device: bool = False) -> MergedEntities:
+                         max_iterations: int = 10, max_levels: int = 10, device: int = 0, as_device: bool = False,
+                         method: str = "louvain") -> MergedEntities:
     """Steps 1-4 of the reference's de-duplication in one call: the pairs of embeddings whose cosine reaches `threshold`, their
-    Louvain communities, the plan and the merge.  The pairs and the labels never leave the device.  Arguments as
-    `entity_clusters` and `merge_entities` take them; row i of `embeddings` is entity i."""
-    from .communities import _embedding_labels
+    Louvain communities — or with method="components" their connected components, the transitive closure of the pairs — the
+    plan and the merge.  The pairs and the labels never leave the device.  Arguments as `entity_clusters` and `merge_entities`
+    take them; row i of `embeddings` is entity i."""
+    from .communities import _embedding_labels, check_method
 
-    n, labels = _embedding_labels(embeddings, threshold, max_iterations, max_levels, device)
+    check_method(method)
+    n, labels = _embedding_labels(embeddings, threshold, max_iterations, max_levels, device, method)
     if labels is None:
         labels = np.arange(n, dtype=np.int64)                        # nothing was similar: every entity is its own class
     for what, x, k in (("graph", graph, "n"), ("mention map", mentions, "n_entities"), ("relation list", relations, "n_entities")):

@@ -126,6 +126,7 @@ class EntityGraph:
             torch.cuda.current_stream(self.device).synchronize()
         self._pairs, self._pair_weights = p, wd                         # kept for subgraph(relations=None): 16 bytes an edge
         self._ws = None
+        self._components = {}                                           # as_device -> Components, filled by components()
 
     @classmethod
     def from_device(cls, n: int, pairs, weights=None):
@@ -172,6 +173,7 @@ class EntityGraph:
             torch.cuda.current_stream(self.device).synchronize()
         self._pairs, self._pair_weights = p, wd
         self._ws = None
+        self._components = {}
         return self
 
     # ---------------------------------------------------------------------------------------------------------------- arguments
@@ -498,6 +500,31 @@ class EntityGraph:
 
         return K.connect(self, index, queries, seeds_per_query=seeds_per_query, max_length=max_length, max_vertices=max_vertices,
                          max_edges=max_edges, relations=relations, as_device=as_device, early_stop=early_stop)
+
+    # ---------------------------------------------------------------------------------------------------------------- components
+    def components(self, as_device: bool = False):
+        """The connected components of the graph (graph_db/components.py) -> Components(labels int64 [n]: the
+        smallest vertex of v's component; dense int32 [n]: that label's rank among the distinct labels; sizes int64
+        [n_components] by dense id; n_components; largest = (label, size), among equals the smallest label; rounds).
+        Computed on the first call and kept: the graph never changes.  as_device=True returns device tensors — the labels are
+        what merge_plan takes."""
+        from . import components as C
+
+        return C.graph_components(self, as_device=as_device)
+
+    def component_of(self, vertices):
+        """The label of each vertex's component, from the kept labels: an int for one vertex, else an int64 array.  ValueError
+        for a vertex outside [0, n)."""
+        from . import components as C
+
+        return C.component_of(self, vertices)
+
+    def same_component(self, a, b):
+        """Whether any path joins a and b (vertices, or arrays of them): PPR mass, k-hop levels and shortest paths never cross a
+        component.  ValueError for a vertex outside [0, n)."""
+        from . import components as C
+
+        return C.same_component(self, a, b)
 
 
 def personalized_pagerank(n: int, pairs, seeds, weights=None, device: int = 0, **kw):

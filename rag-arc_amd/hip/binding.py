@@ -282,6 +282,11 @@ SIGNATURES = {
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "rarc_merge_relations_workspace_bytes": (c_size_t, [c_int64]),
     "rarc_merge_relations": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_components_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "rarc_components_init": (c_int, [c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
+    "rarc_components_round": (c_int, [c_void_p, c_size_t, c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "rarc_components_finish": (c_int, [c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_components_limits": (c_int, [ctypes.POINTER(c_int)]),
     "rarc_compact_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
     "rarc_vmem_create": (c_int, [c_int, c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_void_p)]),
     "rarc_vmem_grow": (c_int, [c_void_p, c_size_t]),
