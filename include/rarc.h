@@ -438,6 +438,9 @@ int rarc_synth_rows_f32(float* d_out_f32, int64_t ld_out, int d, int64_t first_r
  *   rarc_enc_add_ln   : out = LayerNorm(x + resid)
  *   rarc_enc_pool     : out[b] = hidden[b*seq_len + 0] as fp32 (optionally L2-normalised)          [CLS pooling]
  *   rarc_enc_pool_mean: out[b] = mean over the d_lens[b] real tokens of hidden[b*seq_len + t], fp32  [mean pooling]
+ * Limits, refused with an error code before anything is launched: n_tokens, n_rows, n_seq, seq_len > 0 everywhere;
+ * embed_ln / add_ln: hidden a POSITIVE multiple of 64, <= 1024; attention: hidden = n_heads * {32, 64}, seq_len <= 512;
+ * pool: hidden a positive multiple of 8; pool_mean: the same, <= 1024.  d_lens[b] is clamped into [1, seq_len].
  */
 int rarc_enc_embed_ln(const int32_t* d_ids, const uint16_t* d_word, const uint16_t* d_pos,
                       const uint16_t* d_type0, const uint16_t* d_gamma, const uint16_t* d_beta, float eps,

@@ -2498,7 +2498,7 @@ extern "C" int rarc_enc_embed_ln(const int32_t* d_ids, const uint16_t* d_word, c
                                  const uint16_t* d_type0, const uint16_t* d_gamma, const uint16_t* d_beta, float eps,
                                  int n_tokens, int seq_len, int hidden, int vocab, uint16_t* d_out, void* stream) {
   RARC_REQUIRE(d_ids && d_word && d_pos && d_type0 && d_gamma && d_beta && d_out, RARC_E_INVALID, "rarc_enc_embed_ln: null pointer");
-  RARC_REQUIRE(hidden % 64 == 0 && hidden <= 1024 && n_tokens > 0 && seq_len > 0, RARC_E_UNSUPPORTED,
+  RARC_REQUIRE(hidden > 0 && hidden % 64 == 0 && hidden <= 1024 && n_tokens > 0 && seq_len > 0, RARC_E_UNSUPPORTED,
                "rarc_enc_embed_ln: hidden must be a multiple of 64, <= 1024");
   RARC_REQUIRE(vocab > 0, RARC_E_INVALID, "rarc_enc_embed_ln: vocab (rows of the word table) must be given");
   hipLaunchKernelGGL(rarc_embed_ln_kernel, dim3((n_tokens + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_ids,
@@ -2512,7 +2512,7 @@ extern "C" int rarc_enc_add_ln(const uint16_t* d_x, const uint16_t* d_resid, con
                                const uint16_t* d_beta, float eps, int n_rows, int hidden, uint16_t* d_out,
                                void* stream) {
   RARC_REQUIRE(d_x && d_resid && d_gamma && d_beta && d_out, RARC_E_INVALID, "rarc_enc_add_ln: null pointer");
-  RARC_REQUIRE(hidden % 64 == 0 && hidden <= 1024 && n_rows > 0, RARC_E_UNSUPPORTED,
+  RARC_REQUIRE(hidden > 0 && hidden % 64 == 0 && hidden <= 1024 && n_rows > 0, RARC_E_UNSUPPORTED,
                "rarc_enc_add_ln: hidden must be a multiple of 64, <= 1024");
   hipLaunchKernelGGL(rarc_add_ln_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const half_t*)d_x,
                      (const float*)nullptr, 0, (const half_t*)nullptr, (const half_t*)d_resid, (const half_t*)d_gamma,
@@ -2566,7 +2566,9 @@ extern "C" int rarc_enc_attention(const uint16_t* d_qkv, const int32_t* d_lens, 
 
 extern "C" int rarc_enc_pool(const uint16_t* d_hidden, int n_seq, int seq_len, int hidden, int normalize,
                              float* d_out, void* stream) {
-  RARC_REQUIRE(d_hidden && d_out && n_seq > 0 && hidden % 8 == 0, RARC_E_INVALID, "rarc_enc_pool: bad arguments");
+  // (0 % 8 == 0 and -8 % 8 == 0: hidden > 0 is a check of its own; seq_len is the row stride between sequences)
+  RARC_REQUIRE(d_hidden && d_out && n_seq > 0 && seq_len > 0 && hidden > 0 && hidden % 8 == 0, RARC_E_INVALID,
+               "rarc_enc_pool: bad arguments");
   hipLaunchKernelGGL(rarc_pool_kernel, dim3(n_seq), dim3(64), 0, (hipStream_t)stream, (const half_t*)d_hidden, seq_len,
                      hidden, normalize, d_out);
   RARC_HIP_CHECK(hipGetLastError());
@@ -2575,7 +2577,7 @@ extern "C" int rarc_enc_pool(const uint16_t* d_hidden, int n_seq, int seq_len, i
 
 extern "C" int rarc_enc_pool_mean(const uint16_t* d_hidden, const int32_t* d_lens, int n_seq, int seq_len, int hidden,
                                   int normalize, float* d_out, void* stream) {
-  RARC_REQUIRE(d_hidden && d_lens && d_out && n_seq > 0 && seq_len > 0 && hidden % 8 == 0 && hidden <= 1024, RARC_E_INVALID,
+  RARC_REQUIRE(d_hidden && d_lens && d_out && n_seq > 0 && seq_len > 0 && hidden > 0 && hidden % 8 == 0 && hidden <= 1024, RARC_E_INVALID,
                "rarc_enc_pool_mean: bad arguments");
   hipLaunchKernelGGL(rarc_pool_mean_kernel, dim3(n_seq), dim3(256), 0, (hipStream_t)stream, (const half_t*)d_hidden, d_lens,
                      seq_len, hidden, normalize, d_out);
