@@ -1138,6 +1138,48 @@ int rarc_components_finish(int64_t n, int64_t m, void* d_ws, size_t ws_bytes, in
 int rarc_components_limits(int* out4);
 
 /*
+ * Co-occurrence projection: the entity graph a mention map implies — two entities are joined when a chunk mentions both, weighted
+ * by how many chunks do: MATCH (a)<-[:MENTIONS]-(c)-[:MENTIONS]->(b) WHERE id(a) < id(b) RETURN a, b, count(c) — next to the
+ * resident CSR, without an edge list crossing to the host.  The rule (restated by tests/cooccur_ref.py) is in
+ * integers.  The CSR by chunk is taken exactly as rarc_ppr_chunks and rarc_merge_mentions take it, guarded the same way: ranges
+ * clamped to [0, nnz], an entry with an entity outside [0, n) or a weight outside [1, 2^12) skipped and counted.  d_c = the valid
+ * entries of chunk c.  A chunk contributes iff 2 <= d_c <= max_mentions (2 <= max_mentions <= 4096); one of more is counted and
+ * gives nothing.  A contributing chunk gives every two valid entries a < b of its row the value 1 (mode 0, "count") or w_a * w_b
+ * (mode 1, "product", below 2^24); two equal entities in a row (a malformed row) give nothing.  T = sum d_c (d_c - 1) / 2 over the
+ * contributing chunks; W(a, b) = the sum of the values of (a, b) over all chunks.  Every sum is an integer sum over a set: the same
+ * bits for any order of the mentions and from run to run.  An entity id is never used as an index (csrc/cooccur.hip).
+ * Limits: 1 <= n_chunks < 2^31 - 1, 1 <= nnz < 2^31, 2 <= n < 2^31 - 1.  Pointers aligned to their element, workspaces to 256
+ * bytes, each *_workspace_bytes returning 0 for a refused shape; everything is refused before any launch.
+ *
+ * rarc_cooccur_count — every chunk's valid count, its pairs and their exclusive scan (the write offsets), and the lists of the
+ *   chunks of each degree class, into d_ws.  d_out4 int64 [4] = {T, contributing chunks, chunks over max_mentions, entries
+ *   skipped}.  T >= 2^31 (rarc_sort_reduce's count limit) is the caller's to refuse, T == 0 its empty answer: neither may reach
+ *   rarc_cooccur_emit.
+ * rarc_cooccur_emit — after rarc_cooccur_count on the same CSR and d_ws.  d_keys uint64 [T]: key = a << bits | b with bits =
+ *   ceil(log2 n), so key_bits = 2 bits <= 62 is what rarc_sort_reduce is then given; d_values uint32 [T] for mode 1, null (or
+ *   ignored) for mode 0, where every value is 1.  Slots come from the scanned offsets, no atomic cursor: the pairs of a row's
+ *   i-th valid entry are one contiguous run.  A wave expands a chunk of at most 64 valid entries, a workgroup with the row in LDS
+ *   a larger one (rarc_cooccur_limits).  T as rarc_cooccur_count reported it, 1 <= T < 2^31: no slot at or past it is written.
+ *   Two equal entities leave the key a << bits | a (value 0 in mode 1), which rarc_cooccur_edges drops.
+ * rarc_cooccur_edges — d_keys, d_sums uint64 [distinct] as rarc_sort_reduce wrote them (distinct keys ascending, 64-bit sums), 1 <=
+ *   distinct < 2^31; min_weight >= 1.  Keeps the keys with a < b and W >= min_weight, in their order: d_out_pairs int64
+ *   [distinct][2] by (a, b) ascending, d_out_weights uint32 [distinct] (the low 32 bits of W: the largest is reported); d_out3
+ *   int64 [3] = {edges written, largest W over all keys with a < b, edges below min_weight}.  A largest W >= 2^32 (mode 1 only)
+ *   is the caller's to refuse before it uses the result.  Its workspace is rarc_cooccur_edges_workspace_bytes(distinct).
+ * rarc_cooccur_limits — out4 = {largest degree of the wave form, largest max_mentions, bits of a product value, log2 of the T
+ *   limit}.
+ */
+size_t rarc_cooccur_workspace_bytes(int64_t n_chunks, int64_t nnz);
+int rarc_cooccur_count(const int64_t* d_row_ptr, const int32_t* d_ent, const uint32_t* d_w, int64_t n_chunks, int64_t nnz, int64_t n,
+                       int max_mentions, void* d_ws, size_t ws_bytes, int64_t* d_out4, void* stream);
+int rarc_cooccur_emit(const int64_t* d_row_ptr, const int32_t* d_ent, const uint32_t* d_w, int64_t n_chunks, int64_t nnz, int64_t n,
+                      int mode, const void* d_ws, size_t ws_bytes, uint64_t* d_keys, uint32_t* d_values, int64_t total, void* stream);
+size_t rarc_cooccur_edges_workspace_bytes(int64_t distinct);
+int rarc_cooccur_edges(const uint64_t* d_keys, const uint64_t* d_sums, int64_t distinct, int64_t n, int64_t min_weight, void* d_ws,
+                       size_t ws_bytes, int64_t* d_out_pairs, uint32_t* d_out_weights, int64_t* d_out3, void* stream);
+int rarc_cooccur_limits(int* out4);
+
+/*
  * Deleting rows of a resident index: stable in-place compaction.  The reference deletes by clearing the index and
  * embedding every surviving text again (encapsulation/database/vector_db/VectorStore_Faiss.py:374-415); the surviving
  * rows are in HBM already, so here they move down over the holes: row i of the result is the i-th surviving row.

@@ -57,17 +57,22 @@ class HipGraphRetriever(BaseRetriever):
             raise ValueError(f"k must be > 0, got {k!r}")
 
     @classmethod
-    def from_arrays(cls, embedding, entity_embeddings, pairs, mentions, texts: Iterable[str], pair_weights=None, mention_weights=None,
-                    ids: Optional[Iterable[str]] = None, metadatas: Optional[Iterable[Dict[str, Any]]] = None, metric: str = "cosine",
-                    device: int = 0, **kwargs: Any) -> "HipGraphRetriever":
+    def from_arrays(cls, embedding, entity_embeddings, pairs=None, mentions=None, texts: Iterable[str] = (), pair_weights=None,
+                    mention_weights=None, ids: Optional[Iterable[str]] = None, metadatas: Optional[Iterable[Dict[str, Any]]] = None,
+                    metric: str = "cosine", device: int = 0, cooccurrence_weight: str = "count", min_weight: int = 1, max_mentions: int = 64,
+                    **kwargs: Any) -> "HipGraphRetriever":
         """entity_embeddings: float32 [n][d], row i = vertex i; pairs / pair_weights: the entity graph's edges (EntityGraph);
-        mentions / mention_weights: (chunk, entity) links (MentionMap); texts (and ids, metadatas): the chunks, chunk i = text i."""
+        mentions / mention_weights: (chunk, entity) links (MentionMap); texts (and ids, metadatas): the chunks, chunk i = text i.
+        pairs=None: the graph is the co-occurrence projection of the mention map (MentionMap.cooccurrence) —
+        cooccurrence_weight "count" or "product", min_weight and max_mentions as it takes them; with pairs the three are ignored."""
         from ...encapsulation.database.graph_db import EntityGraph, MentionMap
         from ...hip.engine import FlatIndexF16
 
         texts = [str(t) for t in texts]
         if not texts:
             raise ValueError("texts must not be empty")
+        if mentions is None:
+            raise ValueError("mentions must be given: the (chunk, entity) links")
         metadatas = list(metadatas) if metadatas is not None else [{} for _ in texts]
         ids = [str(i) for i in ids] if ids is not None else [str(uuid.uuid4()) for _ in texts]
         if len(metadatas) != len(texts) or len(ids) != len(texts):
@@ -77,8 +82,17 @@ class HipGraphRetriever(BaseRetriever):
         if x.ndim != 2 or x.shape[0] < 2:
             raise ValueError(f"expected [n][d] entity embeddings with n >= 2, got an array of shape {x.shape}")
         n = int(x.shape[0])
-        graph = EntityGraph(n, pairs, weights=pair_weights, device=device)          # (refusals first: the graph and the map
-        mention_map = MentionMap(len(texts), n, mentions, weights=mention_weights, device=device)   # check before anything is stored)
+        if pairs is None:                                                           # (refusals first: the graph and the map
+            from ...encapsulation.database.graph_db.cooccurrence import check_arguments
+
+            if pair_weights is not None:
+                raise ValueError("pair_weights without pairs: the weights of a co-occurrence graph come from the mentions")
+            check_arguments(n, cooccurrence_weight, min_weight, max_mentions)
+            mention_map = MentionMap(len(texts), n, mentions, weights=mention_weights, device=device)   # check before anything is stored)
+            graph = mention_map.cooccurrence(weight=cooccurrence_weight, min_weight=min_weight, max_mentions=max_mentions)
+        else:
+            graph = EntityGraph(n, pairs, weights=pair_weights, device=device)
+            mention_map = MentionMap(len(texts), n, mentions, weights=mention_weights, device=device)
         index = FlatIndexF16(int(x.shape[1]), metric=metric, device=device)
         index.add(x)
         docs = [Document(content=t, metadata=m, id=i) for t, m, i in zip(texts, metadatas, ids)]

@@ -143,6 +143,22 @@ class MentionMap:
         self._cws = None
         return self
 
+    def cooccurrence_pairs(self, weight: str = "count", min_weight: int = 1, max_mentions: int = 64, as_device: bool = False):
+        """The edges of the co-occurrence projection (graph_db/cooccurrence.py): two entities are joined when a chunk
+        mentions both, W(a, b) = the chunks that do (weight="count") or the sum of w_a * w_b over them (weight="product"); a chunk
+        of more than max_mentions mentions gives nothing.  -> Cooccurrence(pairs int64 [m][2] by (a, b) with a < b, weights uint32
+        [m], total_pairs, chunks_skipped, largest_weight); no edge is an empty answer."""
+        from . import cooccurrence as C
+
+        return C.cooccurrence_pairs(self, weight=weight, min_weight=min_weight, max_mentions=max_mentions, as_device=as_device)
+
+    def cooccurrence(self, weight: str = "count", min_weight: int = 1, max_mentions: int = 64):
+        """The co-occurrence projection as an EntityGraph over this map's entities, built on the device from cooccurrence_pairs.
+        ValueError("no two entities share a chunk") when there is no edge."""
+        from . import cooccurrence as C
+
+        return C.cooccurrence(self, weight=weight, min_weight=min_weight, max_mentions=max_mentions)
+
     def check_top_k(self, top_k) -> None:
         if top_k is None:
             return

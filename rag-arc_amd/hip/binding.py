@@ -287,6 +287,13 @@ SIGNATURES = {
     "rarc_components_round": (c_int, [c_void_p, c_size_t, c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
     "rarc_components_finish": (c_int, [c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rarc_components_limits": (c_int, [ctypes.POINTER(c_int)]),
+    "rarc_cooccur_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "rarc_cooccur_count": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "rarc_cooccur_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                  c_int64, c_void_p]),
+    "rarc_cooccur_edges_workspace_bytes": (c_size_t, [c_int64]),
+    "rarc_cooccur_edges": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_cooccur_limits": (c_int, [ctypes.POINTER(c_int)]),
     "rarc_compact_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
     "rarc_vmem_create": (c_int, [c_int, c_size_t, c_size_t, c_size_t, ctypes.POINTER(c_void_p)]),
     "rarc_vmem_grow": (c_int, [c_void_p, c_size_t]),
