@@ -622,6 +622,64 @@ int rarc_lm_embed_last_prefixed(const RarcLmModel* model, const int32_t* d_ids, 
                                 size_t ws_bytes, float* d_out, int64_t ld_out, void* stream);
 
 /*
+ * Decoder layer pieces — each kernel of the forward above alone, launched through the dispatch the forward itself uses (the
+ * tests compare every one with a float64 reference; the GEMMs between them are rarc_enc_gemm).  fp16 tensors as uint16 bits.
+ *   rarc_lm_rope_table    : d_table [n_rows][head_dim]: cos of the head_dim/2 pairs, then their sin, of angle row * theta^(-2i/head_dim)
+ *   rarc_lm_rmsnorm       : d_delta != null: x += delta (one fp16 rounding, WRITTEN BACK to d_x); d_y != null:
+ *                           y = half(w * half(x * rsqrt(mean(x^2) + eps))); d_y = null only adds (d_w may then be null)
+ *   rarc_lm_rowscale_parts: r[t] = rsqrt(sum(d_ssq[t][0..n_parts)) / hidden + eps): the row scales from the partial sums of
+ *                           squares (one per 32 columns) the residual GEMM epilogue leaves; n_parts = hidden / 32
+ *   rarc_lm_swiglu        : out[t][j] = half(half(silu(g)) * u) from d_gate_up [n_rows][2*inter], columns in groups of 16: 8 gates,
+ *                           then the 8 ups of the same features
+ *   rarc_lm_attention     : ctx [n_seq*seq_len][n_q*head_dim] from the fused q|k|v rows [n_seq*seq_len][(n_q+2*n_kv)*head_dim]:
+ *                           per-head RMSNorm (d_q_norm / d_k_norm [head_dim]) + rotary embedding of q and k, causal softmax
+ *                           over the keys of a left-padded sequence, optionally after the raw k|v rows of a shared prefix
+ *                           (d_prefix_kv [n_prefix][prefix_len][2*n_kv*head_dim], null = none; d_prefix_of [n_seq] in
+ *                           [-1, n_prefix), -1 = no prefix for that sequence; d_prefix_start [n_prefix]).  d_rope: a
+ *                           rarc_lm_rope_table of rope_rows rows.  Keys run in a virtual index u: u < P = prefix_len is cache
+ *                           row u, u >= P own row start + (u - P); query row i sits at u = P + (i - start) and sees
+ *                           [prefix_start, u].  Rotary position of u: u with a prefix, u + start without (the row's index in the
+ *                           padded sequence).  d_start[s] is clamped into [0, seq_len - 1], d_prefix_start[p] into [0, P - 1].
+ *                           `kernel`: 0 = what the forward would run (RARC_LM_ATTN=stream included), 1 = the streaming kernel,
+ *                           2 = the LDS-resident kernel; 2 is refused (RARC_E_UNSUPPORTED) when round32(P + seq_len) keys do not
+ *                           fit (288 keys at head_dim 128, 544 at 64) — no fallback.  n_seq * seq_len need NOT be a multiple
+ *                           of 128 (that is the GEMMs' limit).
+ *                           What is read: of a sequence's own rows before `start` only the q columns (never k | v); of the
+ *                           cache only the rows of prefixes some sequence names, and of those the rows from
+ *                           32 * (prefix_start / 32) on.  Rows in [32 * (prefix_start / 32), prefix_start) and rows of the
+ *                           sequence behind a query take part with probability exactly 0: they MUST BE FINITE (0 * NaN would
+ *                           reach the output), their values do not matter.  Everything else may hold anything, NaN included.
+ *                           A padding query (row i < start) sees no key and gets a ZERO context row without a prefix; with one
+ *                           it sees cache rows [prefix_start, P - (start - i)] (its row is written, nothing ever reads it).
+ *   rarc_lm_last_logits   : d_out fp16 [n_seq][2] = <half(w * half(x * inv)), lm_head[{no_id, yes_id}]> of row
+ *                           s * row_stride + row_off of d_x ([..][hidden]); the forward's two forms: (seq_len, seq_len - 1) and
+ *                           (1, 0).  d_lm_head [vocab][hidden]
+ *   rarc_lm_last_embed    : the same row and roundings, the normed row itself as fp32 (rarc_lm_embed_last's out_dim / normalize /
+ *                           ld_out)
+ *   rarc_lm_gather_last   : d_dst[s] = d_src[s * seq_len + seq_len - 1] for s < n_seq, ZERO rows for n_seq <= s < n_rows; rows of
+ *                           `width` halves
+ * Limits, refused with an error code before anything is launched: every count (n_rows, n_seq, seq_len, hidden, inter, width,
+ * n_q, n_kv, vocab, and n_prefix / prefix_len with a cache) > 0; head_dim 64 or 128; n_q % n_kv == 0; hidden a multiple of 8
+ * (rmsnorm) or of 128 with n_parts == hidden / 32 (rowscale_parts: its partial sums load as float4); inter and width multiples
+ * of 8; rope_rows >= prefix_len + seq_len; prefix_len <= 4096; 0 <= row_off < row_stride; token ids in [0, vocab);
+ * 1 <= out_dim <= hidden, ld_out >= out_dim; n_rows >= n_seq (gather_last); theta > 0, n_rows * head_dim / 2 < 2^31 (rope_table).
+ */
+int rarc_lm_rope_table(int n_rows, int head_dim, float theta, uint16_t* d_table, void* stream);
+int rarc_lm_rmsnorm(uint16_t* d_x, const uint16_t* d_delta, const uint16_t* d_w, float eps, int n_rows, int hidden, uint16_t* d_y,
+                    void* stream);
+int rarc_lm_rowscale_parts(const float* d_ssq, int n_parts, float eps, int n_rows, int hidden, float* d_r, void* stream);
+int rarc_lm_swiglu(const uint16_t* d_gate_up, int n_rows, int inter, uint16_t* d_out, void* stream);
+int rarc_lm_attention(const uint16_t* d_qkv, const int32_t* d_start, int n_seq, int seq_len, int n_q, int n_kv, int head_dim,
+                      const uint16_t* d_q_norm, const uint16_t* d_k_norm, float eps, const uint16_t* d_rope, int rope_rows,
+                      const uint16_t* d_prefix_kv, const int32_t* d_prefix_of, const int32_t* d_prefix_start, int n_prefix,
+                      int prefix_len, int kernel, uint16_t* d_ctx, void* stream);
+int rarc_lm_last_logits(const uint16_t* d_x, const uint16_t* d_final_norm, const uint16_t* d_lm_head, float eps, int n_seq,
+                        int row_stride, int row_off, int hidden, int vocab, int no_id, int yes_id, uint16_t* d_out, void* stream);
+int rarc_lm_last_embed(const uint16_t* d_x, const uint16_t* d_final_norm, float eps, int n_seq, int row_stride, int row_off,
+                       int hidden, int out_dim, int normalize, float* d_out, int64_t ld_out, void* stream);
+int rarc_lm_gather_last(const uint16_t* d_src, int seq_len, int width, int n_seq, int n_rows, uint16_t* d_dst, void* stream);
+
+/*
  * Batch WordPiece tokenisation on the host (no device involved) — what sits between the texts the reference hands to
  * `SentenceTransformer.encode` (core/file_management/embeddings/huggingface.py:116-126) and the encoder forward above: the
  * BERT tokeniser (native and multi-threaded in the reference's dependency too).  Same algorithm as the python restatement

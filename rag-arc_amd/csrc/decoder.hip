@@ -914,6 +914,111 @@ __global__ __launch_bounds__(256) void rarc_lm_gather_last_kernel(const half_t* 
   for (int c = lane; c < W / 8; c += 64) to[c] = r < n_seq ? from[c] : (half8){0};
 }
 
+// ---- launchers: ONE per kernel, shared by lm_forward and by the piece entries at the end of this file (rarc_lm_rmsnorm,
+// rarc_lm_attention, ...: the tests reach every kernel alone through the dispatch the forward ships with) ----------------------
+static int lm_launch_rope_table(int rows, int DH, float theta, half2_t* table, hipStream_t s) {
+  hipLaunchKernelGGL(rarc_lm_rope_table_kernel, dim3((rows * (DH / 2) + 255) / 256), dim3(256), 0, s, rows, DH, theta, table);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+static int lm_launch_rmsnorm(half_t* x, const half_t* delta, const half_t* w, float eps, int n_rows, int H, half_t* y, hipStream_t s) {
+  hipLaunchKernelGGL(rarc_lm_rmsnorm_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, x, delta, w, eps, n_rows, H, y);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+static int lm_launch_rowscale_parts(const float* ssq, int n_parts, float eps, int n_rows, int H, float* r, hipStream_t s) {
+  hipLaunchKernelGGL(rarc_lm_rowscale_parts_kernel, dim3((n_rows + 31) / 32), dim3(256), 0, s, ssq, n_parts, eps, n_rows, H, r);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+static int lm_launch_swiglu(const half_t* gu, int n_rows, int I, half_t* h, int blocks, hipStream_t s) {   // (grid-stride kernel)
+  hipLaunchKernelGGL(rarc_lm_swiglu_kernel, dim3(blocks), dim3(256), 0, s, gu, n_rows, I, h);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+static int lm_launch_gather_last(const half_t* src, int L, int W, int n_seq, int n_rows, half_t* dst, hipStream_t s) {
+  hipLaunchKernelGGL(rarc_lm_gather_last_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, src, L, W, n_seq, n_rows, dst);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+static int lm_launch_last_logits(const half_t* x, const half_t* w_final, const half_t* lm_head, float eps, int n_seq, int row_stride,
+                                 int row_off, int H, int no_id, int yes_id, half_t* out, hipStream_t s) {
+  hipLaunchKernelGGL(rarc_lm_last_logits_kernel, dim3(n_seq), dim3(64), 0, s, x, w_final, lm_head, eps, row_stride, row_off, H, no_id,
+                     yes_id, out);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+static int lm_launch_last_embed(const half_t* x, const half_t* w_final, float eps, int n_seq, int row_stride, int row_off, int H,
+                                int out_dim, int normalize, float* out, long long ld_out, hipStream_t s) {
+  hipLaunchKernelGGL(rarc_lm_last_embed_kernel, dim3(n_seq), dim3(64), 0, s, x, w_final, eps, row_stride, row_off, H, out_dim,
+                     normalize, out, ld_out);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+// The attention dispatch.  Short sequences: all P + seq_len keys of a (sequence, K/V head) resident in LDS
+// (rarc_lm_attention_resident_kernel) when their operand images fit the CU's 160 KiB and the staging registers (<= 5 passes: 288
+// keys at head_dim 128, 544 at 64); everything else streams (rarc_lm_attention_kernel).
+struct LmAttnPlan {
+  int q_blocks, wg_per_kv;   // 32-query blocks per sequence; streaming workgroups per (sequence, K/V head)
+  int kcap, vrow, np;        // resident: key capacity (P + seq_len rounded up to a tile), V^T row pitch, staging passes
+  size_t lds;                // resident: bytes of dynamic LDS
+  bool fits;                 // the resident kernel can take this shape
+};
+static LmAttnPlan lm_attn_plan(int seq_len, int P, int NQ, int NKV, int DH) {
+  LmAttnPlan a;
+  a.q_blocks = (seq_len + 31) / 32;
+  a.wg_per_kv = ((NQ / NKV) * a.q_blocks + 3) / 4;
+  a.kcap = (P + seq_len + 31) / 32 * 32;
+  a.vrow = lm_attn_vrow(a.kcap);
+  a.lds = (size_t)a.kcap * (DH + 8) * 2 + (size_t)DH * a.vrow * 2;
+  const int rpp = DH == 128 ? 64 : 128;                  // K rows one pass of its staging covers
+  a.np = (a.kcap + rpp - 1) / rpp;                       // passes its staging holds in registers (<= 5)
+  a.fits = a.lds <= 160 * 1024 && a.np <= 5;
+  return a;
+}
+static int lm_attn_resident_attr() {   // once per device: the resident kernels may take 160 KiB of dynamic LDS
+  static RarcPerDevice attr_dev;
+  size_t& attr = attr_dev.cur();
+  if (!attr) {
+#define LM_RES_ATTR(DHV, NPV) RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_lm_attention_resident_kernel<DHV, NPV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
+    LM_RES_ATTR(128, 2); LM_RES_ATTR(128, 3); LM_RES_ATTR(128, 4); LM_RES_ATTR(128, 5);
+    LM_RES_ATTR(64, 2); LM_RES_ATTR(64, 3); LM_RES_ATTR(64, 4); LM_RES_ATTR(64, 5);
+#undef LM_RES_ATTR
+    attr = 1;
+  }
+  return RARC_OK;
+}
+// `resident`: only with a.fits and after lm_attn_resident_attr()
+static int lm_launch_attention(const LmAttnPlan& a, bool resident, const half_t* qkv, const int32_t* d_start, int n_seq, int seq_len,
+                               int NQ, int NKV, int DH, const half_t* q_norm, const half_t* k_norm, float eps, const half2_t* rope,
+                               int rope_rows, half_t* ctx, const LmAttnPrefix& pf, hipStream_t s) {
+  if (resident) {
+#define LM_RES_LAUNCH(DHV, NPV)                                                                                              \
+    hipLaunchKernelGGL((rarc_lm_attention_resident_kernel<DHV, NPV>), dim3(n_seq * NKV), dim3(512), a.lds, s, qkv, d_start,     \
+                       seq_len, NQ, NKV, a.q_blocks, q_norm, k_norm, eps, rope, rope_rows, ctx, pf, a.kcap, a.vrow)
+    if (DH == 128) {
+      if (a.np <= 2) LM_RES_LAUNCH(128, 2); else if (a.np == 3) LM_RES_LAUNCH(128, 3);
+      else if (a.np == 4) LM_RES_LAUNCH(128, 4); else LM_RES_LAUNCH(128, 5);
+    } else {
+      if (a.np <= 2) LM_RES_LAUNCH(64, 2); else if (a.np == 3) LM_RES_LAUNCH(64, 3);
+      else if (a.np == 4) LM_RES_LAUNCH(64, 4); else LM_RES_LAUNCH(64, 5);
+    }
+#undef LM_RES_LAUNCH
+  } else if (DH == 128)
+    hipLaunchKernelGGL(rarc_lm_attention_kernel<128>, dim3(n_seq * NKV * a.wg_per_kv), dim3(256), 0, s, qkv, d_start, seq_len, NQ, NKV,
+                       a.q_blocks, a.wg_per_kv, q_norm, k_norm, eps, rope, rope_rows, ctx, pf);
+  else
+    hipLaunchKernelGGL(rarc_lm_attention_kernel<64>, dim3(n_seq * NKV * a.wg_per_kv), dim3(256), 0, s, qkv, d_start, seq_len, NQ, NKV,
+                       a.q_blocks, a.wg_per_kv, q_norm, k_norm, eps, rope, rope_rows, ctx, pf);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+static bool lm_attn_stream_forced() {   // RARC_LM_ATTN=stream forces the streaming kernel (A/B runs, tests; read per call: the
+  const char* e = getenv("RARC_LM_ATTN");   // tests switch it inside one process)
+  return e && !strcmp(e, "stream");
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------
 static inline size_t lm_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -1016,10 +1121,7 @@ static int lm_forward(const RarcLmModel* m, const int32_t* d_ids, const int32_t*
               rarc_gemm_norm_fusable(Tg, 2 * I, H) && rarc_gemm_swiglu_fused(Tg, 2 * I, H) && rarc_gemm_norm_fusable(Tg, H, I);
   for (int l = 0; l < m->n_layers && fuse; ++l) fuse = m->layers[l].qkv_w_folded && m->layers[l].gate_up_w_folded;
   auto row_scales = [&]() -> int {   // from the partial sums the residual epilogue (act 96) left: 4 H / 32 bytes per row instead of 2 H
-    hipLaunchKernelGGL(rarc_lm_rowscale_parts_kernel, dim3((Tg + 31) / 32), dim3(256), 0, s, (const float*)ssq, H / 32, m->rms_eps, Tg, H,
-                       rowscale);
-    RARC_HIP_CHECK(hipGetLastError());
-    return RARC_OK;
+    return lm_launch_rowscale_parts((const float*)ssq, H / 32, m->rms_eps, Tg, H, rowscale, s);
   };
   const int tb = (T + 3) / 4;
 
@@ -1028,45 +1130,26 @@ static int lm_forward(const RarcLmModel* m, const int32_t* d_ids, const int32_t*
   RARC_REQUIRE(rope_rows <= T + 4096, RARC_E_UNSUPPORTED, "%s: prefix of %d rows is too long for this batch", who, P);
   const size_t kv_cols = (size_t)2 * NKV * DH;
   const size_t cache_layer = use ? lm_align((size_t)use->n_prefix * P * kv_cols * 2) : (fill ? lm_align((size_t)T * kv_cols * 2) : 0);
-  hipLaunchKernelGGL(rarc_lm_rope_table_kernel, dim3((rope_rows * (DH / 2) + 255) / 256), dim3(256), 0, s, rope_rows, DH,
-                     m->rope_theta, rope);
-  RARC_HIP_CHECK(hipGetLastError());
+  if (int rc = lm_launch_rope_table(rope_rows, DH, m->rope_theta, rope, s)) return rc;
 
   hipLaunchKernelGGL(rarc_lm_embed_kernel, dim3(tb), dim3(256), 0, s, d_ids, (const half_t*)m->embed, T, H, m->vocab, x);
   RARC_HIP_CHECK(hipGetLastError());
   // last layer on the last positions only, when its compact buffers fit into the (then idle) gate|up buffer
   const int Mp = (n_seq + 127) / 128 * 128;
   const bool last_only = 6 * 256 + (size_t)Mp * ((size_t)QD + 3 * (size_t)H + 3 * (size_t)I) * 2 <= (size_t)T * 2 * I * 2;
-  const int q_blocks = (seq_len + 31) / 32, wg_per_kv = ((NQ / NKV) * q_blocks + 3) / 4;  // attention workgroups per (sequence, K/V head)
-  // short sequences: all P + seq_len keys of a (sequence, K/V head) resident in LDS (rarc_lm_attention_resident_kernel);
-  // RARC_LM_ATTN=stream forces the streaming kernel (A/B runs, tests)
-  const int attn_kcap = (P + seq_len + 31) / 32 * 32, attn_vrow = lm_attn_vrow(attn_kcap);
-  const size_t attn_lds = (size_t)attn_kcap * (DH + 8) * 2 + (size_t)DH * attn_vrow * 2;
-  const char* attn_env = getenv("RARC_LM_ATTN");   // (read per call: the tests switch it inside one process)
-  const bool attn_stream_only = attn_env && !strcmp(attn_env, "stream");
-  const int attn_rpp = DH == 128 ? 64 : 128;                  // K rows one pass of its staging covers
-  const int attn_np = (attn_kcap + attn_rpp - 1) / attn_rpp;   // passes its staging holds in registers (<= 5)
-  const bool resident = !attn_stream_only && attn_lds <= 160 * 1024 && attn_np <= 5;
-  if (resident) {
-    static RarcPerDevice attr_dev;
-    size_t& attr = attr_dev.cur();
-    if (!attr) {
-#define LM_RES_ATTR(DHV, NPV) RARC_HIP_CHECK(hipFuncSetAttribute((const void*)rarc_lm_attention_resident_kernel<DHV, NPV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-      LM_RES_ATTR(128, 2); LM_RES_ATTR(128, 3); LM_RES_ATTR(128, 4); LM_RES_ATTR(128, 5);
-      LM_RES_ATTR(64, 2); LM_RES_ATTR(64, 3); LM_RES_ATTR(64, 4); LM_RES_ATTR(64, 5);
-#undef LM_RES_ATTR
-      attr = 1;
-    }
-  }
+  // short sequences run the LDS-resident attention kernel (lm_attn_plan); RARC_LM_ATTN=stream forces the streaming one
+  const LmAttnPlan attn = lm_attn_plan(seq_len, P, NQ, NKV, DH);
+  const bool resident = !lm_attn_stream_forced() && attn.fits;
+  if (resident)
+    if (int rc = lm_attn_resident_attr()) return rc;
   for (int l = 0; l < m->n_layers; ++l) {
     const RarcLmLayer& Ly = m->layers[l];
     if (fuse && l > 0) {   // x already holds the previous layer's MLP output; its row scales were taken after the down projection
       if (int rc = rarc_gemm_fused_norm((const uint16_t*)x, Ly.qkv_w_folded, rowscale, (uint16_t*)qkv, Tg, QKV, H, 16, stream)) return rc;
     } else {
       // (layer 0: plain norm; later layers: the previous layer's MLP output is added here, then normed)
-      hipLaunchKernelGGL(rarc_lm_rmsnorm_kernel, dim3(tb), dim3(256), 0, s, x, (l && !fuse) ? (const half_t*)delta : (const half_t*)nullptr,
-                         (const half_t*)Ly.in_norm, m->rms_eps, T, H, h);
-      RARC_HIP_CHECK(hipGetLastError());
+      if (int rc = lm_launch_rmsnorm(x, (l && !fuse) ? (const half_t*)delta : (const half_t*)nullptr, (const half_t*)Ly.in_norm,
+                                     m->rms_eps, T, H, h, s)) return rc;
       if (int rc = rarc_enc_gemm_zero_bias((const uint16_t*)h, Ly.qkv_w, m->zero_bias, (uint16_t*)qkv, Tg, QKV, H, 0, stream)) return rc;
     }
     if (fill) {   // mode 1: this layer's raw k | v rows go to the cache
@@ -1077,28 +1160,8 @@ static int lm_forward(const RarcLmModel* m, const int32_t* d_ids, const int32_t*
     }
     LmAttnPrefix pf{nullptr, nullptr, nullptr, 0, (int)kv_cols};
     if (use) pf = LmAttnPrefix{(const half_t*)((const char*)use->cache + (size_t)l * cache_layer), use->pidx, use->pstart, P, (int)kv_cols};
-    if (resident) {
-#define LM_RES_LAUNCH(DHV, NPV)                                                                                              \
-      hipLaunchKernelGGL((rarc_lm_attention_resident_kernel<DHV, NPV>), dim3(n_seq * NKV), dim3(512), attn_lds, s, (const half_t*)qkv, \
-                         d_start, seq_len, NQ, NKV, q_blocks, (const half_t*)Ly.q_norm, (const half_t*)Ly.k_norm, m->rms_eps,    \
-                         (const half2_t*)rope, rope_rows, ctx, pf, attn_kcap, attn_vrow)
-      if (DH == 128) {
-        if (attn_np <= 2) LM_RES_LAUNCH(128, 2); else if (attn_np == 3) LM_RES_LAUNCH(128, 3);
-        else if (attn_np == 4) LM_RES_LAUNCH(128, 4); else LM_RES_LAUNCH(128, 5);
-      } else {
-        if (attn_np <= 2) LM_RES_LAUNCH(64, 2); else if (attn_np == 3) LM_RES_LAUNCH(64, 3);
-        else if (attn_np == 4) LM_RES_LAUNCH(64, 4); else LM_RES_LAUNCH(64, 5);
-      }
-#undef LM_RES_LAUNCH
-    } else if (DH == 128)
-      hipLaunchKernelGGL(rarc_lm_attention_kernel<128>, dim3(n_seq * NKV * wg_per_kv), dim3(256), 0, s, (const half_t*)qkv, d_start,
-                         seq_len, NQ, NKV, q_blocks, wg_per_kv, (const half_t*)Ly.q_norm, (const half_t*)Ly.k_norm, m->rms_eps,
-                         (const half2_t*)rope, rope_rows, ctx, pf);
-    else
-      hipLaunchKernelGGL(rarc_lm_attention_kernel<64>, dim3(n_seq * NKV * wg_per_kv), dim3(256), 0, s, (const half_t*)qkv, d_start,
-                         seq_len, NQ, NKV, q_blocks, wg_per_kv, (const half_t*)Ly.q_norm, (const half_t*)Ly.k_norm, m->rms_eps,
-                         (const half2_t*)rope, rope_rows, ctx, pf);
-    RARC_HIP_CHECK(hipGetLastError());
+    if (int rc = lm_launch_attention(attn, resident, (const half_t*)qkv, d_start, n_seq, seq_len, NQ, NKV, DH, (const half_t*)Ly.q_norm,
+                                     (const half_t*)Ly.k_norm, m->rms_eps, (const half2_t*)rope, rope_rows, ctx, pf, s)) return rc;
 #ifdef LM_DUMP_CTX
     if (l == 0 && getenv("RARC_LM_DUMP_CTX")) {
       hipStreamSynchronize(s);
@@ -1119,33 +1182,23 @@ static int lm_forward(const RarcLmModel* m, const int32_t* d_ids, const int32_t*
       half_t* d_l = (half_t*)cw;                   cw += lm_align((size_t)Mp * H * 2);
       half_t* act_l = (half_t*)cw;                 cw += lm_align((size_t)Mp * I * 2);
       half_t* gu_l = (half_t*)cw;
-      const int gb = (Mp + 3) / 4;
-      hipLaunchKernelGGL(rarc_lm_gather_last_kernel, dim3(gb), dim3(256), 0, s, (const half_t*)ctx, seq_len, QD, n_seq, Mp, ctx_l);
-      hipLaunchKernelGGL(rarc_lm_gather_last_kernel, dim3(gb), dim3(256), 0, s, (const half_t*)x, seq_len, H, n_seq, Mp, x_l);
-      RARC_HIP_CHECK(hipGetLastError());
+      if (int rc = lm_launch_gather_last((const half_t*)ctx, seq_len, QD, n_seq, Mp, ctx_l, s)) return rc;
+      if (int rc = lm_launch_gather_last((const half_t*)x, seq_len, H, n_seq, Mp, x_l, s)) return rc;
       if (int rc = rarc_enc_gemm_zero_bias((const uint16_t*)ctx_l, Ly.o_w, m->zero_bias, (uint16_t*)d_l, Mp, H, QD, 0, stream)) return rc;
-      hipLaunchKernelGGL(rarc_lm_rmsnorm_kernel, dim3(gb), dim3(256), 0, s, x_l, (const half_t*)d_l, (const half_t*)Ly.post_norm,
-                         m->rms_eps, Mp, H, h_l);
-      RARC_HIP_CHECK(hipGetLastError());
+      if (int rc = lm_launch_rmsnorm(x_l, (const half_t*)d_l, (const half_t*)Ly.post_norm, m->rms_eps, Mp, H, h_l, s)) return rc;
       if (rarc_gemm_swiglu_fused(Mp, 2 * I, H)) {
         if (int rc = rarc_enc_gemm_zero_bias((const uint16_t*)h_l, Ly.gate_up_w, m->zero_bias, (uint16_t*)act_l, Mp, 2 * I, H, 3, stream)) return rc;
       } else {
         if (int rc = rarc_enc_gemm_zero_bias((const uint16_t*)h_l, Ly.gate_up_w, m->zero_bias, (uint16_t*)gu_l, Mp, 2 * I, H, 0, stream)) return rc;
-        hipLaunchKernelGGL(rarc_lm_swiglu_kernel, dim3(512), dim3(256), 0, s, (const half_t*)gu_l, Mp, I, act_l);
-        RARC_HIP_CHECK(hipGetLastError());
+        if (int rc = lm_launch_swiglu((const half_t*)gu_l, Mp, I, act_l, 512, s)) return rc;
       }
       if (int rc = rarc_enc_gemm_zero_bias((const uint16_t*)act_l, Ly.down_w, m->zero_bias, (uint16_t*)d_l, Mp, H, I, 0, stream)) return rc;
-      hipLaunchKernelGGL(rarc_lm_rmsnorm_kernel, dim3(gb), dim3(256), 0, s, x_l, (const half_t*)d_l, (const half_t*)nullptr,
-                         m->rms_eps, Mp, H, (half_t*)nullptr);
-      RARC_HIP_CHECK(hipGetLastError());
+      if (int rc = lm_launch_rmsnorm(x_l, (const half_t*)d_l, (const half_t*)nullptr, m->rms_eps, Mp, H, (half_t*)nullptr, s)) return rc;
       if (emb)
-        hipLaunchKernelGGL(rarc_lm_last_embed_kernel, dim3(n_seq), dim3(64), 0, s, (const half_t*)x_l, (const half_t*)m->final_norm,
-                           m->rms_eps, 1, 0, H, emb->out_dim, emb->normalize, emb->out, emb->ld);
-      else
-        hipLaunchKernelGGL(rarc_lm_last_logits_kernel, dim3(n_seq), dim3(64), 0, s, (const half_t*)x_l, (const half_t*)m->final_norm,
-                           (const half_t*)m->lm_head, m->rms_eps, 1, 0, H, no_id, yes_id, (half_t*)d_out_f16);
-      RARC_HIP_CHECK(hipGetLastError());
-      return RARC_OK;
+        return lm_launch_last_embed((const half_t*)x_l, (const half_t*)m->final_norm, m->rms_eps, n_seq, 1, 0, H, emb->out_dim,
+                                    emb->normalize, emb->out, emb->ld, s);
+      return lm_launch_last_logits((const half_t*)x_l, (const half_t*)m->final_norm, (const half_t*)m->lm_head, m->rms_eps, n_seq, 1, 0,
+                                   H, no_id, yes_id, (half_t*)d_out_f16, s);
     }
     if (fuse) {
       if (int rc = rarc_gemm_fused_norm((const uint16_t*)ctx, Ly.o_w, m->zero_bias, (uint16_t*)x, Tg, H, QD, 96, stream, ssq)) return rc;
@@ -1157,31 +1210,23 @@ static int lm_forward(const RarcLmModel* m, const int32_t* d_ids, const int32_t*
       continue;
     }
     if (int rc = rarc_enc_gemm_zero_bias((const uint16_t*)ctx, Ly.o_w, m->zero_bias, (uint16_t*)delta, Tg, H, QD, 0, stream)) return rc;
-    hipLaunchKernelGGL(rarc_lm_rmsnorm_kernel, dim3(tb), dim3(256), 0, s, x, (const half_t*)delta, (const half_t*)Ly.post_norm,
-                       m->rms_eps, T, H, h);
-    RARC_HIP_CHECK(hipGetLastError());
+    if (int rc = lm_launch_rmsnorm(x, (const half_t*)delta, (const half_t*)Ly.post_norm, m->rms_eps, T, H, h, s)) return rc;
     if (rarc_gemm_swiglu_fused(Tg, 2 * I, H)) {  // silu(gate)·up in the GEMM's epilogue: the [T][2I] tensor never exists
       if (int rc = rarc_enc_gemm_zero_bias((const uint16_t*)h, Ly.gate_up_w, m->zero_bias, (uint16_t*)act, Tg, 2 * I, H, 3, stream)) return rc;
     } else {
       if (int rc = rarc_enc_gemm_zero_bias((const uint16_t*)h, Ly.gate_up_w, m->zero_bias, (uint16_t*)gu, Tg, 2 * I, H, 0, stream)) return rc;
-      hipLaunchKernelGGL(rarc_lm_swiglu_kernel, dim3(2048), dim3(256), 0, s, (const half_t*)gu, Tg, I, act);
-      RARC_HIP_CHECK(hipGetLastError());
+      if (int rc = lm_launch_swiglu((const half_t*)gu, Tg, I, act, 2048, s)) return rc;
     }
     if (int rc = rarc_enc_gemm_zero_bias((const uint16_t*)act, Ly.down_w, m->zero_bias, (uint16_t*)delta, Tg, H, I, 0, stream)) return rc;
   }
   if (!fuse) {   // the last layer's MLP output joins the residual stream (no norm output wanted: y = null)
-    hipLaunchKernelGGL(rarc_lm_rmsnorm_kernel, dim3(tb), dim3(256), 0, s, x, (const half_t*)delta, (const half_t*)nullptr, m->rms_eps,
-                       T, H, (half_t*)nullptr);
-    RARC_HIP_CHECK(hipGetLastError());
+    if (int rc = lm_launch_rmsnorm(x, (const half_t*)delta, (const half_t*)nullptr, m->rms_eps, T, H, (half_t*)nullptr, s)) return rc;
   }
   if (emb)
-    hipLaunchKernelGGL(rarc_lm_last_embed_kernel, dim3(n_seq), dim3(64), 0, s, (const half_t*)x, (const half_t*)m->final_norm,
-                       m->rms_eps, seq_len, seq_len - 1, H, emb->out_dim, emb->normalize, emb->out, emb->ld);
-  else
-    hipLaunchKernelGGL(rarc_lm_last_logits_kernel, dim3(n_seq), dim3(64), 0, s, (const half_t*)x, (const half_t*)m->final_norm,
-                       (const half_t*)m->lm_head, m->rms_eps, seq_len, seq_len - 1, H, no_id, yes_id, (half_t*)d_out_f16);
-  RARC_HIP_CHECK(hipGetLastError());
-  return RARC_OK;
+    return lm_launch_last_embed((const half_t*)x, (const half_t*)m->final_norm, m->rms_eps, n_seq, seq_len, seq_len - 1, H, emb->out_dim,
+                                emb->normalize, emb->out, emb->ld, s);
+  return lm_launch_last_logits((const half_t*)x, (const half_t*)m->final_norm, (const half_t*)m->lm_head, m->rms_eps, n_seq, seq_len,
+                               seq_len - 1, H, no_id, yes_id, (half_t*)d_out_f16, s);
 }
 
 extern "C" int rarc_lm_yes_no_logits(const RarcLmModel* m, const int32_t* d_ids, const int32_t* d_start, int n_seq,
@@ -1231,4 +1276,104 @@ extern "C" int rarc_lm_embed_last_prefixed(const RarcLmModel* m, const int32_t* 
   const LmPrefixUse use{(const half_t*)d_cache, d_prefix_of, d_prefix_start, n_prefix, prefix_len};
   const LmEmbedOut emb{d_out, (long long)ld_out, out_dim, normalize ? 1 : 0, "rarc_lm_embed_last_prefixed"};
   return lm_forward(m, d_ids, d_start, n_seq, seq_len, 0, 0, d_ws, ws_bytes, nullptr, stream, &use, nullptr, &emb);
+}
+
+// ---- the layer pieces alone (include/rarc.h: "Decoder layer pieces"): one kernel per call through the launchers lm_forward
+// uses, so that a test compares each with a float64 reference at its own edges.  Everything a kernel cannot take is refused
+// here, before any launch. ----------------------------------------------------------------------------------------------------
+extern "C" int rarc_lm_rope_table(int n_rows, int head_dim, float theta, uint16_t* d_table, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_table, RARC_E_INVALID, "rarc_lm_rope_table: null pointer");
+  RARC_REQUIRE(n_rows > 0 && theta > 0.f && theta <= 3.0e38f, RARC_E_INVALID, "rarc_lm_rope_table: n_rows and theta must be positive");
+  RARC_REQUIRE((head_dim == 64 || head_dim == 128) && (long long)n_rows * (head_dim / 2) < (1ll << 31), RARC_E_UNSUPPORTED,
+               "rarc_lm_rope_table: head_dim must be 64 or 128 and n_rows * head_dim / 2 < 2^31");
+  return lm_launch_rope_table(n_rows, head_dim, theta, (half2_t*)d_table, (hipStream_t)stream);
+}
+
+extern "C" int rarc_lm_rmsnorm(uint16_t* d_x, const uint16_t* d_delta, const uint16_t* d_w, float eps, int n_rows, int hidden,
+                               uint16_t* d_y, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_x && (d_w || !d_y), RARC_E_INVALID, "rarc_lm_rmsnorm: null pointer");
+  RARC_REQUIRE(n_rows > 0 && hidden > 0 && hidden % 8 == 0, RARC_E_UNSUPPORTED,
+               "rarc_lm_rmsnorm: n_rows must be positive and hidden a positive multiple of 8");
+  return lm_launch_rmsnorm((half_t*)d_x, (const half_t*)d_delta, (const half_t*)d_w, eps, n_rows, hidden, (half_t*)d_y, (hipStream_t)stream);
+}
+
+extern "C" int rarc_lm_rowscale_parts(const float* d_ssq, int n_parts, float eps, int n_rows, int hidden, float* d_r, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_ssq && d_r, RARC_E_INVALID, "rarc_lm_rowscale_parts: null pointer");
+  RARC_REQUIRE(n_rows > 0 && hidden > 0 && hidden % 128 == 0 && n_parts == hidden / 32, RARC_E_UNSUPPORTED,
+               "rarc_lm_rowscale_parts: n_rows must be positive, hidden a positive multiple of 128 and n_parts = hidden / 32");
+  return lm_launch_rowscale_parts(d_ssq, n_parts, eps, n_rows, hidden, d_r, (hipStream_t)stream);
+}
+
+extern "C" int rarc_lm_swiglu(const uint16_t* d_gate_up, int n_rows, int inter, uint16_t* d_out, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_gate_up && d_out, RARC_E_INVALID, "rarc_lm_swiglu: null pointer");
+  RARC_REQUIRE(n_rows > 0 && inter > 0 && inter % 8 == 0, RARC_E_UNSUPPORTED,
+               "rarc_lm_swiglu: n_rows must be positive and inter a positive multiple of 8");
+  return lm_launch_swiglu((const half_t*)d_gate_up, n_rows, inter, (half_t*)d_out, 2048, (hipStream_t)stream);
+}
+
+extern "C" int rarc_lm_attention(const uint16_t* d_qkv, const int32_t* d_start, int n_seq, int seq_len, int n_q, int n_kv, int head_dim,
+                                 const uint16_t* d_q_norm, const uint16_t* d_k_norm, float eps, const uint16_t* d_rope, int rope_rows,
+                                 const uint16_t* d_prefix_kv, const int32_t* d_prefix_of, const int32_t* d_prefix_start, int n_prefix,
+                                 int prefix_len, int kernel, uint16_t* d_ctx, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_qkv && d_start && d_q_norm && d_k_norm && d_rope && d_ctx, RARC_E_INVALID, "rarc_lm_attention: null pointer");
+  RARC_REQUIRE(!d_prefix_kv || (d_prefix_of && d_prefix_start), RARC_E_INVALID, "rarc_lm_attention: null pointer (prefix)");
+  RARC_REQUIRE(n_seq > 0 && seq_len > 0, RARC_E_INVALID, "rarc_lm_attention: empty batch");
+  RARC_REQUIRE((head_dim == 64 || head_dim == 128) && n_q > 0 && n_kv > 0 && n_q % n_kv == 0, RARC_E_UNSUPPORTED,
+               "rarc_lm_attention: head_dim must be 64 or 128 and the q heads a multiple of the kv heads");
+  RARC_REQUIRE(kernel >= 0 && kernel <= 2, RARC_E_INVALID, "rarc_lm_attention: kernel must be 0 (the forward's choice), 1 (streaming) or 2 (resident)");
+  const int P = d_prefix_kv ? prefix_len : 0;
+  if (d_prefix_kv)
+    RARC_REQUIRE(n_prefix > 0 && prefix_len > 0 && prefix_len <= 4096, RARC_E_INVALID, "rarc_lm_attention: bad prefix shape");
+  RARC_REQUIRE((long long)n_seq * seq_len < (1ll << 31) && (long long)n_seq * n_kv * (((long long)(n_q / n_kv) * ((seq_len + 31) / 32) + 3) / 4) < (1ll << 31),
+               RARC_E_UNSUPPORTED, "rarc_lm_attention: n_seq*seq_len must be below 2^31");
+  RARC_REQUIRE(rope_rows >= P + seq_len, RARC_E_INVALID, "rarc_lm_attention: the rotary table needs prefix_len + seq_len = %d rows (got %d)",
+               P + seq_len, rope_rows);
+  const LmAttnPlan attn = lm_attn_plan(seq_len, P, n_q, n_kv, head_dim);
+  RARC_REQUIRE(kernel != 2 || attn.fits, RARC_E_UNSUPPORTED,
+               "rarc_lm_attention: %d keys do not fit the resident kernel (288 at head_dim 128, 544 at 64)", attn.kcap);
+  const bool resident = kernel == 2 || (kernel == 0 && !lm_attn_stream_forced() && attn.fits);
+  if (resident)
+    if (int rc = lm_attn_resident_attr()) return rc;
+  LmAttnPrefix pf{nullptr, nullptr, nullptr, 0, 2 * n_kv * head_dim};
+  if (d_prefix_kv) pf = LmAttnPrefix{(const half_t*)d_prefix_kv, d_prefix_of, d_prefix_start, P, 2 * n_kv * head_dim};
+  return lm_launch_attention(attn, resident, (const half_t*)d_qkv, d_start, n_seq, seq_len, n_q, n_kv, head_dim, (const half_t*)d_q_norm,
+                             (const half_t*)d_k_norm, eps, (const half2_t*)d_rope, rope_rows, (half_t*)d_ctx, pf, (hipStream_t)stream);
+}
+
+extern "C" int rarc_lm_last_logits(const uint16_t* d_x, const uint16_t* d_final_norm, const uint16_t* d_lm_head, float eps, int n_seq,
+                                   int row_stride, int row_off, int hidden, int vocab, int no_id, int yes_id, uint16_t* d_out,
+                                   void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_x && d_final_norm && d_lm_head && d_out, RARC_E_INVALID, "rarc_lm_last_logits: null pointer");
+  RARC_REQUIRE(n_seq > 0 && hidden > 0 && row_stride > 0 && row_off >= 0 && row_off < row_stride, RARC_E_INVALID,
+               "rarc_lm_last_logits: n_seq, hidden and row_stride must be positive and row_off lie in [0, row_stride)");
+  RARC_REQUIRE(vocab > 0 && no_id >= 0 && yes_id >= 0 && no_id < vocab && yes_id < vocab, RARC_E_INVALID,
+               "rarc_lm_last_logits: token ids outside the vocabulary");
+  return lm_launch_last_logits((const half_t*)d_x, (const half_t*)d_final_norm, (const half_t*)d_lm_head, eps, n_seq, row_stride, row_off,
+                               hidden, no_id, yes_id, (half_t*)d_out, (hipStream_t)stream);
+}
+
+extern "C" int rarc_lm_last_embed(const uint16_t* d_x, const uint16_t* d_final_norm, float eps, int n_seq, int row_stride, int row_off,
+                                  int hidden, int out_dim, int normalize, float* d_out, int64_t ld_out, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_x && d_final_norm && d_out, RARC_E_INVALID, "rarc_lm_last_embed: null pointer");
+  RARC_REQUIRE(n_seq > 0 && hidden > 0 && row_stride > 0 && row_off >= 0 && row_off < row_stride, RARC_E_INVALID,
+               "rarc_lm_last_embed: n_seq, hidden and row_stride must be positive and row_off lie in [0, row_stride)");
+  RARC_REQUIRE(out_dim >= 1 && out_dim <= hidden && ld_out >= out_dim, RARC_E_INVALID,
+               "rarc_lm_last_embed: out_dim outside [1, hidden] or ld_out smaller than out_dim");
+  return lm_launch_last_embed((const half_t*)d_x, (const half_t*)d_final_norm, eps, n_seq, row_stride, row_off, hidden, out_dim,
+                              normalize ? 1 : 0, d_out, (long long)ld_out, (hipStream_t)stream);
+}
+
+extern "C" int rarc_lm_gather_last(const uint16_t* d_src, int seq_len, int width, int n_seq, int n_rows, uint16_t* d_dst, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_src && d_dst, RARC_E_INVALID, "rarc_lm_gather_last: null pointer");
+  RARC_REQUIRE(seq_len > 0 && n_seq > 0 && n_rows >= n_seq && width > 0 && width % 8 == 0, RARC_E_UNSUPPORTED,
+               "rarc_lm_gather_last: seq_len and n_seq must be positive, n_rows >= n_seq and width a positive multiple of 8");
+  return lm_launch_gather_last((const half_t*)d_src, seq_len, width, n_seq, n_rows, (half_t*)d_dst, (hipStream_t)stream);
 }

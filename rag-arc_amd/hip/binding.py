@@ -192,6 +192,18 @@ SIGNATURES = {
                                    c_void_p]),
     "rarc_lm_embed_last_prefixed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                             c_int, c_int, c_void_p, c_size_t, c_void_p, c_int64, c_void_p]),
+    # the decoder's layer pieces alone (include/rarc.h: "Decoder layer pieces")
+    "rarc_lm_rope_table": (c_int, [c_int, c_int, c_float, c_void_p, c_void_p]),
+    "rarc_lm_rmsnorm": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p]),
+    "rarc_lm_rowscale_parts": (c_int, [c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_void_p]),
+    "rarc_lm_swiglu": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "rarc_lm_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "rarc_lm_last_logits": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                    c_void_p]),
+    "rarc_lm_last_embed": (c_int, [c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64,
+                                   c_void_p]),
+    "rarc_lm_gather_last": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "rarc_wordpiece_create": (c_int, [ctypes.c_char_p, c_size_t, c_int, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                       ctypes.c_char_p, ctypes.c_char_p, c_size_t, c_int, ctypes.POINTER(c_void_p)]),
     "rarc_wordpiece_destroy": (None, [c_void_p]),
