@@ -1111,6 +1111,40 @@ int rarc_khop_path_edges(int64_t n, int64_t m, int nq, int hops, const void* d_w
 int rarc_khop_paths_limits(int* out3);
 
 /*
+ * Typed traversal: MATCH (s)-[:CAUSAL|SEQUENTIAL*..h]-(v) — k-hop over the relation types each query allows, still one launch
+ * for a batch of mixed filters.  The rule (restated by tests/typed_ref.py): a type is an integer in [0, 32); an
+ * undirected pair carries a uint32 mask, the OR of 1 << t over the relations that join it; query q carries a uint32 filter F_q
+ * and may cross a pair iff mask & F_q != 0 (a pair of mask 0 is crossed by nobody); hop_q(v) is the fewest crossable edges from
+ * any seed of q to v and a seed has hop 0 whatever its filter.  The state is the one rarc_khop_seed starts and every k-hop reader
+ * takes: rarc_khop_counts, _levels, _list, _chunks, _paths read a typed traversal unchanged.  Every join is an AND or an OR: the
+ * same bits for any order of the pairs and any batch.
+ *
+ * rarc_graph_types — the typed adjacency of a graph rarc_graph_csr built, in d_out (rarc_graph_types_workspace_bytes(n, m)
+ *   bytes, 0 for a refused shape): t_adj int32 [2m] | t_mask uint32 [2m] | cursor uint32 [n] | bad u32, slot arrays of their own
+ *   over the blob's row_ptr (the slot order of the blob's adj is not reproducible, so nothing can be aligned to it).  d_pairs is
+ *   THE pair list the graph was built from, d_masks uint32 [m] beside it; a pair rarc_graph_csr skipped is skipped.  A pair that
+ *   finds a row full is not written and counted: the entry waits for the stream and returns RARC_E_INVALID if there was one.
+ * rarc_khop_step_typed — rarc_khop_step under d_filters uint32 [nq] on the device, over d_types; the same `grew` word.
+ * rarc_khop_edges_typed, rarc_khop_path_edges_typed — rarc_khop_edges and rarc_khop_path_edges for a typed table: d_rel_types
+ *   int32 [r] holds a type id per row (one outside [0, 32) is in no answer) or, with rel_masks = 1, the row's uint32 mask; row e
+ *   is listed for q only if F_q holds its type (its mask & F_q != 0).  For paths the caller repeats the one filter per pair.
+ * Limits and alignment as the untyped entries'; d_types 256-byte aligned, filters, masks and row types 4; refused before any
+ * launch.
+ */
+size_t rarc_graph_types_workspace_bytes(int64_t n, int64_t m);
+int rarc_graph_types(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, const int64_t* d_pairs, const uint32_t* d_masks,
+                     void* d_out, size_t out_bytes, void* stream);
+int rarc_khop_step_typed(const void* d_graph, size_t graph_bytes, const void* d_types, size_t types_bytes, const uint32_t* d_filters,
+                         int64_t n, int64_t m, int nq, int hops, int hop, void* d_ws, size_t ws_bytes, uint32_t* d_grew_out, void* stream);
+int rarc_khop_edges_typed(int64_t n, int64_t m, int nq, int hops, const void* d_ws, size_t ws_bytes, const int64_t* d_rel, int64_t r,
+                          const int32_t* d_rel_types, int rel_masks, const uint32_t* d_filters, int max_edges, void* d_ews, size_t ews_bytes,
+                          int64_t* d_out_ids, int32_t* d_out_levels, int32_t* d_out_count, int32_t* d_out_level_counts, void* stream);
+int rarc_khop_path_edges_typed(int64_t n, int64_t m, int nq, int hops, const void* d_ws, size_t ws_bytes, const int64_t* d_rel, int64_t r,
+                               const int32_t* d_rel_types, int rel_masks, const uint32_t* d_filters, int max_edges, void* d_ews,
+                               size_t ews_bytes, int64_t* d_out_ids, int32_t* d_out_levels, int32_t* d_out_count,
+                               int32_t* d_out_level_counts, void* stream);
+
+/*
  * Entity merging: step 4 of the reference's de-duplication (Base_Neo4j.py:714-890, _merge_clusters) — every class of a labelling
  * becomes one entity, and the pair list, the mention CSR and the relation table are contracted onto the survivors without
  * leaving the device.  The rule (restated by tests/merge_ref.py) is in integers; every result is the same bits for

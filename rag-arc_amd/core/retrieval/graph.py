@@ -11,7 +11,9 @@ what `MultiPathRetriever` reads with getattr(d, "score", 1.0).  No CPU fallback:
 
 `expansion="k_hop"` replaces the PageRank by a traversal: the chunks are ranked by their mentions of the entities within `hops`
 edges of the seeds, a mention one hop nearer counting `decay` times as much (`EntityGraph.expand_chunks`) — the
-expansion a Neo4j-backed local search writes MATCH (s)-[*..h]-(v).  The default, "ppr", is what it was."""
+expansion a Neo4j-backed local search writes MATCH (s)-[*..h]-(v).  The default, "ppr", is what it was.  With
+`relation_types=` (a graph built with `pair_types=`) the traversal crosses only the relation types a query allows,
+MATCH (s)-[:CAUSAL|SEQUENTIAL*..h]-(v), still one launch for a batch of mixed filters."""
 import dataclasses
 import uuid
 from typing import Any, Dict, Iterable, List, Optional
@@ -25,11 +27,12 @@ from .base import BaseRetriever
 class HipGraphRetriever(BaseRetriever):
     def __init__(self, embedding, index, graph, mentions, docs: List[Document], k: int = 5, seeds_per_query: int = 5,
                  damping: float = 0.85, max_iterations: int = 20, tolerance: float = 0.0, expansion: str = "ppr", hops: int = 2,
-                 decay=None, **kwargs):
+                 decay=None, relation_types=None, **kwargs):
         super().__init__(**kwargs)
         self._validate_k(k)
         if expansion not in ("ppr", "k_hop"):
             raise ValueError(f"expansion must be 'ppr' or 'k_hop', got {expansion!r}")
+        self._check_relation_types(expansion, graph, relation_types)
         docs = list(docs)
         if int(index.ntotal) != graph.n:
             raise ValueError(f"the index holds {int(index.ntotal)} rows and the graph {graph.n} vertices: row i must be vertex i")
@@ -45,11 +48,26 @@ class HipGraphRetriever(BaseRetriever):
         self.seeds_per_query, self.damping = int(seeds_per_query), float(damping)
         self.max_iterations, self.tolerance = int(max_iterations), float(tolerance)
         self.expansion, self.hops, self.decay = expansion, int(hops), None
+        self.relation_types = relation_types
         if expansion == "k_hop":                                                 # the refusals of expand_chunks, up front
             from ...encapsulation.database.graph_db.neighbourhood import check_decay, check_hops
 
             self.hops = check_hops(hops)
             self.decay = check_decay(decay, self.hops)
+
+    @staticmethod
+    def _check_relation_types(expansion, graph, relation_types, nq=None) -> None:
+        """the refusals of a typed expand_chunks, before anything is embedded; nq: the queries the filters must fit"""
+        if relation_types is None:
+            return
+        if expansion != "k_hop":
+            raise ValueError("relation_types with expansion='ppr': typed personalized PageRank is not built (the weighted degrees would "
+                             "differ per query); use expansion='k_hop'")
+        from ...encapsulation.database.graph_db.neighbourhood import check_typed, spread_filters
+
+        filters = check_typed(graph, relation_types)
+        if nq:
+            spread_filters(filters, nq)
 
     @staticmethod
     def _validate_k(k) -> None:
@@ -60,11 +78,12 @@ class HipGraphRetriever(BaseRetriever):
     def from_arrays(cls, embedding, entity_embeddings, pairs=None, mentions=None, texts: Iterable[str] = (), pair_weights=None,
                     mention_weights=None, ids: Optional[Iterable[str]] = None, metadatas: Optional[Iterable[Dict[str, Any]]] = None,
                     metric: str = "cosine", device: int = 0, cooccurrence_weight: str = "count", min_weight: int = 1, max_mentions: int = 64,
-                    **kwargs: Any) -> "HipGraphRetriever":
+                    pair_types=None, **kwargs: Any) -> "HipGraphRetriever":
         """entity_embeddings: float32 [n][d], row i = vertex i; pairs / pair_weights: the entity graph's edges (EntityGraph);
         mentions / mention_weights: (chunk, entity) links (MentionMap); texts (and ids, metadatas): the chunks, chunk i = text i.
         pairs=None: the graph is the co-occurrence projection of the mention map (MentionMap.cooccurrence) —
-        cooccurrence_weight "count" or "product", min_weight and max_mentions as it takes them; with pairs the three are ignored."""
+        cooccurrence_weight "count" or "product", min_weight and max_mentions as it takes them; with pairs the three are ignored.
+        pair_types: one relation type per pair, an integer in [0, 32) (EntityGraph(types=)): what relation_types= filters on."""
         from ...encapsulation.database.graph_db import EntityGraph, MentionMap
         from ...hip.engine import FlatIndexF16
 
@@ -87,11 +106,13 @@ class HipGraphRetriever(BaseRetriever):
 
             if pair_weights is not None:
                 raise ValueError("pair_weights without pairs: the weights of a co-occurrence graph come from the mentions")
+            if pair_types is not None:
+                raise ValueError("pair_types without pairs: a co-occurrence graph has no relation types")
             check_arguments(n, cooccurrence_weight, min_weight, max_mentions)
             mention_map = MentionMap(len(texts), n, mentions, weights=mention_weights, device=device)   # check before anything is stored)
             graph = mention_map.cooccurrence(weight=cooccurrence_weight, min_weight=min_weight, max_mentions=max_mentions)
         else:
-            graph = EntityGraph(n, pairs, weights=pair_weights, device=device)
+            graph = EntityGraph(n, pairs, weights=pair_weights, types=pair_types, device=device)
             mention_map = MentionMap(len(texts), n, mentions, weights=mention_weights, device=device)
         index = FlatIndexF16(int(x.shape[1]), metric=metric, device=device)
         index.add(x)
@@ -114,15 +135,18 @@ class HipGraphRetriever(BaseRetriever):
     def batch_invoke(self, inputs: List[str], **kwargs: Any) -> List[List[Document]]:
         """invoke() for a list of queries: one embedding batch, one search and one PageRank run (or one traversal, with
         expansion="k_hop") per 256 queries.  Element i equals invoke(inputs[i], **kwargs) — every query is ranked on its own,
-        by integer arithmetic."""
+        by integer arithmetic.  relation_types= overrides the constructor's: one filter for all inputs or one per input."""
         inputs = list(inputs)
         k = kwargs.get("k", self.k)
         self._validate_k(k)
+        relation_types = kwargs.get("relation_types", self.relation_types)
+        self._check_relation_types(self.expansion, self.graph, relation_types, len(inputs))
         if not inputs:
             return []
         if self.expansion == "k_hop":
             ids, scores, counts = self.graph.expand_chunks(self.index, self._embed(inputs), self.mentions, seeds_per_query=self.seeds_per_query,
-                                                           hops=self.hops, decay=self.decay, top_k=min(k, len(self.docs)))
+                                                           hops=self.hops, decay=self.decay, top_k=min(k, len(self.docs)),
+                                                           relation_types=relation_types)
         else:
             ids, scores, counts = self.graph.retrieve_chunks(self.index, self._embed(inputs), self.mentions,
                                                              seeds_per_query=self.seeds_per_query, top_k=min(k, len(self.docs)),

@@ -49,7 +49,18 @@
 //   path edges  row (a, b) is at level i + 1 iff one end is at position i and the other at i + 1 — on the path state the two
 //               ends share a word, E_{i+1} = P_i(a) & P_{i+1}(b) | P_{i+1}(a) & P_i(b) — through the count / scan / write of `edges`
 //
+// Typed traversal (tests/typed_ref.py restates it): MATCH (s)-[:CAUSAL|SEQUENTIAL*..h]-(v).  An edge carries a
+// uint32 mask M of its relation types, a query a uint32 filter F_q, and q may cross the edge iff M & F_q != 0; a seed has hop 0
+// whatever its filter.  With Q_t the queries whose filter holds t and A(M) = OR over t in M of Q_t,
+//   step   level[hop](v) = (OR over v's slots (u, M) of level[hop - 1](u) & A(M)) & ~seen(v);   seen(v) |= level[hop](v)
+// in the same launch shapes, over a second pair of slot arrays (rarc_graph_types) that holds neighbour and mask side by side.
+// Q_t is 32 x W words, built in LDS from the filters once a workgroup.  The state is the untyped one, so every reader above
+// takes it unchanged; a row (a, b, t) of a typed relation table additionally needs F_q to hold t, which ANDs its level words
+// with Q_t.  Untyped entries launch the kernels they launched before: the typed ones are instantiations of their own.
+//
 // The workspace is {grew u32 | level totals i32 [256][9]} | seen | level 0 .. hops | tile counts u32 [tiles][hops + 1][W * 64].
+#include <type_traits>
+
 #include "graph_csr.h"
 #include "chunk_ws.h"
 
@@ -61,6 +72,7 @@ constexpr int KHOP_MAX_EDGES = 65536;
 constexpr int KHOP_SPLIT_DEGREE = LV_DEG_WAVE;              // a vertex of more neighbours is split across a workgroup
 constexpr int KHOP_GROUP = 16;                              // lanes that share a vertex of up to KHOP_SPLIT_DEGREE neighbours
 constexpr int KHOP_TILE = 1024;                             // vertices, or relation rows, a wave counts and writes for a list
+constexpr int KHOP_TYPES = 32;                              // relation types: the bits of an edge mask and of a query filter
 constexpr uint32_t KHOP_MAX_DECAY = 1u << 16;
 constexpr size_t KHOP_CTL_BYTES = 256 + (size_t)KHOP_MAX_B * (KHOP_MAX_HOPS + 1) * 4;
 
@@ -124,6 +136,55 @@ __device__ __forceinline__ u64 khop_query_mask(int nq, int word) {
   return left <= 0 ? 0ull : (left >= 64 ? ~0ull : (1ull << left) - 1ull);
 }
 
+// ---- the typed adjacency ------------------------------------------------------------------------------------------
+// t_adj int32 [2m] | t_mask uint32 [2m] | cursor uint32 [n] | bad u32: a second pair of slot arrays over the blob's row_ptr.
+// rarc_graph_csr hands out a row's slots through an atomic cursor, so no array can be aligned to its `adj` afterwards; here the
+// neighbour and the mask of a slot are written together, in one pass over the pair list that built the graph
+struct KhopTypes {
+  int32_t* adj;
+  uint32_t* mask;
+  uint32_t* cursor;
+  uint32_t* bad;
+  size_t bytes;
+};
+static KhopTypes khop_types_carve(const void* base, int64_t n, int64_t m) {
+  char* b = (char*)base;
+  size_t o = 0;
+  KhopTypes t;
+  auto take = [&](size_t bytes) { char* p = b + o; o += lv_align(bytes); return p; };
+  t.adj = (int32_t*)take((size_t)m * 8);
+  t.mask = (uint32_t*)take((size_t)m * 8);
+  t.cursor = (uint32_t*)take((size_t)n * 4);
+  t.bad = (uint32_t*)take(4);
+  t.bytes = o;
+  return t;
+}
+// the rule of lv_edge_ok (csrc/louvain.hip): a pair rarc_graph_csr skipped has no slots and is skipped here too
+__device__ __forceinline__ bool khop_pair_ok(int64_t a, int64_t b, int64_t n) { return a >= 0 && a < b && b < n; }
+
+// a thread per pair: one slot in each end's row, taken through the cursor.  A slot at or beyond the end of the row (or of the
+// arrays) is not written and counted in `bad`: the pair list is not the one the blob was built from
+__global__ __launch_bounds__(256) void khop_types_fill_kernel(const int64_t* __restrict__ pairs, const uint32_t* __restrict__ masks, int64_t m,
+                                                              int64_t n, const int64_t* __restrict__ row_ptr, uint32_t* cursor, int32_t* adj,
+                                                              uint32_t* mask, uint32_t* bad) {
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256) {
+    const int64_t a = pairs[2 * e], b = pairs[2 * e + 1];
+    if (!khop_pair_ok(a, b, n)) continue;
+    const uint32_t mk = masks[e];
+    const int64_t pa = row_ptr[a] + atomicAdd(&cursor[a], 1u), pb = row_ptr[b] + atomicAdd(&cursor[b], 1u);
+    const bool fa = pa >= 0 && pa < row_ptr[a + 1] && pa < 2 * m, fb = pb >= 0 && pb < row_ptr[b + 1] && pb < 2 * m;
+    if (fa) {
+      adj[pa] = (int32_t)b;
+      mask[pa] = mk;
+    }
+    if (fb) {
+      adj[pb] = (int32_t)a;
+      mask[pb] = mk;
+    }
+    if (!fa || !fb) atomicAdd(bad, 1u);
+  }
+}
+
 // ---- seeds ------------------------------------------------------------------------------------------------------------------------
 // one thread per (query, slot); a slot whose vertex lies outside [0, n) is unused
 __global__ __launch_bounds__(256) void khop_seed_kernel(const int64_t* __restrict__ seeds, int nq, int s, int64_t n, int W, u64* seen, u64* level0) {
@@ -151,11 +212,45 @@ struct KhopStepArgs {
   int nq;
 };
 
+// ---- typed traversal: the allow table ----------------------------------------------------------------------------
+// Q_t, the queries whose filter holds type t, as STRIDE words per type in LDS: word w of type t at [t * STRIDE + w].  The 256
+// threads of the workgroup are the 256 queries of a batch, wave w holds word w; a word past the batch is 0.  Ends in a barrier
+template <int STRIDE>
+__device__ __forceinline__ void khop_build_allow(u64* s_allow, const uint32_t* __restrict__ filters, int nq) {
+  static_assert(KHOP_MAX_B == 256 && KHOP_TYPES == 32, "a thread of the workgroup is a query, a lane below 32 stores a type's word");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t f = tid < nq ? filters[tid] : 0u;
+  u64 mine = 0;
+#pragma unroll
+  for (int t = 0; t < KHOP_TYPES; ++t) {
+    const u64 holds = __builtin_amdgcn_ballot_w64((f >> t) & 1u);
+    mine = lane == t ? holds : mine;
+  }
+  if (lane < KHOP_TYPES && wave < STRIDE) s_allow[lane * STRIDE + wave] = mine;
+  __syncthreads();
+}
+// A(M) = the OR of Q_t over the types of mask M, for one word: one LDS read where M has one bit; 0 for M = 0
+template <int STRIDE>
+__device__ __forceinline__ u64 khop_allow(const u64* s_allow, uint32_t mask, int word) {
+  if (!mask) return 0ull;
+  u64 a = s_allow[__builtin_ctz(mask) * STRIDE + word];
+  for (uint32_t rest = mask & (mask - 1u); rest; rest &= rest - 1u) a |= s_allow[__builtin_ctz(rest) * STRIDE + word];
+  return a;
+}
+
+// the typed side of a step: p.adj is then the typed slot array, `mask` lies beside it slot for slot
+struct KhopStepTypes {
+  const uint32_t* mask;
+  const uint32_t* filters;                                  // [nq]
+};
+
 // WP: lanes per neighbour slot, one per word (the power of two >= W).  SPLIT: a workgroup per vertex of a degree list, its
 // waves joined in LDS; otherwise KHOP_GROUP lanes per vertex over every vertex, those of more than KHOP_SPLIT_DEGREE
-// neighbours left to the SPLIT launch
-template <int WP, bool SPLIT>
-__global__ __launch_bounds__(256) void khop_step_kernel(const KhopStepArgs p, const int32_t* __restrict__ list, const int64_t* __restrict__ list_count) {
+// neighbours left to the SPLIT launch.  TYPED: a neighbour's word is ANDed with A(mask of the slot); s_allow is the workgroup's
+// table (32 x WP words), built by the caller
+template <int WP, bool SPLIT, bool TYPED>
+__device__ __forceinline__ void khop_step_body(const KhopStepArgs& p, const int32_t* __restrict__ list, const int64_t* __restrict__ list_count,
+                                               const uint32_t* __restrict__ slot_mask, const u64* s_allow) {
   constexpr int LANES = SPLIT ? 256 : KHOP_GROUP;
   constexpr int NSLOT = LANES / WP;
   constexpr int PER_BLOCK = SPLIT ? 1 : 256 / KHOP_GROUP;
@@ -194,7 +289,12 @@ __global__ __launch_bounds__(256) void khop_step_kernel(const KhopStepArgs p, co
 #pragma unroll 4
       for (int64_t e = slot; e < deg; e += NSLOT) {
         const int32_t u = p.adj[r0 + e];
-        acc |= p.prev[(size_t)u * W + word];
+        if constexpr (TYPED) {                                           // an edge no query still needed may cross: its end's word is not read
+          const u64 allow = khop_allow<WP>(s_allow, slot_mask[r0 + e], word) & need;
+          if (allow) acc |= p.prev[(size_t)u * W + word] & allow;
+        } else {
+          acc |= p.prev[(size_t)u * W + word];
+        }
       }
     }
 #pragma unroll
@@ -215,6 +315,17 @@ __global__ __launch_bounds__(256) void khop_step_kernel(const KhopStepArgs p, co
     }
   }
   if (__builtin_amdgcn_ballot_w64(grew) && lane == 0) atomicOr(p.grew, 1u);
+}
+template <int WP, bool SPLIT>
+__global__ __launch_bounds__(256) void khop_step_kernel(const KhopStepArgs p, const int32_t* __restrict__ list, const int64_t* __restrict__ list_count) {
+  khop_step_body<WP, SPLIT, false>(p, list, list_count, nullptr, nullptr);
+}
+template <int WP, bool SPLIT>
+__global__ __launch_bounds__(256) void khop_step_typed_kernel(const KhopStepArgs p, const int32_t* __restrict__ list,
+                                                              const int64_t* __restrict__ list_count, const KhopStepTypes ty) {
+  __shared__ u64 s_allow[KHOP_TYPES * WP];
+  khop_build_allow<WP>(s_allow, ty.filters, p.nq);
+  khop_step_body<WP, SPLIT, true>(p, list, list_count, ty.mask, s_allow);
 }
 
 // ---- counting: shared by the counts and the list --------------------------------------------------------------------------------
@@ -334,10 +445,26 @@ struct KhopRowWalk {
   }
 };
 
+// the types of the rows of a typed relation table: a row is in q's answer only if F_q holds its type.  `type`
+// holds a type id per row (one outside [0, 32) is allowed to nobody) or, with `masks`, the row's mask as an edge carries it
+struct KhopRowTypes {
+  const int32_t* type;                                                 // [r]
+  const uint32_t* filters;                                             // [nq]
+  int masks;
+};
+constexpr int KHOP_ROW_STRIDE = KHOP_MAX_B / 64;                       // the allow table of the row kernels: every word of a batch
+__device__ __forceinline__ u64 khop_row_allow(const KhopRowTypes& ty, const u64* s_allow, int64_t e, int64_t r, int word) {
+  if (e >= r) return 0ull;
+  const uint32_t t = (uint32_t)ty.type[e];
+  return khop_allow<KHOP_ROW_STRIDE>(s_allow, ty.masks ? t : (t < (uint32_t)KHOP_TYPES ? 1u << t : 0u), word);
+}
+
 // a wave per (tile of relation rows, word): every level of a row in one walk up its ends' words;
-// tiles[tile][h][word * 64 + b] = rows of the tile at level h for query word * 64 + b
-template <bool PATHS>
-__global__ __launch_bounds__(256) void khop_edge_count_kernel(const KhopEdgeBits src, int W, int H, uint32_t* tiles) {
+// tiles[tile][h][word * 64 + b] = rows of the tile at level h for query word * 64 + b.  TYPED: the queries that may not take the
+// row's type are cleared from its words first
+template <bool PATHS, bool TYPED>
+__device__ __forceinline__ void khop_edge_count_body(const KhopEdgeBits& src, int W, int H, uint32_t* tiles, const KhopRowTypes& ty,
+                                                     const u64* s_allow) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t items = khop_tiles(src.r) * W;
   for (int64_t item = (int64_t)blockIdx.x * 4 + wave; item < items; item += (int64_t)gridDim.x * 4) {
@@ -346,7 +473,10 @@ __global__ __launch_bounds__(256) void khop_edge_count_kernel(const KhopEdgeBits
     uint32_t cnt[KHOP_MAX_HOPS + 1] = {};                              // (indexed by unrolled loops only: registers)
     for (int c = 0; c < KHOP_TILE / 64; ++c) {
       size_t ia, ib;
-      const u64 in = src.within(tile * KHOP_TILE + c * 64 + lane, word, W, ia, ib);
+      u64 in = src.within(tile * KHOP_TILE + c * 64 + lane, word, W, ia, ib);
+      if constexpr (TYPED) {
+        if (in) in &= khop_row_allow(ty, s_allow, tile * KHOP_TILE + c * 64 + lane, src.r, word);
+      }
       if (__builtin_amdgcn_ballot_w64(in != 0) == 0) continue;
       KhopRowWalk<PATHS> walk;
 #pragma unroll
@@ -357,6 +487,10 @@ __global__ __launch_bounds__(256) void khop_edge_count_kernel(const KhopEdgeBits
             xa = src.level[src.level_stride * (size_t)h + ia];
             xb = src.level[src.level_stride * (size_t)h + ib];
           }
+          if constexpr (TYPED) {                                       // (untyped: a level is inside `in` already)
+            xa &= in;
+            xb &= in;
+          }
           cnt[h] = khop_count_bits(walk.next(xa, xb), lane, cnt[h]);
         }
       }
@@ -366,14 +500,26 @@ __global__ __launch_bounds__(256) void khop_edge_count_kernel(const KhopEdgeBits
       if (h < H) tiles[((size_t)tile * H + h) * ((size_t)W * 64) + word * 64 + lane] = cnt[h];
   }
 }
+template <bool PATHS>
+__global__ __launch_bounds__(256) void khop_edge_count_kernel(const KhopEdgeBits src, int W, int H, uint32_t* tiles) {
+  khop_edge_count_body<PATHS, false>(src, W, H, tiles, KhopRowTypes{nullptr, nullptr, 0}, nullptr);
+}
+template <bool PATHS>
+__global__ __launch_bounds__(256) void khop_edge_count_typed_kernel(const KhopEdgeBits src, int W, int H, int nq, uint32_t* tiles,
+                                                                    const KhopRowTypes ty) {
+  __shared__ u64 s_allow[KHOP_TYPES * KHOP_ROW_STRIDE];
+  khop_build_allow<KHOP_ROW_STRIDE>(s_allow, ty.filters, nq);
+  khop_edge_count_body<PATHS, true>(src, W, H, tiles, ty, s_allow);
+}
 
 // a wave per (tile, word): the entries of its items, level by level, at offset + rank; block 0 also writes the counts.
 // EDGES: the items are the rows of `rel` and a row's level word is derived from its ends' (PATHS: by the rule of the connecting
-// paths); otherwise they are the vertices
-template <bool EDGES, bool PATHS = false>
-__global__ __launch_bounds__(256) void khop_list_kernel(const u64* __restrict__ level, size_t level_stride, int64_t n, int W, int H, int nq,
-                                                        const uint32_t* __restrict__ tiles, const int32_t* __restrict__ totals, uint32_t max_vertices,
-                                                        int64_t* out_ids, int32_t* out_hops, int32_t* out_count, const KhopRelations rel) {
+// paths); otherwise they are the vertices.  TYPED (EDGES only): a row's word keeps the queries whose filter holds its type
+template <bool EDGES, bool PATHS, bool TYPED>
+__device__ __forceinline__ void khop_list_body(const u64* __restrict__ level, size_t level_stride, int64_t n, int W, int H, int nq,
+                                               const uint32_t* __restrict__ tiles, const int32_t* __restrict__ totals, uint32_t max_vertices,
+                                               int64_t* out_ids, int32_t* out_hops, int32_t* out_count, const KhopRelations& rel,
+                                               const KhopRowTypes& ty, const u64* s_allow) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (blockIdx.x == 0) {
     for (int q = threadIdx.x; q < nq; q += 256) {
@@ -405,6 +551,9 @@ __global__ __launch_bounds__(256) void khop_list_kernel(const u64* __restrict__ 
         u64 x;
         if constexpr (EDGES) x = rows.template word<PATHS>(v, h, word, W);
         else x = v < n ? lv[(size_t)v * W + word] : 0ull;
+        if constexpr (TYPED) {
+          if (x) x &= khop_row_allow(ty, s_allow, v, rel.r, word);
+        }
         if (__builtin_amdgcn_ballot_w64(x != 0) == 0) continue;
         for (int b = 0; b < 64; ++b) {                                 // (b is wave-uniform)
           const bool mine = (x >> b) & 1ull;
@@ -425,6 +574,22 @@ __global__ __launch_bounds__(256) void khop_list_kernel(const u64* __restrict__ 
       }
     }
   }
+}
+template <bool EDGES, bool PATHS = false>
+__global__ __launch_bounds__(256) void khop_list_kernel(const u64* __restrict__ level, size_t level_stride, int64_t n, int W, int H, int nq,
+                                                        const uint32_t* __restrict__ tiles, const int32_t* __restrict__ totals, uint32_t max_vertices,
+                                                        int64_t* out_ids, int32_t* out_hops, int32_t* out_count, const KhopRelations rel) {
+  khop_list_body<EDGES, PATHS, false>(level, level_stride, n, W, H, nq, tiles, totals, max_vertices, out_ids, out_hops, out_count, rel,
+                                      KhopRowTypes{nullptr, nullptr, 0}, nullptr);
+}
+template <bool PATHS>
+__global__ __launch_bounds__(256) void khop_list_typed_kernel(const u64* __restrict__ level, size_t level_stride, int64_t n, int W, int H, int nq,
+                                                              const uint32_t* __restrict__ tiles, const int32_t* __restrict__ totals,
+                                                              uint32_t max_vertices, int64_t* out_ids, int32_t* out_hops, int32_t* out_count,
+                                                              const KhopRelations rel, const KhopRowTypes ty) {
+  __shared__ u64 s_allow[KHOP_TYPES * KHOP_ROW_STRIDE];
+  khop_build_allow<KHOP_ROW_STRIDE>(s_allow, ty.filters, nq);
+  khop_list_body<true, PATHS, true>(level, level_stride, n, W, H, nq, tiles, totals, max_vertices, out_ids, out_hops, out_count, rel, ty, s_allow);
 }
 
 // ---- the dense answer ---------------------------------------------------------------------------------------------------------------
@@ -688,17 +853,49 @@ extern "C" int rarc_khop_seed(int64_t n, int64_t m, const int64_t* d_seeds, int 
   return RARC_OK;
 }
 
-template <int WP>
-static void khop_launch_step(const KhopStepArgs& p, const LvGraph& g, int64_t n, int64_t m, hipStream_t s) {
-  hipLaunchKernelGGL((khop_step_kernel<WP, false>), dim3(lv_grid(n, 256 / KHOP_GROUP, 16384)), dim3(256), 0, s, p, (const int32_t*)nullptr,
-                     (const int64_t*)nullptr);
+// TYPED: the same three launches of khop_step_typed_kernel, `ty` beside the arguments
+template <int WP, bool TYPED = false>
+static void khop_launch_step(const KhopStepArgs& p, const LvGraph& g, int64_t n, int64_t m, hipStream_t s, const KhopStepTypes ty = {}) {
+  auto launch = [&](auto split, unsigned grid, const int32_t* list, const int64_t* count) {
+    constexpr bool SPLIT = decltype(split)::value;
+    if constexpr (TYPED) hipLaunchKernelGGL((khop_step_typed_kernel<WP, SPLIT>), dim3(grid), dim3(256), 0, s, p, list, count, ty);
+    else hipLaunchKernelGGL((khop_step_kernel<WP, SPLIT>), dim3(grid), dim3(256), 0, s, p, list, count);
+  };
+  launch(std::false_type{}, lv_grid(n, 256 / KHOP_GROUP, 16384), nullptr, nullptr);
   const int64_t dmax = lv_max_degree(n, m);              // no vertex of this graph has more neighbours: skip the lists that must be empty
-  if (dmax > LV_DEG_WAVE)
-    hipLaunchKernelGGL((khop_step_kernel<WP, true>), dim3(lv_grid(n, 1, 2048)), dim3(256), 0, s, p, (const int32_t*)g.list[2],
-                       (const int64_t*)&g.hdr[LV_H_LIST + 2]);
-  if (dmax > LV_DEG_LDS)
-    hipLaunchKernelGGL((khop_step_kernel<WP, true>), dim3(lv_grid(n / LV_DEG_LDS + 1, 1, 2048)), dim3(256), 0, s, p, (const int32_t*)g.list[3],
-                       (const int64_t*)&g.hdr[LV_H_LIST + 3]);
+  if (dmax > LV_DEG_WAVE) launch(std::true_type{}, lv_grid(n, 1, 2048), g.list[2], &g.hdr[LV_H_LIST + 2]);
+  if (dmax > LV_DEG_LDS) launch(std::true_type{}, lv_grid(n / LV_DEG_LDS + 1, 1, 2048), g.list[3], &g.hdr[LV_H_LIST + 3]);
+}
+
+extern "C" size_t rarc_graph_types_workspace_bytes(int64_t n, int64_t m) {
+  if (!lv_shape_ok(n, m)) return 0;
+  return khop_types_carve(nullptr, n, m).bytes;
+}
+
+extern "C" int rarc_graph_types(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, const int64_t* d_pairs, const uint32_t* d_masks,
+                                void* d_out, size_t out_bytes, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_graph && d_pairs && d_masks && d_out, RARC_E_INVALID, "rarc_graph_types: null pointer");
+  RARC_REQUIRE(KHOP_ALIGNED(d_graph, 256) && KHOP_ALIGNED(d_out, 256), RARC_E_INVALID,
+               "rarc_graph_types: the graph or the typed adjacency is not 256-byte aligned");
+  RARC_REQUIRE(KHOP_ALIGNED(d_pairs, 8) && KHOP_ALIGNED(d_masks, 4), RARC_E_INVALID,
+               "rarc_graph_types: an array is not aligned to its element (pairs 8 bytes, masks 4)");
+  RARC_REQUIRE(lv_shape_ok(n, m), RARC_E_INVALID, "rarc_graph_types: n=%lld m=%lld out of range (2 <= n < 2^31 - 1, 1 <= m < 2^30)",
+               (long long)n, (long long)m);
+  const LvGraph g = lv_graph_carve(d_graph, n, m);
+  RARC_REQUIRE(graph_bytes >= g.bytes, RARC_E_WORKSPACE, "rarc_graph_types: graph workspace of %zu bytes, %zu needed", graph_bytes, g.bytes);
+  const KhopTypes t = khop_types_carve(d_out, n, m);
+  RARC_REQUIRE(out_bytes >= t.bytes, RARC_E_WORKSPACE, "rarc_graph_types: typed adjacency of %zu bytes, %zu needed", out_bytes, t.bytes);
+  hipStream_t s = (hipStream_t)stream;
+  RARC_HIP_CHECK(hipMemsetAsync(d_out, 0, t.bytes, s));  // a slot no pair fills: neighbour 0 under mask 0, crossed by nobody
+  hipLaunchKernelGGL(khop_types_fill_kernel, dim3(lv_grid(m, 256, 4096)), dim3(256), 0, s, d_pairs, d_masks, m, n, (const int64_t*)g.row_ptr,
+                     t.cursor, t.adj, t.mask, t.bad);
+  RARC_HIP_CHECK(hipGetLastError());
+  uint32_t bad = 0;                                      // built once a graph: the entry waits for the count and reports it
+  RARC_HIP_CHECK(hipMemcpyAsync(&bad, t.bad, 4, hipMemcpyDeviceToHost, s));
+  RARC_HIP_CHECK(hipStreamSynchronize(s));
+  RARC_REQUIRE(bad == 0, RARC_E_INVALID, "rarc_graph_types: %u pairs found their rows full: not the pair list the graph was built from", bad);
+  return RARC_OK;
 }
 
 extern "C" int rarc_khop_step(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, int nq, int hops, int hop, void* d_ws,
@@ -726,6 +923,42 @@ extern "C" int rarc_khop_step(const void* d_graph, size_t graph_bytes, int64_t n
   if (W > 2) khop_launch_step<4>(p, g, n, m, s);
   else if (W > 1) khop_launch_step<2>(p, g, n, m, s);
   else khop_launch_step<1>(p, g, n, m, s);
+  RARC_HIP_CHECK(hipGetLastError());
+  if (d_grew_out) RARC_HIP_CHECK(hipMemcpyAsync(d_grew_out, ws.grew, 4, hipMemcpyDeviceToDevice, s));
+  return RARC_OK;
+}
+
+extern "C" int rarc_khop_step_typed(const void* d_graph, size_t graph_bytes, const void* d_types, size_t types_bytes, const uint32_t* d_filters,
+                                    int64_t n, int64_t m, int nq, int hops, int hop, void* d_ws, size_t ws_bytes, uint32_t* d_grew_out,
+                                    void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_graph && d_types && d_filters && d_ws, RARC_E_INVALID, "rarc_khop_step_typed: null pointer");
+  RARC_REQUIRE(KHOP_ALIGNED(d_graph, 256), RARC_E_INVALID, "rarc_khop_step_typed: the graph is not 256-byte aligned");
+  RARC_REQUIRE(KHOP_ALIGNED(d_types, 256), RARC_E_INVALID, "rarc_khop_step_typed: the typed adjacency is not 256-byte aligned");
+  RARC_REQUIRE(KHOP_ALIGNED(d_filters, 4) && KHOP_ALIGNED(d_grew_out, 4), RARC_E_INVALID,
+               "rarc_khop_step_typed: the filters or the grew word are not 4-byte aligned");
+  KHOP_SHAPE_CHECKS("rarc_khop_step_typed");
+  RARC_REQUIRE(hop >= 1 && hop <= hops, RARC_E_INVALID, "rarc_khop_step_typed: hop %d out of range (1 <= hop <= hops = %d)", hop, hops);
+  const LvGraph g = lv_graph_carve(d_graph, n, m);
+  RARC_REQUIRE(graph_bytes >= g.bytes, RARC_E_WORKSPACE, "rarc_khop_step_typed: graph workspace of %zu bytes, %zu needed", graph_bytes, g.bytes);
+  const KhopTypes t = khop_types_carve(d_types, n, m);
+  RARC_REQUIRE(types_bytes >= t.bytes, RARC_E_WORKSPACE, "rarc_khop_step_typed: typed adjacency of %zu bytes, %zu needed", types_bytes, t.bytes);
+  hipStream_t s = (hipStream_t)stream;
+  KhopStepArgs p;
+  p.row_ptr = g.row_ptr;
+  p.adj = t.adj;
+  p.prev = khop_level(ws, hop - 1);
+  p.next = khop_level(ws, hop);
+  p.seen = ws.seen;
+  p.grew = ws.grew;
+  p.n = n;
+  p.W = W;
+  p.nq = nq;
+  const KhopStepTypes ty = {t.mask, d_filters};
+  RARC_HIP_CHECK(hipMemsetAsync(ws.grew, 0, 4, s));
+  if (W > 2) khop_launch_step<4, true>(p, g, n, m, s, ty);
+  else if (W > 1) khop_launch_step<2, true>(p, g, n, m, s, ty);
+  else khop_launch_step<1, true>(p, g, n, m, s, ty);
   RARC_HIP_CHECK(hipGetLastError());
   if (d_grew_out) RARC_HIP_CHECK(hipMemcpyAsync(d_grew_out, ws.grew, 4, hipMemcpyDeviceToDevice, s));
   return RARC_OK;
@@ -815,20 +1048,28 @@ extern "C" size_t rarc_khop_edges_workspace_bytes(int64_t r, int nq, int hops) {
   RARC_REQUIRE(ews_bytes >= ews.bytes, RARC_E_WORKSPACE, NAME ": edge workspace of %zu bytes, %zu needed", ews_bytes, ews.bytes)
 
 // count / scan / write over the rows of the table, against the state in `ws`; PATHS: by the rule of the connecting paths
-template <bool PATHS>
+// TYPED: a row answers only the queries whose filter holds its type (`ty`)
+template <bool PATHS, bool TYPED = false>
 static int khop_edges_run(const KhopWs& ws, const KhopEdgeWs& ews, size_t level_stride, int64_t n, int nq, int W, int H, const int64_t* d_rel,
                           int64_t r, int max_edges, bool listed, int64_t* d_out_ids, int32_t* d_out_levels, int32_t* d_out_count,
-                          int32_t* d_out_level_counts, hipStream_t s) {
+                          int32_t* d_out_level_counts, hipStream_t s, const KhopRowTypes ty = {}) {
   const KhopEdgeBits src = {d_rel, ws.seen, ws.level, level_stride, r, n};
   const int64_t tiles = khop_tiles(r);
-  hipLaunchKernelGGL(khop_edge_count_kernel<PATHS>, dim3(lv_grid(tiles * W, 4, 16384)), dim3(256), 0, s, src, W, H, ews.tiles);
+  if constexpr (TYPED)
+    hipLaunchKernelGGL(khop_edge_count_typed_kernel<PATHS>, dim3(lv_grid(tiles * W, 4, 16384)), dim3(256), 0, s, src, W, H, nq, ews.tiles, ty);
+  else hipLaunchKernelGGL(khop_edge_count_kernel<PATHS>, dim3(lv_grid(tiles * W, 4, 16384)), dim3(256), 0, s, src, W, H, ews.tiles);
   hipLaunchKernelGGL(khop_tile_scan_kernel, dim3((H * nq + 255) / 256), dim3(256), 0, s, tiles, W, H, nq, ews.tiles, ews.totals);
   if (listed) {
     RARC_HIP_CHECK(hipMemsetAsync(d_out_ids, 0xFF, (size_t)nq * max_edges * 8, s));            // (-1, -1) past the count
     RARC_HIP_CHECK(hipMemsetAsync(d_out_levels, 0xFF, (size_t)nq * max_edges * 4, s));
-    hipLaunchKernelGGL((khop_list_kernel<true, PATHS>), dim3(lv_grid(tiles * W, 4, 16384)), dim3(256), 0, s, (const u64*)ws.level, level_stride, n, W,
-                       H, nq, (const uint32_t*)ews.tiles, (const int32_t*)ews.totals, (uint32_t)max_edges, d_out_ids, d_out_levels, d_out_count,
-                       KhopRelations{d_rel, ws.seen, r});
+    if constexpr (TYPED)
+      hipLaunchKernelGGL(khop_list_typed_kernel<PATHS>, dim3(lv_grid(tiles * W, 4, 16384)), dim3(256), 0, s, (const u64*)ws.level, level_stride, n,
+                         W, H, nq, (const uint32_t*)ews.tiles, (const int32_t*)ews.totals, (uint32_t)max_edges, d_out_ids, d_out_levels,
+                         d_out_count, KhopRelations{d_rel, ws.seen, r}, ty);
+    else
+      hipLaunchKernelGGL((khop_list_kernel<true, PATHS>), dim3(lv_grid(tiles * W, 4, 16384)), dim3(256), 0, s, (const u64*)ws.level, level_stride, n,
+                         W, H, nq, (const uint32_t*)ews.tiles, (const int32_t*)ews.totals, (uint32_t)max_edges, d_out_ids, d_out_levels,
+                         d_out_count, KhopRelations{d_rel, ws.seen, r});
   }
   RARC_HIP_CHECK(hipGetLastError());
   RARC_HIP_CHECK(hipMemcpyAsync(d_out_level_counts, ews.totals, (size_t)nq * H * 4, hipMemcpyDeviceToDevice, s));
@@ -842,6 +1083,25 @@ extern "C" int rarc_khop_edges(int64_t n, int64_t m, int nq, int hops, const voi
   KHOP_EDGE_CHECKS("rarc_khop_edges");
   return khop_edges_run<false>(ws, ews, level_stride, n, nq, W, H, d_rel, r, max_edges, listed, d_out_ids, d_out_levels, d_out_count,
                                d_out_level_counts, (hipStream_t)stream);
+}
+
+// what the typed forms add to KHOP_EDGE_CHECKS
+#define KHOP_ROW_TYPE_CHECKS(NAME)                                                                                                        \
+  RARC_REQUIRE(d_rel_types && d_filters, RARC_E_INVALID, NAME ": null pointer");                                                         \
+  RARC_REQUIRE(KHOP_ALIGNED(d_rel_types, 4) && KHOP_ALIGNED(d_filters, 4), RARC_E_INVALID,                                               \
+               NAME ": the row types or the filters are not 4-byte aligned");                                                            \
+  RARC_REQUIRE(rel_masks == 0 || rel_masks == 1, RARC_E_INVALID, NAME ": rel_masks=%d out of range (0: a type id per row, 1: a mask)",   \
+               rel_masks)
+
+extern "C" int rarc_khop_edges_typed(int64_t n, int64_t m, int nq, int hops, const void* d_ws, size_t ws_bytes, const int64_t* d_rel, int64_t r,
+                                     const int32_t* d_rel_types, int rel_masks, const uint32_t* d_filters, int max_edges, void* d_ews,
+                                     size_t ews_bytes, int64_t* d_out_ids, int32_t* d_out_levels, int32_t* d_out_count,
+                                     int32_t* d_out_level_counts, void* stream) {
+  RARC_RANGE();
+  KHOP_ROW_TYPE_CHECKS("rarc_khop_edges_typed");
+  KHOP_EDGE_CHECKS("rarc_khop_edges_typed");
+  return khop_edges_run<false, true>(ws, ews, level_stride, n, nq, W, H, d_rel, r, max_edges, listed, d_out_ids, d_out_levels, d_out_count,
+                                     d_out_level_counts, (hipStream_t)stream, KhopRowTypes{d_rel_types, d_filters, rel_masks});
 }
 
 // ---- connecting paths: the entries -------------------------------------------------------------------------------------------------
@@ -897,6 +1157,17 @@ extern "C" int rarc_khop_path_edges(int64_t n, int64_t m, int nq, int hops, cons
   KHOP_EDGE_CHECKS("rarc_khop_path_edges");
   return khop_edges_run<true>(ws, ews, level_stride, n, nq, W, H, d_rel, r, max_edges, listed, d_out_ids, d_out_levels, d_out_count,
                               d_out_level_counts, (hipStream_t)stream);
+}
+
+extern "C" int rarc_khop_path_edges_typed(int64_t n, int64_t m, int nq, int hops, const void* d_ws, size_t ws_bytes, const int64_t* d_rel,
+                                          int64_t r, const int32_t* d_rel_types, int rel_masks, const uint32_t* d_filters, int max_edges,
+                                          void* d_ews, size_t ews_bytes, int64_t* d_out_ids, int32_t* d_out_levels, int32_t* d_out_count,
+                                          int32_t* d_out_level_counts, void* stream) {
+  RARC_RANGE();
+  KHOP_ROW_TYPE_CHECKS("rarc_khop_path_edges_typed");
+  KHOP_EDGE_CHECKS("rarc_khop_path_edges_typed");
+  return khop_edges_run<true, true>(ws, ews, level_stride, n, nq, W, H, d_rel, r, max_edges, listed, d_out_ids, d_out_levels, d_out_count,
+                                    d_out_level_counts, (hipStream_t)stream, KhopRowTypes{d_rel_types, d_filters, rel_masks});
 }
 
 extern "C" int rarc_khop_chunks(int64_t n, int64_t m, int nq, int hops, const uint32_t* decay, const void* d_ws, size_t ws_bytes,

@@ -120,10 +120,104 @@ def _check_mentions(graph, mentions, top_k):
     mentions.check_top_k(top_k)
 
 
-def traverse(graph, sd, hops: int, early_stop: bool = False):
+# ---- typed traversal: the relation types a query may cross (restated by tests/typed_ref.py) ------------------------------
+MAX_TYPES = 32                 # a type is an integer in [0, 32): a bit of an edge's mask and of a query's filter
+
+
+def type_mask(types) -> int:
+    """an iterable of type ids -> the uint32 with their bits; ValueError for an id that is no integer in [0, 32)"""
+    mask = 0
+    for x in types:
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or not 0 <= int(x) < MAX_TYPES:
+            raise ValueError(f"a relation type must be an integer in [0, {MAX_TYPES}), got {x!r}")
+        mask |= 1 << int(x)
+    return mask
+
+
+def check_type_ids(types, count: int, what: str) -> np.ndarray:
+    """one type id per row -> int32 [count]; ValueError for another length or an id outside [0, 32)"""
+    a = np.asarray(types)
+    if a.shape != (count,):
+        raise ValueError(f"expected {count} types, one per {what}, got an array of shape {a.shape}")
+    if a.dtype == np.bool_ or (count and not np.all(a == np.floor(a))) or (count and (a.min() < 0 or a.max() >= MAX_TYPES)):
+        raise ValueError(f"a relation type must be an integer in [0, {MAX_TYPES})")
+    return np.ascontiguousarray(a.astype(np.int32))
+
+
+def host_filters(relation_types) -> np.ndarray:
+    """relation_types as the query calls take it -> uint32 [k] of filters, k >= 1: a uint32 array [k] of masks as it is, one
+    iterable of type ids as one filter, a sequence of k iterables as k filters.  ValueError for an id outside [0, 32) or no
+    filter at all"""
+    if isinstance(relation_types, np.ndarray) and relation_types.dtype == np.uint32:
+        if relation_types.ndim != 1 or relation_types.shape[0] < 1:
+            raise ValueError(f"filter masks must be a uint32 array [B], got an array of shape {relation_types.shape}")
+        return np.ascontiguousarray(relation_types)
+    if isinstance(relation_types, (str, bytes)) or not hasattr(relation_types, "__iter__"):
+        raise ValueError(f"relation_types must be None, an iterable of type ids, a sequence of them or a uint32 array of masks, got "
+                         f"{relation_types!r}")
+    rows = list(relation_types)
+    if all(not hasattr(x, "__iter__") for x in rows):                                        # one filter for every query (an empty one: F = 0)
+        return np.array([type_mask(rows)], np.uint32)
+    if any(not hasattr(x, "__iter__") or isinstance(x, (str, bytes)) for x in rows):
+        raise ValueError("relation_types mixes type ids and filters: give one iterable of ids, or one iterable per query")
+    return np.array([type_mask(x) for x in rows], np.uint32)
+
+
+def spread_filters(filters: np.ndarray, nq: int) -> np.ndarray:
+    """uint32 [1] or [nq] -> uint32 [nq]; ValueError for another count"""
+    if filters.shape[0] == nq:
+        return filters
+    if filters.shape[0] != 1:
+        raise ValueError(f"{filters.shape[0]} filters for {nq} queries: relation_types holds one filter for all of them or one per query")
+    return np.repeat(filters, nq)
+
+
+def check_typed(graph, relation_types):
+    """-> None for relation_types=None (the untyped traversal), else host_filters(); ValueError on a graph without masks"""
+    if relation_types is None:
+        return None
+    if not graph.typed:
+        raise ValueError("relation_types on a graph without type masks: build it with EntityGraph(..., types=), from_relations() or "
+                         "from_device(type_masks=)")
+    return host_filters(relation_types)
+
+
+def _device_filters(graph, filters, nq: int):
+    """host filters (or None) -> device int32 [nq] holding the uint32 bits (or None)"""
+    if filters is None:
+        return None
+    return graph.torch.from_numpy(spread_filters(filters, nq).view(np.int32)).to(graph.device)
+
+
+def _single_filter(graph, relation_types):
+    """the filter of a paths call: None, or uint32 [1]; ValueError for per-query filters"""
+    filters = check_typed(graph, relation_types)
+    if filters is not None and filters.shape[0] != 1:
+        raise ValueError(f"{filters.shape[0]} filters on a paths call: hop_A(v) + hop_B(v) == d needs every source under one filter, give "
+                         f"one iterable of type ids")
+    return filters
+
+
+def typed_adjacency(graph):
+    """The graph's typed slot arrays (rarc_graph_types), built on the first typed call and kept -> the device buffer"""
+    ta = getattr(graph, "_typed_adj", None)
+    if ta is None:
+        t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
+        need = int(lib.rarc_graph_types_workspace_bytes(n, m))
+        if need == 0:
+            raise B.RarcError(f"typed traversal: n={n}, m={m} refused by rarc_graph_types_workspace_bytes")
+        ta = t.empty(need, dtype=t.uint8, device=graph.device)
+        stream = t.cuda.current_stream(graph.device).cuda_stream
+        B.check(lib.rarc_graph_types(graph._graph.data_ptr(), graph._graph.numel(), n, m, graph._pairs.data_ptr(), graph._type_masks.data_ptr(),
+                                     ta.data_ptr(), ta.numel(), stream), "rarc_graph_types")
+        graph._typed_adj = ta
+    return ta
+
+
+def traverse(graph, sd, hops: int, early_stop: bool = False, filters=None):
     """Seeds one launch batch (<= 256 queries) and steps it `hops` times in the graph's k-hop workspace -> (workspace pointer,
     bytes).  early_stop reads the `grew` word after every step and leaves the remaining steps out once it is 0: the levels they
-    would write are empty either way."""
+    would write are empty either way.  filters: None, or a device int32 [nq] of uint32 filters — the typed step, same state."""
     t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
     nq, s = int(sd.shape[0]), int(sd.shape[1])
     need = int(lib.rarc_khop_workspace_bytes(n, m, nq, hops))
@@ -137,19 +231,25 @@ def traverse(graph, sd, hops: int, early_stop: bool = False):
     stream = t.cuda.current_stream(graph.device).cuda_stream
     B.check(lib.rarc_khop_seed(n, m, sd.data_ptr(), nq, s, hops, ws, wb, stream), "rarc_khop_seed")
     grew = t.zeros(1, dtype=t.int32, device=graph.device) if early_stop else None
+    ta = typed_adjacency(graph) if filters is not None and hops else None
     for hop in range(1, hops + 1):
-        B.check(lib.rarc_khop_step(graph._graph.data_ptr(), graph._graph.numel(), n, m, nq, hops, hop, ws, wb,
-                                   grew.data_ptr() if grew is not None else None, stream), "rarc_khop_step")
+        if filters is None:
+            B.check(lib.rarc_khop_step(graph._graph.data_ptr(), graph._graph.numel(), n, m, nq, hops, hop, ws, wb,
+                                       grew.data_ptr() if grew is not None else None, stream), "rarc_khop_step")
+        else:
+            B.check(lib.rarc_khop_step_typed(graph._graph.data_ptr(), graph._graph.numel(), ta.data_ptr(), ta.numel(), filters.data_ptr(), n, m,
+                                             nq, hops, hop, ws, wb, grew.data_ptr() if grew is not None else None, stream),
+                    "rarc_khop_step_typed")
         if grew is not None and not bool(grew.item()):
             break
     return ws, wb
 
 
-def _vertices(graph, sd, hops, max_vertices, early_stop):
+def _vertices(graph, sd, hops, max_vertices, early_stop, filters=None):
     """one launch batch -> device tensors: levels uint8 [B][n], or (ids, hops, counts, hop_counts)"""
     t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
     nq = int(sd.shape[0])
-    ws, wb = traverse(graph, sd, hops, early_stop)
+    ws, wb = traverse(graph, sd, hops, early_stop, filters)
     stream = t.cuda.current_stream(graph.device).cuda_stream
     if max_vertices is None:
         out = t.empty((nq, n), dtype=t.uint8, device=graph.device)
@@ -164,11 +264,11 @@ def _vertices(graph, sd, hops, max_vertices, early_stop):
     return ids, hp, cnt, hc
 
 
-def _chunks(graph, mentions, sd, hops, decay, top_k, early_stop):
+def _chunks(graph, mentions, sd, hops, decay, top_k, early_stop, filters=None):
     """one launch batch -> device tensors: scores float64 [B][n_chunks], or (ids, scores, counts)"""
     t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
     nq = int(sd.shape[0])
-    ws, wb = traverse(graph, sd, hops, early_stop)
+    ws, wb = traverse(graph, sd, hops, early_stop, filters)
     cws, cb = mentions.workspace(nq)
     split, n_split = mentions.split_list()
     stream = t.cuda.current_stream(graph.device).cuda_stream
@@ -178,52 +278,59 @@ def _chunks(graph, mentions, sd, hops, decay, top_k, early_stop):
     return (out,) if top_k is None else out
 
 
-def _batched(graph, sd, as_device, one):
-    """cuts the queries at 256 per launch batch, runs `one` on each and joins the parts"""
+def _batched(graph, sd, as_device, one, filters=None):
+    """cuts the queries at 256 per launch batch, and the host `filters` (None: untyped) with them, runs `one(seeds, device
+    filters)` on each and joins the parts"""
     t = graph.torch
-    parts = [one(sd[s0:s0 + MAX_BATCH]) for s0 in range(0, int(sd.shape[0]), MAX_BATCH)]
+    fd = _device_filters(graph, filters, int(sd.shape[0]))
+    parts = [one(sd[s0:s0 + MAX_BATCH], None if fd is None else fd[s0:s0 + MAX_BATCH]) for s0 in range(0, int(sd.shape[0]), MAX_BATCH)]
     out = parts[0] if len(parts) == 1 else tuple(t.cat([p[i] for p in parts]) for i in range(len(parts[0])))
     out = out if as_device else tuple(x.cpu().numpy() for x in out)
     return out[0] if len(out) == 1 else tuple(out)
 
 
-def neighbourhood(graph, seeds, hops: int = 2, max_vertices=None, as_device: bool = False, early_stop: bool = False):
+def neighbourhood(graph, seeds, hops: int = 2, max_vertices=None, as_device: bool = False, early_stop: bool = False, relation_types=None):
     hops = check_hops(hops, max_vertices)
+    filters = check_typed(graph, relation_types)
     with graph.torch.cuda.device(graph.device):
         sd = _device_seeds(graph, seeds)
-        return _batched(graph, sd, as_device, lambda part: _vertices(graph, part, hops, None if max_vertices is None else int(max_vertices),
-                                                                      early_stop))
+        return _batched(graph, sd, as_device, lambda part, f: _vertices(graph, part, hops, None if max_vertices is None else int(max_vertices),
+                                                                         early_stop, f), filters)
 
 
 def expand(graph, index, queries, seeds_per_query: int = 5, hops: int = 2, max_vertices=None, as_device: bool = False,
-           early_stop: bool = False):
+           early_stop: bool = False, relation_types=None):
     hops = check_hops(hops, max_vertices)
+    filters = check_typed(graph, relation_types)
     graph._check_index(index, seeds_per_query)
     sd, _ = graph._index_seeds(index, queries, seeds_per_query)
     with graph.torch.cuda.device(graph.device):
-        return _batched(graph, sd, as_device, lambda part: _vertices(graph, part, hops, None if max_vertices is None else int(max_vertices),
-                                                                      early_stop))
+        return _batched(graph, sd, as_device, lambda part, f: _vertices(graph, part, hops, None if max_vertices is None else int(max_vertices),
+                                                                         early_stop, f), filters)
 
 
-def neighbourhood_chunks(graph, mentions, seeds, hops: int = 2, decay=None, top_k=None, as_device: bool = False, early_stop: bool = False):
+def neighbourhood_chunks(graph, mentions, seeds, hops: int = 2, decay=None, top_k=None, as_device: bool = False, early_stop: bool = False,
+                         relation_types=None):
     hops = check_hops(hops)
     decay = check_decay(decay, hops)
+    filters = check_typed(graph, relation_types)
     _check_mentions(graph, mentions, top_k)
     with graph.torch.cuda.device(graph.device):
         sd = _device_seeds(graph, seeds)
-        return _batched(graph, sd, as_device, lambda part: _chunks(graph, mentions, part, hops, decay, None if top_k is None else int(top_k),
-                                                                    early_stop))
+        return _batched(graph, sd, as_device, lambda part, f: _chunks(graph, mentions, part, hops, decay, None if top_k is None else int(top_k),
+                                                                       early_stop, f), filters)
 
 
 def expand_chunks(graph, index, queries, mentions, seeds_per_query: int = 5, hops: int = 2, decay=None, top_k: int = 10,
-                  as_device: bool = False, early_stop: bool = False):
+                  as_device: bool = False, early_stop: bool = False, relation_types=None):
     hops = check_hops(hops)
     decay = check_decay(decay, hops)
+    filters = check_typed(graph, relation_types)
     graph._check_index(index, seeds_per_query)
     _check_mentions(graph, mentions, top_k)
     sd, _ = graph._index_seeds(index, queries, seeds_per_query)
     with graph.torch.cuda.device(graph.device):
-        return _batched(graph, sd, as_device, lambda part: _chunks(graph, mentions, part, hops, decay, int(top_k), early_stop))
+        return _batched(graph, sd, as_device, lambda part, f: _chunks(graph, mentions, part, hops, decay, int(top_k), early_stop, f), filters)
 
 
 # ---- subgraphs: the relations inside the neighbourhood (DESIGN §4.13g, restated by tests/subgraph_ref.py) --------------------------------
@@ -249,9 +356,26 @@ class RelationList:
     a == b allowed.  Nothing is normalised — a subgraph answers in row numbers of this table, where the caller keeps each
     relation's type and description.  A row with an end outside [0, n_entities) is part of no subgraph.
     pairs: an [r][2] integer array-like, uploaded once, or an int64 device tensor [r][2], used where it is.
-    weights: one number per row, of any numeric type; only gathered for the rows an answer returns."""
+    weights: one number per row, of any numeric type; only gathered for the rows an answer returns.
+    types: one relation type per row, an integer in [0, 32) (type_ids() maps names to them), kept on the device as int32: a typed
+    call (relation_types=) lists a row only for the queries whose filter holds its type."""
 
-    def __init__(self, n_entities: int, pairs, weights=None, device: int = 0):
+    @staticmethod
+    def type_ids(names):
+        """Type names -> (ids int32 [r], vocabulary): a name's id is its rank by first appearance, vocabulary[id] the name.
+        RarcUnsupported for more than 32 distinct names."""
+        vocabulary, index, ids = [], {}, []
+        for name in names:
+            if name not in index:
+                if len(vocabulary) == MAX_TYPES:
+                    raise B.RarcUnsupported(f"more than {MAX_TYPES} distinct relation types: an edge mask and a query filter hold {MAX_TYPES} "
+                                            f"bits (the 33rd is {name!r})")
+                index[name] = len(vocabulary)
+                vocabulary.append(name)
+            ids.append(index[name])
+        return np.array(ids, np.int32), vocabulary
+
+    def __init__(self, n_entities: int, pairs, weights=None, types=None, device: int = 0):
         import torch
 
         on_device = isinstance(pairs, torch.Tensor) and pairs.is_cuda
@@ -275,6 +399,9 @@ class RelationList:
             w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(weights)))
             if tuple(w.shape) != (r,) or w.dtype == torch.bool or w.is_complex():
                 raise ValueError(f"expected {r} numeric weights, got {w.dtype} {tuple(w.shape)}")
+        ty = None
+        if types is not None:
+            ty = check_type_ids(types.cpu().numpy() if isinstance(types, torch.Tensor) else types, r, "row")
         if not torch.cuda.is_available():
             raise B.RarcError("no ROCm device visible: the HIP backend has no CPU fallback")
         self.n_entities, self.r = int(n_entities), r
@@ -284,14 +411,22 @@ class RelationList:
         with torch.cuda.device(self.device):
             self._pairs = pairs.contiguous() if on_device else torch.from_numpy(np.ascontiguousarray(arr.astype(np.int64))).to(self.device)
             self._weights = None if w is None else w.to(self.device)
+            self._types = None if ty is None else torch.from_numpy(ty).to(self.device)
+
+    @property
+    def typed(self) -> bool:
+        return getattr(self, "_types", None) is not None
 
 
-def check_relations(graph, relations):
-    """ValueError for anything but None or a RelationList over the graph's vertices on the graph's device"""
+def check_relations(graph, relations, typed: bool = False):
+    """ValueError for anything but None or a RelationList over the graph's vertices on the graph's device; typed: the call has
+    relation_types, and the list must carry a type per row"""
     if relations is None:
         return
     if not isinstance(relations, RelationList):
         raise ValueError("relations must be a RelationList (or None for the graph's own pair list)")
+    if typed and not relations.typed:
+        raise ValueError("relation_types with a RelationList without types: build it with RelationList(..., types=), one type per row")
     if relations.n_entities != graph.n:
         raise ValueError(f"the relation list is over {relations.n_entities} entities and the graph has {graph.n} vertices: entity i must be "
                          f"vertex i")
@@ -314,9 +449,10 @@ def _own_relations(graph):
     return rel
 
 
-def _edges(graph, rel, nq, hops, max_edges, ws, wb, entry="rarc_khop_edges"):
+def _edges(graph, rel, nq, hops, max_edges, ws, wb, entry="rarc_khop_edges", filters=None):
     """the relations inside the neighbourhoods the traversal left in (ws, wb) -> device tensors, in the order of EDGE_FIELDS;
-    entry="rarc_khop_path_edges": the relations on the paths of the path state in (ws, wb)"""
+    entry="rarc_khop_path_edges": the relations on the paths of the path state in (ws, wb).  filters (device int32 [nq], uint32
+    bits): the typed entry — a row needs its type in the query's filter; the graph's own pair list carries its masks instead"""
     t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
     need = int(lib.rarc_khop_edges_workspace_bytes(rel.r, nq, hops))
     if need == 0:
@@ -330,8 +466,15 @@ def _edges(graph, rel, nq, hops, max_edges, ws, wb, entry="rarc_khop_edges"):
     cnt = t.empty(nq, dtype=t.int32, device=graph.device)
     lc = t.empty((nq, hops + 1), dtype=t.int32, device=graph.device)
     stream = t.cuda.current_stream(graph.device).cuda_stream
-    B.check(getattr(lib, entry)(n, m, nq, hops, ws, wb, rel._pairs.data_ptr(), rel.r, max_edges, ews.data_ptr(), ews.numel(), ids.data_ptr(),
-                                lv.data_ptr(), cnt.data_ptr(), lc.data_ptr(), stream), entry)
+    if filters is None:
+        B.check(getattr(lib, entry)(n, m, nq, hops, ws, wb, rel._pairs.data_ptr(), rel.r, max_edges, ews.data_ptr(), ews.numel(), ids.data_ptr(),
+                                    lv.data_ptr(), cnt.data_ptr(), lc.data_ptr(), stream), entry)
+    else:
+        own = rel is getattr(graph, "_own_relation_list", None)
+        row_types = graph._type_masks if own else rel._types
+        B.check(getattr(lib, entry + "_typed")(n, m, nq, hops, ws, wb, rel._pairs.data_ptr(), rel.r, row_types.data_ptr(), int(own),
+                                               filters.data_ptr(), max_edges, ews.data_ptr(), ews.numel(), ids.data_ptr(), lv.data_ptr(),
+                                               cnt.data_ptr(), lc.data_ptr(), stream), entry + "_typed")
     rows = ids.clamp(min=0)                                                                  # the few returned rows: gathered here
     ends = t.where((ids >= 0).unsqueeze(-1), rel._pairs[rows], t.full_like(rel._pairs[:1], -1))
     out = (ids, ends, lv, cnt, lc)
@@ -340,13 +483,13 @@ def _edges(graph, rel, nq, hops, max_edges, ws, wb, entry="rarc_khop_edges"):
     return out
 
 
-def _subgraph(graph, rel, sd, hops, max_vertices, max_edges, early_stop):
+def _subgraph(graph, rel, sd, hops, max_vertices, max_edges, early_stop, filters=None):
     """one launch batch, one traversal -> the vertex list (unless max_vertices is None) followed by the edge list"""
     t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
     nq = int(sd.shape[0])
-    ws, wb = traverse(graph, sd, hops, early_stop)
+    ws, wb = traverse(graph, sd, hops, early_stop, filters)
     if max_vertices is None:
-        return _edges(graph, rel, nq, hops, max_edges, ws, wb)
+        return _edges(graph, rel, nq, hops, max_edges, ws, wb, filters=filters)
     ids = t.empty((nq, max_vertices), dtype=t.int64, device=graph.device)
     hp = t.empty((nq, max_vertices), dtype=t.int32, device=graph.device)
     cnt = t.empty(nq, dtype=t.int32, device=graph.device)
@@ -354,37 +497,44 @@ def _subgraph(graph, rel, sd, hops, max_vertices, max_edges, early_stop):
     stream = t.cuda.current_stream(graph.device).cuda_stream
     B.check(lib.rarc_khop_list(n, m, nq, hops, max_vertices, ws, wb, ids.data_ptr(), hp.data_ptr(), cnt.data_ptr(), stream), "rarc_khop_list")
     B.check(lib.rarc_khop_counts(n, m, nq, hops, ws, wb, hc.data_ptr(), stream), "rarc_khop_counts")
-    return (ids, hp, cnt, hc) + _edges(graph, rel, nq, hops, max_edges, ws, wb)
+    return (ids, hp, cnt, hc) + _edges(graph, rel, nq, hops, max_edges, ws, wb, filters=filters)
 
 
-def neighbourhood_edges(graph, seeds, hops: int = 2, max_edges: int = 16384, relations=None, as_device: bool = False, early_stop: bool = False):
+def neighbourhood_edges(graph, seeds, hops: int = 2, max_edges: int = 16384, relations=None, as_device: bool = False, early_stop: bool = False,
+                        relation_types=None):
     hops, max_edges = check_hops(hops), check_max_edges(max_edges)
-    check_relations(graph, relations)
+    filters = check_typed(graph, relation_types)
+    check_relations(graph, relations, typed=filters is not None)
     with graph.torch.cuda.device(graph.device):
         rel = _own_relations(graph) if relations is None else relations
         sd = _device_seeds(graph, seeds)
-        return SubgraphEdges(*_batched(graph, sd, as_device, lambda part: _subgraph(graph, rel, part, hops, None, max_edges, early_stop)))
+        return SubgraphEdges(*_batched(graph, sd, as_device, lambda part, f: _subgraph(graph, rel, part, hops, None, max_edges, early_stop, f),
+                                       filters))
 
 
 def subgraph(graph, seeds, hops: int = 2, max_vertices: int = 4096, max_edges: int = 16384, relations=None, as_device: bool = False,
-             early_stop: bool = False):
+             early_stop: bool = False, relation_types=None):
     hops, max_edges = check_hops(hops, max_vertices), check_max_edges(max_edges)
-    check_relations(graph, relations)
+    filters = check_typed(graph, relation_types)
+    check_relations(graph, relations, typed=filters is not None)
     with graph.torch.cuda.device(graph.device):
         rel = _own_relations(graph) if relations is None else relations
         sd = _device_seeds(graph, seeds)
-        return Subgraph(*_batched(graph, sd, as_device, lambda part: _subgraph(graph, rel, part, hops, int(max_vertices), max_edges, early_stop)))
+        return Subgraph(*_batched(graph, sd, as_device,
+                                  lambda part, f: _subgraph(graph, rel, part, hops, int(max_vertices), max_edges, early_stop, f), filters))
 
 
 def expand_subgraph(graph, index, queries, seeds_per_query: int = 5, hops: int = 2, max_vertices: int = 4096, max_edges: int = 16384,
-                    relations=None, as_device: bool = False, early_stop: bool = False):
+                    relations=None, as_device: bool = False, early_stop: bool = False, relation_types=None):
     hops, max_edges = check_hops(hops, max_vertices), check_max_edges(max_edges)
-    check_relations(graph, relations)
+    filters = check_typed(graph, relation_types)
+    check_relations(graph, relations, typed=filters is not None)
     graph._check_index(index, seeds_per_query)
     sd, _ = graph._index_seeds(index, queries, seeds_per_query)
     with graph.torch.cuda.device(graph.device):
         rel = _own_relations(graph) if relations is None else relations
-        return Subgraph(*_batched(graph, sd, as_device, lambda part: _subgraph(graph, rel, part, hops, int(max_vertices), max_edges, early_stop)))
+        return Subgraph(*_batched(graph, sd, as_device,
+                                  lambda part, f: _subgraph(graph, rel, part, hops, int(max_vertices), max_edges, early_stop, f), filters))
 
 
 # ---- connecting paths: all shortest paths between sources (restated by tests/paths_ref.py) ------------------------------
@@ -466,12 +616,13 @@ def _device_sources(graph, sources, pairs):
     return sd, t.from_numpy(host_pairs(ns, pairs.cpu().numpy() if isinstance(pairs, t.Tensor) else pairs)).to(graph.device)
 
 
-def mark_paths(graph, sd, pd, length: int, early_stop: bool = False):
+def mark_paths(graph, sd, pd, length: int, early_stop: bool = False, filters=None):
     """One traversal of the sources `sd` to `length`, then rarc_khop_paths for the pairs `pd` -> (distances, a device int32
-    [np]; path workspace pointer, bytes): a k-hop state of np columns with positions for hops, for the k-hop readers"""
+    [np]; path workspace pointer, bytes): a k-hop state of np columns with positions for hops, for the k-hop readers.
+    filters: None, or the one filter of a typed call as host uint32 [1]: every source traverses under it"""
     t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
     ns, npairs = int(sd.shape[0]), int(pd.shape[0])
-    ws, wb = traverse(graph, sd, length, early_stop)
+    ws, wb = traverse(graph, sd, length, early_stop, _device_filters(graph, filters, ns))
     need = int(lib.rarc_khop_workspace_bytes(n, m, npairs, length))
     if need == 0:
         raise B.RarcError(f"shortest_paths: n={n}, m={m}, {npairs} pairs, max_length={length} refused by rarc_khop_workspace_bytes")
@@ -486,11 +637,11 @@ def mark_paths(graph, sd, pd, length: int, early_stop: bool = False):
     return dist, pws.data_ptr(), pws.numel()
 
 
-def _paths(graph, rel, sd, pd, length, max_vertices, max_edges, early_stop):
+def _paths(graph, rel, sd, pd, length, max_vertices, max_edges, early_stop, filters=None):
     """one call -> device tensors in the order of PATH_FIELDS"""
     t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
     npairs = int(pd.shape[0])
-    dist, pws, pwb = mark_paths(graph, sd, pd, length, early_stop)
+    dist, pws, pwb = mark_paths(graph, sd, pd, length, early_stop, filters)
     ids = t.empty((npairs, max_vertices), dtype=t.int64, device=graph.device)
     pos = t.empty((npairs, max_vertices), dtype=t.int32, device=graph.device)
     cnt = t.empty(npairs, dtype=t.int32, device=graph.device)
@@ -498,7 +649,8 @@ def _paths(graph, rel, sd, pd, length, max_vertices, max_edges, early_stop):
     stream = t.cuda.current_stream(graph.device).cuda_stream
     B.check(lib.rarc_khop_list(n, m, npairs, length, max_vertices, pws, pwb, ids.data_ptr(), pos.data_ptr(), cnt.data_ptr(), stream), "rarc_khop_list")
     B.check(lib.rarc_khop_counts(n, m, npairs, length, pws, pwb, pc.data_ptr(), stream), "rarc_khop_counts")
-    return (dist, ids, pos, cnt, pc) + _edges(graph, rel, npairs, length, max_edges, pws, pwb, entry="rarc_khop_path_edges")
+    return (dist, ids, pos, cnt, pc) + _edges(graph, rel, npairs, length, max_edges, pws, pwb, entry="rarc_khop_path_edges",
+                                              filters=_device_filters(graph, filters, npairs))
 
 
 def _host(out, as_device):
@@ -506,26 +658,28 @@ def _host(out, as_device):
 
 
 def shortest_paths(graph, sources, pairs, max_length: int = 4, max_vertices: int = 4096, max_edges: int = 16384, relations=None,
-                   as_device: bool = False, early_stop: bool = False):
+                   as_device: bool = False, early_stop: bool = False, relation_types=None):
     length = check_length(max_length)
     max_vertices, max_edges = check_path_caps(max_vertices, max_edges)
-    check_relations(graph, relations)
+    filters = _single_filter(graph, relation_types)
+    check_relations(graph, relations, typed=filters is not None)
     with graph.torch.cuda.device(graph.device):
         sd, pd = _device_sources(graph, sources, pairs)
         rel = _own_relations(graph) if relations is None else relations
-        return ShortestPaths(*_host(_paths(graph, rel, sd, pd, length, max_vertices, max_edges, early_stop), as_device))
+        return ShortestPaths(*_host(_paths(graph, rel, sd, pd, length, max_vertices, max_edges, early_stop, filters), as_device))
 
 
 def path_chunks(graph, mentions, sources, pairs, max_length: int = 4, decay=None, top_k=None, as_device: bool = False,
-                early_stop: bool = False):
+                early_stop: bool = False, relation_types=None):
     length = check_length(max_length)
     decay = check_decay(decay, length)
+    filters = _single_filter(graph, relation_types)
     _check_mentions(graph, mentions, top_k)
     t, lib = graph.torch, graph.lib
     with t.cuda.device(graph.device):
         sd, pd = _device_sources(graph, sources, pairs)
         npairs = int(pd.shape[0])
-        _, pws, pwb = mark_paths(graph, sd, pd, length, early_stop)
+        _, pws, pwb = mark_paths(graph, sd, pd, length, early_stop, filters)
         cws, cb = mentions.workspace(npairs)
         split, n_split = mentions.split_list()
         stream = t.cuda.current_stream(graph.device).cuda_stream
@@ -538,10 +692,11 @@ def path_chunks(graph, mentions, sources, pairs, max_length: int = 4, decay=None
 
 
 def connect(graph, index, queries, seeds_per_query: int = 5, max_length: int = 4, max_vertices: int = 4096, max_edges: int = 16384,
-            relations=None, as_device: bool = False, early_stop: bool = False):
+            relations=None, as_device: bool = False, early_stop: bool = False, relation_types=None):
     length = check_length(max_length)
     max_vertices, max_edges = check_path_caps(max_vertices, max_edges)
-    check_relations(graph, relations)
+    filters = _single_filter(graph, relation_types)
+    check_relations(graph, relations, typed=filters is not None)
     graph._check_index(index, seeds_per_query)
     k = int(seeds_per_query)
     if k < 2:
@@ -565,18 +720,34 @@ def connect(graph, index, queries, seeds_per_query: int = 5, max_length: int = 4
             sd = part.reshape(-1, 1).contiguous()                                            # every seed a one-vertex source
             pq = t.from_numpy(np.repeat(np.arange(q0, q0 + nq, dtype=np.int32), len(per_query))).to(graph.device)
             ends = sd[:, 0][pd.to(t.int64)]
-            parts.append(_paths(graph, rel, sd, pd, length, max_vertices, max_edges, early_stop) + (pq, ends))
+            parts.append(_paths(graph, rel, sd, pd, length, max_vertices, max_edges, early_stop, filters) + (pq, ends))
         if rel._weights is None:                                                             # edge_weights stays None, before the two pair fields
             parts = [p[:-2] + (None,) + p[-2:] for p in parts]
         out = tuple(None if p0 is None else (p0 if len(parts) == 1 else t.cat([p[f] for p in parts])) for f, p0 in enumerate(parts[0]))
         return Connection(*(out if as_device else tuple(None if x is None else x.cpu().numpy() for x in out)))
 
 
-def all_shortest_paths(n: int, edges, sources, pairs, device: int = 0, **kw):
-    """The one-shot form: EntityGraph(n, edges, device=device).shortest_paths(sources, pairs, **kw).  The arguments are checked
-    before the graph is built: a bad source, pair, max_length, max_vertices, max_edges or relation list raises with no device
-    visible."""
+def _check_one_shot_types(types, kw, nq=None, single=False):
+    """the typed arguments of a one-shot form, before the graph is built: relation_types needs `types` (one id per pair), its
+    ids must lie in [0, 32) and its filters number 1 or nq (paths: 1)"""
+    if kw.get("relation_types") is None:
+        return
+    if types is None:
+        raise ValueError("relation_types on a graph without type masks: give types=, one relation type per pair")
+    filters = host_filters(kw["relation_types"])
+    if single and filters.shape[0] != 1:
+        raise ValueError(f"{filters.shape[0]} filters on a paths call: give one iterable of type ids")
+    if nq is not None:
+        spread_filters(filters, nq)
+
+
+def all_shortest_paths(n: int, edges, sources, pairs, device: int = 0, types=None, **kw):
+    """The one-shot form: EntityGraph(n, edges, types=types, device=device).shortest_paths(sources, pairs, **kw).  The arguments
+    are checked before the graph is built: a bad source, pair, max_length, max_vertices, max_edges, relation list or filter raises
+    with no device visible."""
     from .pagerank import EntityGraph
+
+    _check_one_shot_types(types, kw, single=True)
 
     check_length(kw.get("max_length", 4))
     check_path_caps(kw.get("max_vertices", 4096), kw.get("max_edges", 16384))
@@ -587,13 +758,15 @@ def all_shortest_paths(n: int, edges, sources, pairs, device: int = 0, **kw):
         ns = host_sources(int(n), sources).shape[0]
         if not hasattr(pairs, "is_cuda"):
             host_pairs(ns, pairs)
-    return EntityGraph(n, edges, device=device).shortest_paths(sources, pairs, **kw)
+    return EntityGraph(n, edges, types=types, device=device).shortest_paths(sources, pairs, **kw)
 
 
-def k_hop_subgraph(n: int, pairs, seeds, hops: int = 2, device: int = 0, **kw):
-    """The one-shot form: EntityGraph(n, pairs, device=device).subgraph(seeds, hops, **kw).  The arguments are checked before the
-    graph is built: a bad seed, hops, max_vertices, max_edges or relation list raises with no device visible."""
+def k_hop_subgraph(n: int, pairs, seeds, hops: int = 2, device: int = 0, types=None, **kw):
+    """The one-shot form: EntityGraph(n, pairs, types=types, device=device).subgraph(seeds, hops, **kw).  The arguments are checked
+    before the graph is built: a bad seed, hops, max_vertices, max_edges, relation list or filter raises with no device visible."""
     from .pagerank import EntityGraph
+
+    _check_one_shot_types(types, kw, None if hasattr(seeds, "is_cuda") else len(list(seeds)))
 
     check_hops(hops, kw.get("max_vertices", 4096))
     check_max_edges(kw.get("max_edges", 16384))
@@ -602,15 +775,17 @@ def k_hop_subgraph(n: int, pairs, seeds, hops: int = 2, device: int = 0, **kw):
         raise ValueError(f"relations must be a RelationList over the graph's {int(n)} vertices (or None for the graph's own pair list)")
     if not hasattr(seeds, "is_cuda"):
         host_seeds(int(n), seeds)
-    return EntityGraph(n, pairs, device=device).subgraph(seeds, hops=hops, **kw)
+    return EntityGraph(n, pairs, types=types, device=device).subgraph(seeds, hops=hops, **kw)
 
 
-def k_hop(n: int, pairs, seeds, hops: int = 2, device: int = 0, **kw):
-    """The one-shot form: EntityGraph(n, pairs, device=device).neighbourhood(seeds, hops, **kw).  The arguments are checked
-    before the graph is built: a bad seed, hops or max_vertices raises with no device visible."""
+def k_hop(n: int, pairs, seeds, hops: int = 2, device: int = 0, types=None, **kw):
+    """The one-shot form: EntityGraph(n, pairs, types=types, device=device).neighbourhood(seeds, hops, **kw).  The arguments are
+    checked before the graph is built: a bad seed, hops, max_vertices or filter raises with no device visible."""
     from .pagerank import EntityGraph
+
+    _check_one_shot_types(types, kw, None if hasattr(seeds, "is_cuda") else len(list(seeds)))
 
     check_hops(hops, kw.get("max_vertices"))
     if not hasattr(seeds, "is_cuda"):
         host_seeds(int(n), seeds)
-    return EntityGraph(n, pairs, device=device).neighbourhood(seeds, hops=hops, **kw)
+    return EntityGraph(n, pairs, types=types, device=device).neighbourhood(seeds, hops=hops, **kw)

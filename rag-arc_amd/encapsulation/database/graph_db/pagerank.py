@@ -49,6 +49,14 @@ def quantise_seed_weights(w: np.ndarray) -> np.ndarray:
 def _normalise_pairs(n: int, pairs, weights):
     """exactly louvain_communities' normalisation of host pairs (swapped to i < j, duplicates dropped); the weights of
     duplicates add up"""
+    return _normalise_typed_pairs(n, pairs, weights, None)[:2]
+
+
+def _normalise_typed_pairs(n: int, pairs, weights, types):
+    """_normalise_pairs with one relation type per input pair (or None) -> (pairs, weights, masks): the uint32 mask of a pair is
+    the OR of 1 << type over its duplicates, in either orientation"""
+    from .neighbourhood import check_type_ids
+
     arr = np.asarray(pairs)
     if arr.size == 0:
         arr = np.zeros((0, 2), np.int64)
@@ -66,6 +74,9 @@ def _normalise_pairs(n: int, pairs, weights):
         if not np.all(w == np.floor(w)) or (w.size and (w.min() < 1 or w.max() >= 1 << 32)):
             raise ValueError("edge weights must be integers in [1, 2^32)")
         w = w.astype(np.int64)
+    masks = None
+    if types is not None:
+        masks = np.uint32(1) << check_type_ids(types, arr.shape[0], "pair").astype(np.uint32)
     if arr.shape[0]:
         if arr.min() < 0 or arr.max() >= n:
             raise ValueError(f"a pair names a vertex outside [0, {n})")
@@ -74,20 +85,27 @@ def _normalise_pairs(n: int, pairs, weights):
         arr, inverse = np.unique(np.stack([arr.min(axis=1), arr.max(axis=1)], axis=1), axis=0, return_inverse=True)
         if w is not None:
             w = np.bincount(inverse.ravel(), weights=w.astype(np.float64), minlength=arr.shape[0]).astype(np.int64)
-    return arr, w
+        if masks is not None:
+            joined = np.zeros(arr.shape[0], np.uint32)
+            np.bitwise_or.at(joined, inverse.ravel(), masks)
+            masks = joined
+    return arr, w, masks
 
 
 class EntityGraph:
     """An undirected graph on n vertices, resident on the device as the CSR of `rarc_graph_csr`.
     pairs: an [m][2] array-like — normalised as louvain_communities normalises it: swapped to i < j, duplicates dropped (the
     weights of duplicates add up) — or an int64 device tensor [m][2], used where it is: every pair i < j, each once.
-    weights: integers >= 1 per pair (unit by default), their total below 2^31."""
+    weights: integers >= 1 per pair (unit by default), their total below 2^31.
+    types: one relation type per input pair, an integer in [0, 32) (RelationList.type_ids maps names to them): the graph keeps a
+    uint32 mask per edge, the OR over its duplicates, and the query calls take relation_types=."""
 
-    def __init__(self, n: int, pairs, weights=None, device: int = 0):
+    def __init__(self, n: int, pairs, weights=None, types=None, device: int = 0):
         import torch
 
         n = int(n)
         on_device = isinstance(pairs, torch.Tensor) and pairs.is_cuda
+        masks = None
         if on_device:
             if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype != torch.int64:
                 raise ValueError(f"expected an int64 [m][2] tensor of pairs, got {pairs.dtype} {tuple(pairs.shape)}")
@@ -98,8 +116,12 @@ class EntityGraph:
                 if w.shape != (m,) or not np.all(w == np.floor(w)) or (m and (w.min() < 1 or w.max() >= 1 << 32)):
                     raise ValueError(f"edge weights must be {m} integers in [1, 2^32)")
                 w = w.astype(np.int64)
+            if types is not None:                                       # (device pairs are unique by contract: a pair's mask is its one type)
+                from .neighbourhood import check_type_ids
+
+                masks = np.uint32(1) << check_type_ids(types.cpu().numpy() if isinstance(types, torch.Tensor) else types, m, "pair").astype(np.uint32)
         else:
-            arr, w = _normalise_pairs(n, pairs.cpu().numpy() if isinstance(pairs, torch.Tensor) else pairs, weights)
+            arr, w, masks = _normalise_typed_pairs(n, pairs.cpu().numpy() if isinstance(pairs, torch.Tensor) else pairs, weights, types)
             m = int(arr.shape[0])
         if n < 2:
             raise ValueError("a graph needs at least 2 vertices")
@@ -124,15 +146,39 @@ class EntityGraph:
             B.check(self.lib.rarc_graph_csr(p.data_ptr(), wd.data_ptr() if wd is not None else None, None, n, m, self._graph.data_ptr(),
                                             self._graph.numel(), stream), "rarc_graph_csr")
             torch.cuda.current_stream(self.device).synchronize()
+            md = None if masks is None else torch.from_numpy(masks.view(np.int32)).to(self.device)
         self._pairs, self._pair_weights = p, wd                         # kept for subgraph(relations=None): 16 bytes an edge
+        self._type_masks, self._typed_adj = md, None                    # uint32 bits [m]; the typed slot arrays, built on the first typed call
         self._ws = None
         self._components = {}                                           # as_device -> Components, filled by components()
 
+    @property
+    def typed(self) -> bool:
+        """whether the edges carry type masks: relation_types= is refused without them"""
+        return getattr(self, "_type_masks", None) is not None
+
     @classmethod
-    def from_device(cls, n: int, pairs, weights=None):
+    def from_relations(cls, relations, device=None):
+        """The graph of a typed RelationList: every row (a, b, t) with a != b and both ends in [0, n_entities) is a relation of
+        the pair {a, b}; the pair's mask is the OR of 1 << t over its rows, its weight the number of its rows or, where the list
+        has weights, their sum (integers >= 1, as the constructor takes them)."""
+        from .neighbourhood import RelationList
+
+        if not isinstance(relations, RelationList) or not relations.typed:
+            raise ValueError("from_relations takes a RelationList with types")
+        n = relations.n_entities
+        p = relations._pairs.cpu().numpy()
+        keep = (p[:, 0] != p[:, 1]) & (p >= 0).all(axis=1) & (p < n).all(axis=1)
+        w = None if relations._weights is None else relations._weights.cpu().numpy()[keep]
+        return cls(n, p[keep], weights=np.ones(int(keep.sum()), np.int64) if w is None else w, types=relations._types.cpu().numpy()[keep],
+                   device=relations.device.index if device is None else device)
+
+    @classmethod
+    def from_device(cls, n: int, pairs, weights=None, type_masks=None):
         """Adopts buffers that are on a device already (graph_db/merge.py builds a merged graph this way): `pairs` an int64 device
         tensor [m][2], every pair 0 <= i < j < n, each once, and `weights` None (unit) or a device tensor [m] of int32 holding
-        uint32 bits (what rarc_merge_pairs writes), each >= 1.  Nothing passes through the host but the two words of the checks:
+        uint32 bits (what rarc_merge_pairs writes), each >= 1; `type_masks` None or a device tensor [m] of int32 holding each pair's
+        uint32 mask of relation types.  Nothing passes through the host but the two words of the checks:
         the same limits as the constructor's, refused the same way."""
         import torch
 
@@ -143,6 +189,9 @@ class EntityGraph:
         if weights is not None and not (isinstance(weights, torch.Tensor) and weights.device == pairs.device and weights.dtype == torch.int32
                                         and tuple(weights.shape) == (m,)):
             raise ValueError(f"edge weights must be an int32 device tensor [{m}] (uint32 bits) beside the pairs")
+        if type_masks is not None and not (isinstance(type_masks, torch.Tensor) and type_masks.device == pairs.device
+                                           and type_masks.dtype == torch.int32 and tuple(type_masks.shape) == (m,)):
+            raise ValueError(f"type masks must be an int32 device tensor [{m}] (uint32 bits) beside the pairs")
         if n < 2:
             raise ValueError("a graph needs at least 2 vertices")
         if m < 1:
@@ -172,6 +221,7 @@ class EntityGraph:
                                             self._graph.numel(), stream), "rarc_graph_csr")
             torch.cuda.current_stream(self.device).synchronize()
         self._pairs, self._pair_weights = p, wd
+        self._type_masks, self._typed_adj = None if type_masks is None else type_masks.contiguous(), None
         self._ws = None
         self._components = {}
         return self
@@ -389,47 +439,50 @@ class EntityGraph:
             return self._ranked(sd, wd, a, tol, max_iterations, int(top_k), as_device, mentions=mentions)
 
     # ---------------------------------------------------------------------------------------------------------------- traversal
-    def neighbourhood(self, seeds, hops: int = 2, max_vertices=None, as_device: bool = False, early_stop: bool = False):
+    def neighbourhood(self, seeds, hops: int = 2, max_vertices=None, as_device: bool = False, early_stop: bool = False, relation_types=None):
         """The vertices within `hops` edges of each query's seeds, and how far each is (graph_db/neighbourhood.py).
         seeds: as personalized_pagerank takes them (no weights: a seed has hop 0); a query may have none.  0 <= hops <= 8.
         -> uint8 [B][n]: hop_q(v), 255 for "not within hops"; or with max_vertices (1 .. 65536) the tuple (ids int64 [B][max],
         hops int32 [B][max], counts int32 [B], hop_counts int32 [B][hops + 1]): each neighbourhood by (hop ascending, vertex
         ascending), cut at max_vertices, (-1, -1) past the count; hop_counts[q][h] = the vertices at hop h exactly, never cut.
         early_stop=True reads one word after every step and stops stepping once no query reached a new vertex: the same answer.
-        ValueError for a seed outside [0, n), more than 64 seeds or negative hops; RarcUnsupported for hops > 8 or
-        max_vertices > 65536."""
+        relation_types (a graph built with types only): None — the untyped traversal — or the relation types each
+        query may cross: one iterable of type ids as one filter for every query, a sequence of B iterables, or a uint32 array
+        [B] of masks.  An edge is crossed iff its mask shares a type with the filter; a seed has hop 0 whatever the filter.
+        ValueError for a seed outside [0, n), more than 64 seeds, negative hops, relation_types on a graph without masks, a type
+        outside [0, 32) or a filter count other than 1 or B; RarcUnsupported for hops > 8 or max_vertices > 65536."""
         from . import neighbourhood as K
 
-        return K.neighbourhood(self, seeds, hops=hops, max_vertices=max_vertices, as_device=as_device, early_stop=early_stop)
+        return K.neighbourhood(self, seeds, hops=hops, max_vertices=max_vertices, as_device=as_device, early_stop=early_stop, relation_types=relation_types)
 
     def expand(self, index, queries, seeds_per_query: int = 5, hops: int = 2, max_vertices=None, as_device: bool = False,
-               early_stop: bool = False):
+               early_stop: bool = False, relation_types=None):
         """neighbourhood for embedded queries: each query's seeds are the index's own top-`seeds_per_query` ids (row i of `index`
         is the embedding of vertex i), taken on the device — nothing leaves HBM between the search and the traversal."""
         from . import neighbourhood as K
 
         return K.expand(self, index, queries, seeds_per_query=seeds_per_query, hops=hops, max_vertices=max_vertices, as_device=as_device,
-                        early_stop=early_stop)
+                        early_stop=early_stop, relation_types=relation_types)
 
-    def neighbourhood_chunks(self, mentions, seeds, hops: int = 2, decay=None, top_k=None, as_device: bool = False, early_stop: bool = False):
+    def neighbourhood_chunks(self, mentions, seeds, hops: int = 2, decay=None, top_k=None, as_device: bool = False, early_stop: bool = False, relation_types=None):
         """neighbourhood, ending in chunks: S(c) = sum over c's mentions (e, w) with hop(e) <= hops of w * decay[hop(e)].
         decay: hops + 1 integers in [0, 2^16]; by default 4096 >> (2 h), a mention one hop nearer counts four times as much.
         -> float64 [B][n_chunks] scores (S / 2^28, exact), or with top_k (ids, scores, counts) as rank_chunks returns them:
         (score descending, chunk ascending), a chunk of score 0 never returned."""
         from . import neighbourhood as K
 
-        return K.neighbourhood_chunks(self, mentions, seeds, hops=hops, decay=decay, top_k=top_k, as_device=as_device, early_stop=early_stop)
+        return K.neighbourhood_chunks(self, mentions, seeds, hops=hops, decay=decay, top_k=top_k, as_device=as_device, early_stop=early_stop, relation_types=relation_types)
 
     def expand_chunks(self, index, queries, mentions, seeds_per_query: int = 5, hops: int = 2, decay=None, top_k: int = 10,
-                      as_device: bool = False, early_stop: bool = False):
+                      as_device: bool = False, early_stop: bool = False, relation_types=None):
         """expand, ending in chunks -> (ids, scores, counts) as neighbourhood_chunks(top_k=top_k)."""
         from . import neighbourhood as K
 
         return K.expand_chunks(self, index, queries, mentions, seeds_per_query=seeds_per_query, hops=hops, decay=decay, top_k=top_k,
-                               as_device=as_device, early_stop=early_stop)
+                               as_device=as_device, early_stop=early_stop, relation_types=relation_types)
 
     def subgraph(self, seeds, hops: int = 2, max_vertices: int = 4096, max_edges: int = 16384, relations=None, as_device: bool = False,
-                 early_stop: bool = False):
+                 early_stop: bool = False, relation_types=None):
         """The neighbourhood and the relations inside it, from one traversal.
         relations: a RelationList over this graph's vertices — the caller's table, rows (a, b) in any orientation, repeats and
         a == b allowed — or None for the graph's own normalised pair list.  A row's level is max(hop(a), hop(b)); it is listed
@@ -439,31 +492,33 @@ class EntityGraph:
         int32 [B][max_edges], edge_counts int32 [B], edge_level_counts int32 [B][hops + 1], and edge_weights [B][max_edges] when
         the list has weights (0 past the count): each list by (level ascending, row ascending), cut at max_edges (1 .. 65536),
         -1 past the count; edge_level_counts[q][h] = the rows at level h exactly, never cut.
-        ValueError for max_edges < 1 or a relation list over other entities or on another device; RarcUnsupported for
-        max_edges > 65536."""
+        relation_types: as neighbourhood takes it; a row (a, b, t) is then listed for q only if q's filter holds t, so
+        `relations` must carry types (None: the graph's own pairs, a pair listed iff its mask shares a type with the filter).
+        ValueError for max_edges < 1, a relation list over other entities or on another device, or relation_types with a
+        RelationList without types; RarcUnsupported for max_edges > 65536."""
         from . import neighbourhood as K
 
         return K.subgraph(self, seeds, hops=hops, max_vertices=max_vertices, max_edges=max_edges, relations=relations, as_device=as_device,
-                          early_stop=early_stop)
+                          early_stop=early_stop, relation_types=relation_types)
 
     def neighbourhood_edges(self, seeds, hops: int = 2, max_edges: int = 16384, relations=None, as_device: bool = False,
-                            early_stop: bool = False):
+                            early_stop: bool = False, relation_types=None):
         """The edge part of subgraph alone -> the named tuple (edge_ids, edge_ends, edge_levels, edge_counts, edge_level_counts,
         edge_weights or None)."""
         from . import neighbourhood as K
 
-        return K.neighbourhood_edges(self, seeds, hops=hops, max_edges=max_edges, relations=relations, as_device=as_device, early_stop=early_stop)
+        return K.neighbourhood_edges(self, seeds, hops=hops, max_edges=max_edges, relations=relations, as_device=as_device, early_stop=early_stop, relation_types=relation_types)
 
     def expand_subgraph(self, index, queries, seeds_per_query: int = 5, hops: int = 2, max_vertices: int = 4096, max_edges: int = 16384,
-                        relations=None, as_device: bool = False, early_stop: bool = False):
+                        relations=None, as_device: bool = False, early_stop: bool = False, relation_types=None):
         """subgraph for embedded queries: the seeds are the index's own top-`seeds_per_query` ids, as expand takes them."""
         from . import neighbourhood as K
 
         return K.expand_subgraph(self, index, queries, seeds_per_query=seeds_per_query, hops=hops, max_vertices=max_vertices, max_edges=max_edges,
-                                 relations=relations, as_device=as_device, early_stop=early_stop)
+                                 relations=relations, as_device=as_device, early_stop=early_stop, relation_types=relation_types)
 
     def shortest_paths(self, sources, pairs, max_length: int = 4, max_vertices: int = 4096, max_edges: int = 16384, relations=None,
-                       as_device: bool = False, early_stop: bool = False):
+                       as_device: bool = False, early_stop: bool = False, relation_types=None):
         """How sources are connected: every shortest path of at most `max_length` edges between the two sources of each pair,
         MATCH p = allShortestPaths((a)-[*..L]-(b)), from one traversal of all sources.
         sources: 1 .. 256 seed sets as neighbourhood takes them (a set may be empty).  pairs: [np][2] indices into `sources`,
@@ -472,25 +527,27 @@ class EntityGraph:
         iff hop_A(v) == i and hop_B(v) == d - i; a row of `relations` is at level i + 1 iff it joins positions i and i + 1.
         -> the named tuple (distances int32 [np], vertex_ids, vertex_positions, vertex_counts, position_counts) shaped as
         neighbourhood(max_vertices=...) shapes its lists, then the edge fields exactly as neighbourhood_edges returns them.
-        ValueError for a seed outside [0, n), more than 64 seeds, a pair index outside [0, ns) or a negative length;
-        RarcUnsupported for max_length > 8, more than 256 sources or pairs, or a cap above 65536."""
+        relation_types: None or ONE filter (an iterable of type ids) for the whole call — every source traverses under it, so
+        hop_A(v) + hop_B(v) == d stays valid — and a relation row additionally needs its type in the filter.
+        ValueError for a seed outside [0, n), more than 64 seeds, a pair index outside [0, ns), a negative length or per-query
+        filters; RarcUnsupported for max_length > 8, more than 256 sources or pairs, or a cap above 65536."""
         from . import neighbourhood as K
 
         return K.shortest_paths(self, sources, pairs, max_length=max_length, max_vertices=max_vertices, max_edges=max_edges,
-                                relations=relations, as_device=as_device, early_stop=early_stop)
+                                relations=relations, as_device=as_device, early_stop=early_stop, relation_types=relation_types)
 
     def path_chunks(self, mentions, sources, pairs, max_length: int = 4, decay=None, top_k=None, as_device: bool = False,
-                    early_stop: bool = False):
+                    early_stop: bool = False, relation_types=None):
         """shortest_paths, ending in chunks: S_p(c) = sum over c's mentions (e, w) with e on p's paths of w * decay[position(e)],
         decay of max_length + 1 entries -> scores float64 [np][n_chunks], or with top_k (ids, scores, counts), as
         neighbourhood_chunks shapes them."""
         from . import neighbourhood as K
 
         return K.path_chunks(self, mentions, sources, pairs, max_length=max_length, decay=decay, top_k=top_k, as_device=as_device,
-                             early_stop=early_stop)
+                             early_stop=early_stop, relation_types=relation_types)
 
     def connect(self, index, queries, seeds_per_query: int = 5, max_length: int = 4, max_vertices: int = 4096, max_edges: int = 16384,
-                relations=None, as_device: bool = False, early_stop: bool = False):
+                relations=None, as_device: bool = False, early_stop: bool = False, relation_types=None):
         """shortest_paths between the entities a query links to: each query's seeds are the index's own top-`seeds_per_query`
         ids, as expand takes them; every seed is a one-vertex source and the pairs are all i < j within a query (2 <=
         seeds_per_query <= 23), cut into launches of at most 256 sources and pairs.
@@ -499,7 +556,7 @@ class EntityGraph:
         from . import neighbourhood as K
 
         return K.connect(self, index, queries, seeds_per_query=seeds_per_query, max_length=max_length, max_vertices=max_vertices,
-                         max_edges=max_edges, relations=relations, as_device=as_device, early_stop=early_stop)
+                         max_edges=max_edges, relations=relations, as_device=as_device, early_stop=early_stop, relation_types=relation_types)
 
     # ---------------------------------------------------------------------------------------------------------------- components
     def components(self, as_device: bool = False):

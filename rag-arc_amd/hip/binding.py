@@ -282,6 +282,14 @@ SIGNATURES = {
     "rarc_khop_path_edges": (c_int, [c_int64, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int64, c_int, c_void_p, c_size_t,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rarc_khop_paths_limits": (c_int, [ctypes.POINTER(c_int)]),
+    "rarc_graph_types_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "rarc_graph_types": (c_int, [c_void_p, c_size_t, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rarc_khop_step_typed": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p,
+                                     c_size_t, c_void_p, c_void_p]),
+    "rarc_khop_edges_typed": (c_int, [c_int64, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int,
+                                      c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_khop_path_edges_typed": (c_int, [c_int64, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_int, c_void_p,
+                                           c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rarc_sort_reduce_workspace_bytes": (c_size_t, [c_int64]),
     "rarc_sort_reduce": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rarc_sort_reduce_limits": (c_int, [ctypes.POINTER(c_int)]),
