@@ -39,6 +39,25 @@ def chunk_state(p, n_chunks, mentions, weights=None):
     return [x >> WEIGHT_BITS for x in raw_sums(p, n_chunks, mentions, weights)]
 
 
+def chunk_states_batch(states, n_chunks, mentions, weights=None):
+    """`chunk_state` for every row of a uint64 [B][n] array of states at once, in numpy uint64 -> uint64 [B][n_chunks].  The
+    Python-integer functions above stay the definition (tests/test_ppr_batch_ref_host.py finds this one equal to them); the
+    sums are asserted below 2^63 (csrc/ppr.hip proves 2^52)."""
+    import numpy as np
+
+    states = np.asarray(states, dtype=np.uint64)
+    items = sorted(merged(n_chunks, states.shape[1], mentions, weights).items())
+    c = np.asarray([k[0] for k, _ in items], dtype=np.int64)
+    e = np.asarray([k[1] for k, _ in items], dtype=np.int64)
+    w = np.asarray([x for _, x in items], dtype=np.uint64)
+    terms = states[:, e] * w[None, :]                                     # w p < 2^12 * 2^40
+    assert int(states.max()) <= R.ONE and int(terms.max()) < 1 << 63
+    acc = np.zeros((states.shape[0], n_chunks), np.uint64)
+    np.add.at(acc, (np.arange(states.shape[0])[:, None], c[None, :]), terms)
+    assert int(acc.max()) < 1 << 63
+    return acc >> np.uint64(WEIGHT_BITS)
+
+
 def scores(S):
     """S / 2^28 as floats: exact, S < 2^40 < 2^53"""
     return [x / SCORE_ONE for x in S]
@@ -96,4 +115,4 @@ def split_weights(mentions, weights, seed):
     return [m2[i] for i in order], [w2[i] for i in order]
 
 
-__all__ = ["R", "chunk_state", "scores", "topk", "raw_sums", "merged", "chunk_of_degree", "random_mentions", "with_twins", "split_weights"]
+__all__ = ["R", "chunk_state", "chunk_states_batch", "scores", "topk", "raw_sums", "merged", "chunk_of_degree", "random_mentions", "with_twins", "split_weights"]

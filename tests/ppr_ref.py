@@ -83,6 +83,57 @@ def ppr(n, edges, seed_lists, seed_weight_lists=None, **kw):
     return [p for p, _ in out], [it for _, it in out]
 
 
+def ppr_batch(n, edges, seed_lists, seed_weight_lists=None, weights=None, damping=0.85, max_iterations=20, tolerance=0.0):
+    """`ppr` for shapes the Python integers are too slow for: the same rule in numpy uint64 over the whole batch
+    -> (uint64 array [B][n], list of iterations run).  The Python-integer functions above stay the definition: this one is
+    trusted only because tests/test_ppr_batch_ref_host.py finds it equal to them, element for element.
+    Every intermediate is asserted below 2^63 (csrc/ppr.hip's header proves 2^57), so no uint64 wraps unseen."""
+    import numpy as np
+
+    def u64(x):
+        x = np.asarray(x)
+        assert x.size == 0 or int(x.max()) < 1 << 63
+        return x.astype(np.uint64, copy=False)
+
+    B = len(seed_lists)
+    a, tol = damping_q16(damping), tolerance_units(tolerance)
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 2)
+    w = np.ones(len(e), np.int64) if weights is None else np.asarray(weights, dtype=np.int64)
+    assert w.shape == (len(e),) and (len(e) == 0 or (e.min() >= 0 and e.max() < n and (e[:, 0] != e[:, 1]).all() and w.min() >= 1))
+    src, dst = np.concatenate([e[:, 0], e[:, 1]]), np.concatenate([e[:, 1], e[:, 0]])       # the doubled edge list: flow goes src -> dst
+    w2 = u64(np.concatenate([w, w]))
+    W = np.zeros(n, np.int64)
+    np.add.at(W, src, np.concatenate([w, w]))
+    W = u64(W)
+    linked = W > 0
+    t = np.zeros((B, n), np.uint64)
+    for q, seeds in enumerate(seed_lists):
+        ws = None if seed_weight_lists is None else seed_weight_lists[q]
+        t[q] = u64(np.array(teleport(n, seeds, ws), dtype=np.uint64))                       # Python integers <= 2^40: the same floors
+    p = t.copy()
+    its = [0] * B
+    live = np.ones(B, bool)
+    safe_W = np.where(linked, W, np.uint64(1))
+    for _ in range(max_iterations):
+        rows = np.flatnonzero(live)
+        if rows.size == 0:
+            break
+        pl = p[rows]
+        c = np.where(linked[None, :], pl // safe_W[None, :], np.uint64(0))
+        terms = u64(c[:, src] * w2[None, :])                                                # w_uv * c(u) <= p(u) <= 2^40
+        flow = np.zeros_like(pl)
+        np.add.at(flow, (np.arange(rows.size)[:, None], dst[None, :]), terms)
+        flow = u64(np.where(linked[None, :], flow, pl))
+        nxt = u64(np.uint64(65536 - a) * t[rows] + np.uint64(a) * flow) >> np.uint64(16)
+        delta = np.where(nxt > pl, nxt - pl, pl - nxt).max(axis=1)
+        p[rows] = nxt
+        for i, q in enumerate(rows):
+            its[q] += 1
+            if int(delta[i]) <= tol:
+                live[q] = False
+    return p, its
+
+
 def scores(p):
     """p / ONE as floats: exact, p <= 2^40 < 2^53"""
     return [x / ONE for x in p]
@@ -133,6 +184,27 @@ def path_graph(n):
 def star_graph(leaves):
     """hub 0 with `leaves` neighbours"""
     return leaves + 1, [(0, i) for i in range(1, leaves + 1)]
+
+
+def complete_bipartite(a, b):
+    """K(a, b): left vertices 0 .. a - 1, right vertices a .. a + b - 1 -> (n, edges)"""
+    return a + b, [(i, a + j) for i in range(a) for j in range(b)]
+
+
+def with_hub(n, edges, d, weights=None, max_weight=1):
+    """one more vertex, n, joined to the vertices 0 .. d - 1 with weights 1 .. max_weight in turn -> (n + 1, edges, weights)"""
+    assert 1 <= d <= n
+    ws = [1] * len(edges) if weights is None else list(weights)
+    return n + 1, list(edges) + [(v, n) for v in range(d)], ws + [1 + v % max_weight for v in range(d)]
+
+
+def degrees(n, edges):
+    """the number of neighbours of every vertex (edges are undirected pairs, each once)"""
+    deg = [0] * n
+    for a, b in edges:
+        deg[a] += 1
+        deg[b] += 1
+    return deg
 
 
 def random_graph(n, m, seed, max_weight=1):

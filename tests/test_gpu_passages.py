@@ -2,7 +2,13 @@
 tests/passage_ref.py: the [B][n_chunks] scores (S / 2^28, exact) and the top-k ids, scores and counts are equal bit for bit —
 the rule is integer arithmetic, so there is no band.  The shapes are the smallest that reach each form of the kernel: both
 forms, a partial wave and a second one, the 16-byte form and the odd batch that falls off it, a chunk one below, at and above
-the degree at which it is split across a workgroup, chunks without mentions, twins, the largest key, the kernel's own guard."""
+the degree at which it is split across a workgroup, chunks without mentions, twins, the largest key, the kernel's own guard.
+Of ppr_chunks_kernel<BP, QPL, SPLIT> the first cases reach BP = 1, 4, 32 and 64 (2 and 8 only in passing: two device-side
+queries, five for the twins, seven in retrieve_chunks), split at B = 1, 3, 64, 65 only;
+test_the_random_map_in_the_chunk_parallel_forms_between adds BP = 2, 8 and 16, test_a_split_chunk_in_every_form the split form
+at every BP and with two queries per lane, and the two strided cases a grid-stride walk of each launch (their references are
+the numpy forms of ppr_ref and passage_ref, proved equal to the Python integers by tests/test_ppr_batch_ref_host.py).  The
+step's own forms are in tests/test_gpu_ppr.py and tests/test_gpu_ppr_forms.py; DESIGN §4.13e lists instantiation x launch -> case."""
 import random
 
 import numpy as np
@@ -99,6 +105,97 @@ def test_a_random_weighted_graph_in_every_form(g200, batch):
     130: two queries and one 16-byte load per lane"""
     seeds, w = _seed_sets(g200["n"], batch, random.Random(batch))
     _check(*_args(g200), seeds, w, weights=g200["weights"], ks=(1, 10, 150, 157) if batch <= 3 else (10,), g=g200["g"], mm=g200["mm"])
+
+
+def _chunk_form(batch):
+    """(BP, QPL, chunks of queries) of the ppr_chunks_kernel instantiation rarc_ppr_chunks picks: the step's own rule"""
+    from rag_arc_amd.encapsulation.database.graph_db.pagerank import limits
+
+    if batch > limits()["vertex_parallel_max_batch"]:
+        qpl = 2 if batch > 64 and batch % 2 == 0 else 1
+        return 64, qpl, -(-batch // (64 * qpl))
+    bp = 1
+    while bp < batch:
+        bp *= 2
+    return bp, 1, 1
+
+
+def _batch_states(f, seeds, seed_w, **kw):
+    """the PPR states of a batch from ppr_ref's numpy form (proved equal to the Python integers on the host) -> uint64 [B][n]"""
+    return R.ppr_batch(f["n"], f["edges"], seeds, [R.quantise_weights(w) for w in seed_w], weights=f["weights"], **kw)[0]
+
+
+@pytest.mark.parametrize("batch", [2, 5, 8, 9, 16, 17])
+def test_the_random_map_in_the_chunk_parallel_forms_between(g200, batch):
+    """BP = 2, 8 (B = 5 and 8), 16 (9 and 16) and 32 at its smallest batch: the instantiations the cases above pass over"""
+    assert _chunk_form(batch)[:2] == {2: (2, 1), 5: (8, 1), 8: (8, 1), 9: (16, 1), 16: (16, 1), 17: (32, 1)}[batch]
+    seeds, w = _seed_sets(g200["n"], batch, random.Random(500 + batch))
+    _check(*_args(g200), seeds, w, weights=g200["weights"], ks=(10,), g=g200["g"], mm=g200["mm"])
+
+
+@pytest.mark.parametrize("batch", [2, 8, 16, 32, 66, 130, 256])
+def test_a_split_chunk_in_every_form(g200, batch):
+    """chunk 1 has one mention more than a single wave walks: the split form at every BP the cases above leave out, and with two
+    queries per lane (66, 130, 256); chunk 0 and 2 are ordinary, chunk 3 has none"""
+    from rag_arc_amd.encapsulation.database.graph_db.passages import limits
+
+    want_form = {2: (2, 1, 1), 8: (8, 1, 1), 16: (16, 1, 1), 32: (32, 1, 1), 66: (64, 2, 1), 130: (64, 2, 2), 256: (64, 2, 2)}
+    assert _chunk_form(batch) == want_form[batch]
+    n, d = g200["n"], limits()["split_degree"] + 1
+    big, bw = P.chunk_of_degree(n, d, seed=600 + batch, chunk=1)
+    mentions, mweights = [(0, 5), (2, 9), (2, 5)] + big, [7, 4095, 1] + bw
+    mm = _map(4, n, mentions, mweights)
+    assert mm.n_split == 1 and mm.nnz == d + 3
+    seeds, w = _seed_sets(n, batch, random.Random(600 + batch))
+    states = _batch_states(g200, seeds, w, max_iterations=5).tolist()
+    want = _check(n, g200["edges"], 4, mentions, mweights, seeds, w, weights=g200["weights"], ks=(4,), g=g200["g"], mm=mm, states=states,
+                  max_iterations=5)
+    assert all(S[1] > 0 and S[3] == 0 for S in want)
+
+
+def _check_batch(f, n_chunks, mentions, mweights, mm, batch, seed, rows, k=5):
+    """a map too large for passage_ref's Python integers: the scores in full against its numpy form, the top-k of `rows`"""
+    seeds, w = _seed_sets(f["n"], batch, random.Random(seed))
+    want = P.chunk_states_batch(_batch_states(f, seeds, w, max_iterations=5), n_chunks, mentions, mweights)
+    got = f["g"].rank_chunks(mm, seeds, w, max_iterations=5)
+    assert got.dtype == np.float64 and got.shape == (batch, n_chunks)
+    assert np.array_equal(got, want.astype(np.float64) / float(P.SCORE_ONE))      # S < 2^40: both steps exact
+    ids, sc, cnt = f["g"].rank_chunks(mm, seeds, w, max_iterations=5, top_k=k)
+    for q in rows:
+        wi, wsc, wc = P.topk(want[q].tolist(), k)
+        assert cnt[q] == wc and ids[q].tolist() == wi and sc[q].tolist() == wsc, q
+    return want
+
+
+def test_a_strided_walk_over_17000_chunks(g200):
+    """17000 chunks of one to three mentions at B = 65: 2 chunks of queries, 34000 items for the plain launch's 8192 workgroups of
+    4 waves; the chunks from 16384 on are some wave's second visit"""
+    n, n_chunks, batch = g200["n"], 17000, 65
+    assert _chunk_form(batch) == (64, 1, 2) and n_chunks * 2 > 8192 * 4
+    rng = random.Random(700)
+    mentions = [(c, e) for c in range(n_chunks) for e in rng.sample(range(n), 1 + c % 3)]
+    mweights = [rng.randint(1, P.MAX_WEIGHT - 1) for _ in mentions]
+    mm = _map(n_chunks, n, mentions, mweights)
+    assert mm.n_split == 0
+    want = _check_batch(g200, n_chunks, mentions, mweights, mm, batch, seed=701, rows=(0, 31, 64))
+    assert want[:, 8192 * 4 // 2:].any(axis=1).all()
+
+
+def test_a_strided_split_walk_over_1100_chunks(g200):
+    """1100 chunks of 65 mentions at B = 65: every chunk is split, 2200 items for the split launch's 2048 workgroups"""
+    from rag_arc_amd.encapsulation.database.graph_db.passages import limits
+
+    n, n_chunks, batch, d = g200["n"], 1100, 65, limits()["split_degree"] + 1
+    assert _chunk_form(batch) == (64, 1, 2) and n_chunks * 2 > 2048 and d == 65
+    mentions, mweights = [], []
+    for c in range(n_chunks):
+        ms, ws = P.chunk_of_degree(n, d, seed=800 + c, chunk=c)
+        mentions += ms
+        mweights += ws
+    mm = _map(n_chunks, n, mentions, mweights)
+    assert mm.n_split == n_chunks
+    want = _check_batch(g200, n_chunks, mentions, mweights, mm, batch, seed=801, rows=(0, 31, 64))
+    assert want[:, 2048 // 2:].any(axis=1).all()
 
 
 def test_the_largest_key_damping_0_one_seed_weight_4095(g200):

@@ -1,8 +1,12 @@
 """EntityGraph.personalized_pagerank / retrieve on the GPU (csrc/ppr.hip) against the integer restatement tests/ppr_ref.py:
 the fixed-point state p (read back through rarc_ppr_scores as p / 2^40, exact) and the top-k ids, scores and counts are equal
-bit for bit — the rule is integer arithmetic, so there is no band.  The shapes are the smallest that reach each form of the
-kernels: both forms of the step, a partial wave and a second one, the 16-byte form, a hub one below, at and above the degree
-at which a vertex is split across a workgroup, isolated vertices, duplicated and unused seed slots, a query without weight."""
+bit for bit — the rule is integer arithmetic, so there is no band.  The shapes are small ones that reach both forms of the
+step — of ppr_step_kernel<BP, QPL, SPLIT>, BP = 1, 4 and 64 (B = 1, 3 and 40 .. 130) on the random graph, BP = 2 and 8 only
+in passing (two device-side queries, five on 13 vertices, seven in retrieve) — a partial wave and a second one, the 16-byte
+form, a hub one below, at and above the degree at which a vertex is split across a workgroup (B = 1, 3, 64, 65: one query
+per lane), isolated vertices, duplicated and unused seed slots, a query without weight.  Every instantiation on one graph
+(BP = 16 and 32 run nowhere here), the split form at every BP and with two queries per lane, the launch over degree list 3,
+the grid-stride walks and freezing outside B = 40 live in tests/test_gpu_ppr_forms.py."""
 import random
 
 import numpy as np
