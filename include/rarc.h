@@ -1145,6 +1145,38 @@ int rarc_khop_path_edges_typed(int64_t n, int64_t m, int nq, int hops, const voi
                                int32_t* d_out_level_counts, void* stream);
 
 /*
+ * Typed personalized PageRank: gds.pageRank.stream over a relationship-filtered projection, one launch group for a batch of
+ * mixed filters.  The rule (restated by tests/typed_ppr_ref.py): for query q with filter F_q it is the rule of
+ * rarc_ppr_step on the graph whose edges are those with mask & F_q != 0, each at its full weight — W_q(u) = the sum of the
+ * weights of u's allowed edges, c(u) = p(u) // W_q(u), flow(v) = the sum over v's allowed edges of w_uv c(u), flow(v) = p(v) where
+ * W_q(v) = 0 (a vertex isolated under the filter keeps its mass); p', delta_q, freezing, scores and ranking as untyped.  Row q of
+ * any batch is the one-query answer on the filtered edge list, bit for bit, for any order of the pairs and of the queries; an
+ * all-ones filter over non-zero masks is the untyped call; filter 0 crosses nothing: p = t, delta = 0.  A pair's mask is the
+ * OR and its weight the sum over its duplicates, so a pair of types {0, 1} is crossed at its whole weight under filter {0}:
+ * per-type weights are not kept.
+ *
+ * rarc_graph_types_weighted — rarc_graph_types with a weight plane: d_out (rarc_graph_types_weighted_workspace_bytes(n, m) bytes,
+ *   0 for a refused shape) receives what rarc_graph_types writes, byte for byte at the same offsets, followed by t_w uint32 [2m],
+ *   the weight of each slot.  d_weights uint32 [m] beside the pairs — THE weights the graph was built with — or null = all 1.
+ *   The first rarc_graph_types_workspace_bytes(n, m) bytes are a valid d_types of the typed k-hop entries: a graph keeps one copy.
+ * rarc_ppr_seed_typed — rarc_ppr_seed with c_0(v) = t_q(v) // W_q(v), under d_filters uint32 [nq] on the device.
+ * rarc_ppr_step_typed — rarc_ppr_step under d_filters: the same workspace, slots, forms and launches over the same degree lists
+ *   (by total degree); per slot it reads neighbour, mask and weight from d_types.  rarc_ppr_scores, rarc_ppr_topk and
+ *   rarc_ppr_chunks* read the state unchanged.
+ * Limits as the untyped entries'; d_types 256-byte aligned and of exactly the weighted size (the unweighted blob has no weight
+ * plane: RARC_E_WORKSPACE), d_filters 4-byte aligned; refused before any launch.
+ */
+size_t rarc_graph_types_weighted_workspace_bytes(int64_t n, int64_t m);
+int rarc_graph_types_weighted(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, const int64_t* d_pairs, const uint32_t* d_masks,
+                              const uint32_t* d_weights, void* d_out, size_t out_bytes, void* stream);
+int rarc_ppr_seed_typed(const void* d_graph, size_t graph_bytes, const void* d_types, size_t types_bytes, const uint32_t* d_filters, int64_t n,
+                        int64_t m, const int64_t* d_seeds, const uint32_t* d_seed_weights, int nq, int n_slots, void* d_ws, size_t ws_bytes,
+                        void* stream);
+int rarc_ppr_step_typed(const void* d_graph, size_t graph_bytes, const void* d_types, size_t types_bytes, const uint32_t* d_filters, int64_t n,
+                        int64_t m, int nq, int damping_q16, int64_t tolerance, int cur, void* d_ws, size_t ws_bytes, uint32_t* d_done_out,
+                        void* stream);
+
+/*
  * Entity merging: step 4 of the reference's de-duplication (Base_Neo4j.py:714-890, _merge_clusters) — every class of a labelling
  * becomes one entity, and the pair list, the mention CSR and the relation table are contracted onto the survivors without
  * leaving the device.  The rule (restated by tests/merge_ref.py) is in integers; every result is the same bits for

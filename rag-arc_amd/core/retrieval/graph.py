@@ -61,8 +61,9 @@ class HipGraphRetriever(BaseRetriever):
         if relation_types is None:
             return
         if expansion != "k_hop":
-            raise ValueError("relation_types with expansion='ppr': typed personalized PageRank is not built (the weighted degrees would "
-                             "differ per query); use expansion='k_hop'")
+            raise ValueError("relation_types with expansion='ppr': typed personalized PageRank is not built into the retriever: its 'ppr' expansion "
+                             "does not take filters yet; use expansion='k_hop', or call EntityGraph.retrieve_chunks(..., relation_types=) "
+                             "on the retriever's graph")
         from ...encapsulation.database.graph_db.neighbourhood import check_typed, spread_filters
 
         filters = check_typed(graph, relation_types)

@@ -140,46 +140,34 @@ __device__ __forceinline__ u64 khop_query_mask(int nq, int word) {
 // t_adj int32 [2m] | t_mask uint32 [2m] | cursor uint32 [n] | bad u32: a second pair of slot arrays over the blob's row_ptr.
 // rarc_graph_csr hands out a row's slots through an atomic cursor, so no array can be aligned to its `adj` afterwards; here the
 // neighbour and the mask of a slot are written together, in one pass over the pair list that built the graph
-struct KhopTypes {
-  int32_t* adj;
-  uint32_t* mask;
-  uint32_t* cursor;
-  uint32_t* bad;
-  size_t bytes;
-};
-static KhopTypes khop_types_carve(const void* base, int64_t n, int64_t m) {
-  char* b = (char*)base;
-  size_t o = 0;
-  KhopTypes t;
-  auto take = [&](size_t bytes) { char* p = b + o; o += lv_align(bytes); return p; };
-  t.adj = (int32_t*)take((size_t)m * 8);
-  t.mask = (uint32_t*)take((size_t)m * 8);
-  t.cursor = (uint32_t*)take((size_t)n * 4);
-  t.bad = (uint32_t*)take(4);
-  t.bytes = o;
-  return t;
-}
+#include "graph_types.h"
 // the rule of lv_edge_ok (csrc/louvain.hip): a pair rarc_graph_csr skipped has no slots and is skipped here too
 __device__ __forceinline__ bool khop_pair_ok(int64_t a, int64_t b, int64_t n) { return a >= 0 && a < b && b < n; }
 
 // a thread per pair: one slot in each end's row, taken through the cursor.  A slot at or beyond the end of the row (or of the
-// arrays) is not written and counted in `bad`: the pair list is not the one the blob was built from
-__global__ __launch_bounds__(256) void khop_types_fill_kernel(const int64_t* __restrict__ pairs, const uint32_t* __restrict__ masks, int64_t m,
-                                                              int64_t n, const int64_t* __restrict__ row_ptr, uint32_t* cursor, int32_t* adj,
-                                                              uint32_t* mask, uint32_t* bad) {
+// arrays) is not written and counted in `bad`: the pair list is not the one the blob was built from.  WEIGHTED: the pair's
+// weight goes into the same slot of a third plane, `w`; a null `weights` is weight 1 for every pair
+template <bool WEIGHTED>
+__global__ __launch_bounds__(256) void khop_types_fill_kernel(const int64_t* __restrict__ pairs, const uint32_t* __restrict__ masks,
+                                                              const uint32_t* __restrict__ weights, int64_t m, int64_t n,
+                                                              const int64_t* __restrict__ row_ptr, uint32_t* cursor, int32_t* adj, uint32_t* mask,
+                                                              uint32_t* w, uint32_t* bad) {
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < m; e += (int64_t)gridDim.x * 256) {
     const int64_t a = pairs[2 * e], b = pairs[2 * e + 1];
     if (!khop_pair_ok(a, b, n)) continue;
     const uint32_t mk = masks[e];
+    const uint32_t we = WEIGHTED && weights ? weights[e] : 1u;
     const int64_t pa = row_ptr[a] + atomicAdd(&cursor[a], 1u), pb = row_ptr[b] + atomicAdd(&cursor[b], 1u);
     const bool fa = pa >= 0 && pa < row_ptr[a + 1] && pa < 2 * m, fb = pb >= 0 && pb < row_ptr[b + 1] && pb < 2 * m;
     if (fa) {
       adj[pa] = (int32_t)b;
       mask[pa] = mk;
+      if (WEIGHTED) w[pa] = we;
     }
     if (fb) {
       adj[pb] = (int32_t)a;
       mask[pb] = mk;
+      if (WEIGHTED) w[pb] = we;
     }
     if (!fa || !fb) atomicAdd(bad, 1u);
   }
@@ -872,30 +860,51 @@ extern "C" size_t rarc_graph_types_workspace_bytes(int64_t n, int64_t m) {
   return khop_types_carve(nullptr, n, m).bytes;
 }
 
-extern "C" int rarc_graph_types(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, const int64_t* d_pairs, const uint32_t* d_masks,
-                                void* d_out, size_t out_bytes, void* stream) {
-  RARC_RANGE();
-  RARC_REQUIRE(d_graph && d_pairs && d_masks && d_out, RARC_E_INVALID, "rarc_graph_types: null pointer");
+// the body of rarc_graph_types and rarc_graph_types_weighted: the same checks, the same fill kernel, the same wait for `bad`
+template <bool WEIGHTED>
+static int khop_graph_types(const char* name, const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, const int64_t* d_pairs,
+                            const uint32_t* d_masks, const uint32_t* d_weights, void* d_out, size_t out_bytes, void* stream) {
+  RARC_REQUIRE(d_graph && d_pairs && d_masks && d_out, RARC_E_INVALID, "%s: null pointer", name);
   RARC_REQUIRE(KHOP_ALIGNED(d_graph, 256) && KHOP_ALIGNED(d_out, 256), RARC_E_INVALID,
-               "rarc_graph_types: the graph or the typed adjacency is not 256-byte aligned");
-  RARC_REQUIRE(KHOP_ALIGNED(d_pairs, 8) && KHOP_ALIGNED(d_masks, 4), RARC_E_INVALID,
-               "rarc_graph_types: an array is not aligned to its element (pairs 8 bytes, masks 4)");
-  RARC_REQUIRE(lv_shape_ok(n, m), RARC_E_INVALID, "rarc_graph_types: n=%lld m=%lld out of range (2 <= n < 2^31 - 1, 1 <= m < 2^30)",
-               (long long)n, (long long)m);
+               "%s: the graph or the typed adjacency is not 256-byte aligned", name);
+  RARC_REQUIRE(KHOP_ALIGNED(d_pairs, 8) && KHOP_ALIGNED(d_masks, 4) && KHOP_ALIGNED(d_weights, 4), RARC_E_INVALID,
+               "%s: an array is not aligned to its element (pairs 8 bytes, masks%s 4)", name, WEIGHTED ? " and weights" : "");
+  RARC_REQUIRE(lv_shape_ok(n, m), RARC_E_INVALID, "%s: n=%lld m=%lld out of range (2 <= n < 2^31 - 1, 1 <= m < 2^30)", name, (long long)n,
+               (long long)m);
   const LvGraph g = lv_graph_carve(d_graph, n, m);
-  RARC_REQUIRE(graph_bytes >= g.bytes, RARC_E_WORKSPACE, "rarc_graph_types: graph workspace of %zu bytes, %zu needed", graph_bytes, g.bytes);
+  RARC_REQUIRE(graph_bytes >= g.bytes, RARC_E_WORKSPACE, "%s: graph workspace of %zu bytes, %zu needed", name, graph_bytes, g.bytes);
   const KhopTypes t = khop_types_carve(d_out, n, m);
-  RARC_REQUIRE(out_bytes >= t.bytes, RARC_E_WORKSPACE, "rarc_graph_types: typed adjacency of %zu bytes, %zu needed", out_bytes, t.bytes);
+  const size_t need = WEIGHTED ? t.weighted_bytes : t.bytes;
+  RARC_REQUIRE(out_bytes >= need, RARC_E_WORKSPACE, "%s: typed adjacency of %zu bytes, %zu needed", name, out_bytes, need);
   hipStream_t s = (hipStream_t)stream;
-  RARC_HIP_CHECK(hipMemsetAsync(d_out, 0, t.bytes, s));  // a slot no pair fills: neighbour 0 under mask 0, crossed by nobody
-  hipLaunchKernelGGL(khop_types_fill_kernel, dim3(lv_grid(m, 256, 4096)), dim3(256), 0, s, d_pairs, d_masks, m, n, (const int64_t*)g.row_ptr,
-                     t.cursor, t.adj, t.mask, t.bad);
+  RARC_HIP_CHECK(hipMemsetAsync(d_out, 0, need, s));     // a slot no pair fills: neighbour 0 under mask 0 (and weight 0), crossed by nobody
+  hipLaunchKernelGGL(khop_types_fill_kernel<WEIGHTED>, dim3(lv_grid(m, 256, 4096)), dim3(256), 0, s, d_pairs, d_masks, d_weights, m, n,
+                     (const int64_t*)g.row_ptr, t.cursor, t.adj, t.mask, t.w, t.bad);
   RARC_HIP_CHECK(hipGetLastError());
   uint32_t bad = 0;                                      // built once a graph: the entry waits for the count and reports it
   RARC_HIP_CHECK(hipMemcpyAsync(&bad, t.bad, 4, hipMemcpyDeviceToHost, s));
   RARC_HIP_CHECK(hipStreamSynchronize(s));
-  RARC_REQUIRE(bad == 0, RARC_E_INVALID, "rarc_graph_types: %u pairs found their rows full: not the pair list the graph was built from", bad);
+  RARC_REQUIRE(bad == 0, RARC_E_INVALID, "%s: %u pairs found their rows full: not the pair list the graph was built from", name, bad);
   return RARC_OK;
+}
+
+extern "C" int rarc_graph_types(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, const int64_t* d_pairs, const uint32_t* d_masks,
+                                void* d_out, size_t out_bytes, void* stream) {
+  RARC_RANGE();
+  return khop_graph_types<false>("rarc_graph_types", d_graph, graph_bytes, n, m, d_pairs, d_masks, nullptr, d_out, out_bytes, stream);
+}
+
+// the typed adjacency with a weight plane behind it: the first rarc_graph_types_workspace_bytes(n, m) bytes are
+// what rarc_graph_types writes, so the typed k-hop entries take the same buffer
+extern "C" size_t rarc_graph_types_weighted_workspace_bytes(int64_t n, int64_t m) {
+  if (!lv_shape_ok(n, m)) return 0;
+  return khop_types_carve(nullptr, n, m).weighted_bytes;
+}
+
+extern "C" int rarc_graph_types_weighted(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, const int64_t* d_pairs,
+                                         const uint32_t* d_masks, const uint32_t* d_weights, void* d_out, size_t out_bytes, void* stream) {
+  RARC_RANGE();
+  return khop_graph_types<true>("rarc_graph_types_weighted", d_graph, graph_bytes, n, m, d_pairs, d_masks, d_weights, d_out, out_bytes, stream);
 }
 
 extern "C" int rarc_khop_step(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, int nq, int hops, int hop, void* d_ws,

@@ -33,9 +33,23 @@
 // waves of a workgroup, which are joined by integer adds in LDS: each wave writes 64 (or 128) consecutive 8-byte words, wave 0
 // reads them back the same way — consecutive lanes on consecutive bank pairs, no conflict.
 //
+// Typed PPR (tests/typed_ppr_ref.py restates it): query q carries a uint32 filter F_q and the rule above runs on
+// the graph of the edges whose mask shares a bit with it, each at its full weight:
+//   W_q(u) = sum over u's slots (v, M, w) with M & F_q != 0 of w;   c(u) = p(u) // W_q(u);   flow(v) sums the same slots
+//   (W_q(v) = 0: flow(v) = p(v), a vertex isolated under the filter keeps its mass)
+// The step already walks every slot of v's row once per query lane, so W_q(v) is a second accumulator beside flow(v), summed
+// under the same test and joined by the same shuffles and the same LDS words — no [n][B] array of degrees.  It is 32 bits wide:
+// W_q <= W < 2^31.  The slots come from the typed adjacency with its weight plane (rarc_graph_types_weighted: neighbour, mask
+// and weight side by side); the state, the workspace, the degree lists (by total degree, which is what bounds the walk) and
+// every reader are the untyped ones.  The overflow argument carries over word for word with W_q for W: u contributes
+// c(u) * sum over its allowed slots of w = c(u) W_q(u) <= p(u) to the flows, a vertex with W_q = 0 contributes p(v), so mass
+// is still never created, w_uv * c(u) <= W_q(u) * c(u) <= p(u) <= 2^40 and every bound above holds.  A lane whose filters meet
+// none of a slot's types does not load that neighbour's row of c.
+//
 // The last section projects the state through a mention map onto chunks (rarc_ppr_chunks*): its rule, its
 // bounds and its guards are stated there.
 #include "graph_csr.h"
+#include "graph_types.h"
 #include "chunk_ws.h"
 #include "canon_topk.h"
 
@@ -100,7 +114,8 @@ __global__ __launch_bounds__(256) void ppr_seed_kernel(const int64_t* __restrict
     if (v >= 0 && v < n && w) t[(size_t)v * B + q] += ((u64)w << PPR_ONE_SHIFT) / wq;
   }
 }
-// p_0 = t, c_0 = t // W
+// p_0 = t, c_0 = t // W.  TYPED: c_0 = 0 here, ppr_seed_typed_kernel writes t // W_q at the seeds (t is 0 elsewhere)
+template <bool TYPED>
 __global__ __launch_bounds__(256) void ppr_init_kernel(int64_t n, int B, const uint32_t* __restrict__ k, const u64* __restrict__ t, u64* p,
                                                        u64* c) {
   const int64_t total = n * B;
@@ -108,11 +123,33 @@ __global__ __launch_bounds__(256) void ppr_init_kernel(int64_t n, int B, const u
     const u64 x = t[i];
     p[i] = x;
     u64 cv = 0;
-    if (x) {
+    if (!TYPED && x) {
       const u64 w = k[i / B];
       cv = w ? x / w : 0;
     }
     c[i] = cv;
+  }
+}
+// a wave per (query, seed slot): W_q of the seed vertex from its typed row, c_0(v) = t_q(v) // W_q(v).  t_q is non-zero on
+// the seeds only; a vertex that repeats among q's slots is written twice with the same value
+__global__ __launch_bounds__(256) void ppr_seed_typed_kernel(const int64_t* __restrict__ seeds, const uint32_t* __restrict__ filters, int B, int s,
+                                                             int64_t n, const int64_t* __restrict__ row_ptr, const uint32_t* __restrict__ mask,
+                                                             const uint32_t* __restrict__ adj_w, const u64* __restrict__ t, u64* c) {
+  const int lane = threadIdx.x & 63;
+  const int item = blockIdx.x * 4 + (threadIdx.x >> 6);                // (wave-uniform)
+  if (item >= B * s) return;
+  const int q = item / s;
+  const int64_t v = seeds[item];
+  if (v < 0 || v >= n) return;
+  const uint32_t f = filters[q];
+  const int64_t r0 = row_ptr[v], r1 = row_ptr[v + 1];
+  uint32_t wq = 0;
+  for (int64_t e = r0 + lane; e < r1; e += 64) wq += (mask[e] & f) ? adj_w[e] : 0u;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) wq += (uint32_t)__shfl_xor((int)wq, d, 64);
+  if (lane == 0) {
+    const size_t at = (size_t)v * B + q;
+    c[at] = wq ? t[at] / wq : 0;
   }
 }
 
@@ -122,6 +159,8 @@ struct PprStepArgs {
   const int32_t* adj;
   const uint32_t* adj_w;
   const uint32_t* k;
+  const uint32_t* mask;                                     // TYPED: adj | mask | adj_w are the typed slot arrays, `k` is not read
+  const uint32_t* filters;                                  // TYPED: uint32 [B]
   const u64* t;
   u64* p;
   const u64* c_old;
@@ -146,12 +185,14 @@ __device__ __forceinline__ void ppr_load(const u64* at, u64 (&x)[QPL]) {
 
 // BP: query lanes per neighbour slot (64: a lane is a query), QPL: queries per lane, SPLIT: a workgroup per vertex of a degree
 // list, its waves joined in LDS; otherwise a wave per (vertex, chunk of BP * QPL queries) over every vertex, those of more
-// than PPR_SPLIT_DEGREE neighbours left to the SPLIT launch
-template <int BP, int QPL, bool SPLIT>
+// than PPR_SPLIT_DEGREE neighbours left to the SPLIT launch.  TYPED: a slot counts for query q iff its mask meets F_q, and
+// W_q(v), summed beside flow(v) under that test, stands where the untyped step reads k[v]
+template <int BP, int QPL, bool SPLIT, bool TYPED = false>
 __global__ __launch_bounds__(256) void ppr_step_kernel(const PprStepArgs p, const int32_t* __restrict__ list, const int64_t* __restrict__ list_count) {
   constexpr int NSLOT = 64 / BP;
   constexpr int STEP = SPLIT ? 4 * NSLOT : NSLOT;
   __shared__ u64 s_part[SPLIT ? 4 * BP * QPL : 1];
+  __shared__ uint32_t s_wq[SPLIT && TYPED ? 4 * BP * QPL : 1];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int slot = lane / BP, ql = lane % BP;
   const int B = p.B;
@@ -164,6 +205,8 @@ __global__ __launch_bounds__(256) void ppr_step_kernel(const PprStepArgs p, cons
   for (int i = 0; i < QPL; ++i) my_delta[i] = 0;
   int q_prev = -1;
   uint32_t dn[QPL];
+  uint32_t f[QPL];                                                     // TYPED: the filters of this lane's live queries, 0 for a frozen one
+  uint32_t f_any = 0;                                                  // ... and their OR: a slot it does not meet is not loaded
   for (int64_t item = first; item < items; item += stride) {
     const int64_t vi = item / chunks;
     const int chunk = (int)(item - vi * chunks);
@@ -175,6 +218,14 @@ __global__ __launch_bounds__(256) void ppr_step_kernel(const PprStepArgs p, cons
     if (q != q_prev) {                                                 // (once: the launcher's grids keep a wave on its chunk)
 #pragma unroll
       for (int i = 0; i < QPL; ++i) dn[i] = in_b ? p.done[q + i] : 1u;
+      if (TYPED) {
+        f_any = 0;
+#pragma unroll
+        for (int i = 0; i < QPL; ++i) {
+          f[i] = dn[i] ? 0u : p.filters[q + i];                        // (dn = 1 past the batch: nothing is read there)
+          f_any |= f[i];
+        }
+      }
       if (q_prev >= 0 && q_prev < B) {
 #pragma unroll
         for (int i = 0; i < QPL; ++i)
@@ -188,58 +239,91 @@ __global__ __launch_bounds__(256) void ppr_step_kernel(const PprStepArgs p, cons
 #pragma unroll
     for (int i = 0; i < QPL; ++i) live = live || !dn[i];
     u64 acc[QPL];
+    uint32_t wq[QPL];                                                  // TYPED: W_q(v) <= W(v) < 2^31
 #pragma unroll
-    for (int i = 0; i < QPL; ++i) acc[i] = 0;
+    for (int i = 0; i < QPL; ++i) acc[i] = 0, wq[i] = 0;
     if (live) {
       int64_t e = (SPLIT ? wave * NSLOT : 0) + slot;
       for (; e + 3 * STEP < deg; e += 4 * STEP) {                      // four neighbours in flight
         int32_t u[4];
         uint32_t w[4];
+        uint32_t mk[4];
         u64 x[4][QPL];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           u[j] = p.adj[r0 + e + j * STEP];
           w[j] = p.adj_w[r0 + e + j * STEP];
+          if (TYPED) mk[j] = p.mask[r0 + e + j * STEP];
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) ppr_load<QPL>(p.c_old + (size_t)u[j] * B + q, x[j]);
+        for (int j = 0; j < 4; ++j) {
+          if (!TYPED || (mk[j] & f_any)) {
+            ppr_load<QPL>(p.c_old + (size_t)u[j] * B + q, x[j]);
+          } else {
+#pragma unroll
+            for (int i = 0; i < QPL; ++i) x[j][i] = 0;
+          }
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-          for (int i = 0; i < QPL; ++i) acc[i] += (u64)w[j] * x[j][i];
+          for (int i = 0; i < QPL; ++i) {
+            const uint32_t wj = !TYPED || (mk[j] & f[i]) ? w[j] : 0u;
+            acc[i] += (u64)wj * x[j][i];
+            if (TYPED) wq[i] += wj;
+          }
       }
       for (; e < deg; e += STEP) {
         const int32_t u = p.adj[r0 + e];
         const uint32_t w = p.adj_w[r0 + e];
+        const uint32_t mk = TYPED ? p.mask[r0 + e] : 0u;
         u64 x[QPL];
-        ppr_load<QPL>(p.c_old + (size_t)u * B + q, x);
+        if (!TYPED || (mk & f_any)) {
+          ppr_load<QPL>(p.c_old + (size_t)u * B + q, x);
+        } else {
 #pragma unroll
-        for (int i = 0; i < QPL; ++i) acc[i] += (u64)w * x[i];
+          for (int i = 0; i < QPL; ++i) x[i] = 0;
+        }
+#pragma unroll
+        for (int i = 0; i < QPL; ++i) {
+          const uint32_t wj = !TYPED || (mk & f[i]) ? w : 0u;
+          acc[i] += (u64)wj * x[i];
+          if (TYPED) wq[i] += wj;
+        }
       }
     }
     // the slots of a wave: integer shuffle-adds (every lane takes part, a frozen or idle one with zeros)
 #pragma unroll
     for (int i = 0; i < QPL; ++i)
 #pragma unroll
-      for (int d = BP; d < 64; d <<= 1) acc[i] += (u64)__shfl_xor((long long)acc[i], d, 64);
+      for (int d = BP; d < 64; d <<= 1) {
+        acc[i] += (u64)__shfl_xor((long long)acc[i], d, 64);
+        if (TYPED) wq[i] += (uint32_t)__shfl_xor((int)wq[i], d, 64);
+      }
     if (SPLIT) {                                                       // the waves of the workgroup: integer adds in LDS
       if (slot == 0) {
 #pragma unroll
-        for (int i = 0; i < QPL; ++i) s_part[(wave * BP + ql) * QPL + i] = acc[i];
+        for (int i = 0; i < QPL; ++i) {
+          s_part[(wave * BP + ql) * QPL + i] = acc[i];
+          if (TYPED) s_wq[(wave * BP + ql) * QPL + i] = wq[i];
+        }
       }
       __syncthreads();
       if (wave == 0 && slot == 0) {
 #pragma unroll
-        for (int i = 0; i < QPL; ++i)
+        for (int i = 0; i < QPL; ++i) {
           acc[i] = (s_part[ql * QPL + i] + s_part[(BP + ql) * QPL + i]) + (s_part[(2 * BP + ql) * QPL + i] + s_part[(3 * BP + ql) * QPL + i]);
+          if (TYPED) wq[i] = (s_wq[ql * QPL + i] + s_wq[(BP + ql) * QPL + i]) + (s_wq[(2 * BP + ql) * QPL + i] + s_wq[(3 * BP + ql) * QPL + i]);
+        }
       }
       __syncthreads();
     }
     if (slot == 0 && in_b && (!SPLIT || wave == 0)) {
-      const u64 wv = p.k[v];
+      const u64 wk = TYPED ? 0 : p.k[v];
       const size_t at = (size_t)v * B + q;
 #pragma unroll
       for (int i = 0; i < QPL; ++i) {
+        const u64 wv = TYPED ? (u64)wq[i] : wk;
         if (dn[i]) {                                                   // frozen: p stays, c moves to the slot the next step reads
           p.c_new[at + i] = p.c_old[at + i];
           continue;
@@ -375,26 +459,42 @@ extern "C" int rarc_ppr_seed(const void* d_graph, size_t graph_bytes, int64_t n,
   RARC_HIP_CHECK(hipMemsetAsync(ws.delta, 0, PPR_CTL_BYTES, s));
   RARC_HIP_CHECK(hipMemsetAsync(ws.t, 0, (size_t)n * nq * 8, s));
   hipLaunchKernelGGL(ppr_seed_kernel, dim3(1), dim3(256), 0, s, d_seeds, d_seed_weights, nq, n_slots, n, ws.t);
-  hipLaunchKernelGGL(ppr_init_kernel, dim3(lv_grid(n * nq, 256, 4096)), dim3(256), 0, s, n, nq, (const uint32_t*)g.k, (const u64*)ws.t, ws.p,
+  hipLaunchKernelGGL(ppr_init_kernel<false>, dim3(lv_grid(n * nq, 256, 4096)), dim3(256), 0, s, n, nq, (const uint32_t*)g.k, (const u64*)ws.t, ws.p,
                      ws.c[0]);
   RARC_HIP_CHECK(hipGetLastError());
   return RARC_OK;
 }
 
-template <int BP, int QPL>
+template <int BP, int QPL, bool TYPED>
 static void ppr_launch_step(const PprStepArgs& p, const LvGraph& g, int64_t n, int64_t m, hipStream_t s) {
   const int chunks = (p.B + BP * QPL - 1) / (BP * QPL);
   // every grid is a multiple of the chunk count, so the stride of a wave's walk is one too: a wave keeps its chunk of queries
   auto grid = [chunks](int64_t items, int per_block, int cap) { return (lv_grid(items, per_block, cap) + chunks - 1) / chunks * chunks; };
-  hipLaunchKernelGGL((ppr_step_kernel<BP, QPL, false>), dim3(grid(n * chunks, 4, 8192)), dim3(256), 0, s, p, (const int32_t*)nullptr,
+  hipLaunchKernelGGL((ppr_step_kernel<BP, QPL, false, TYPED>), dim3(grid(n * chunks, 4, 8192)), dim3(256), 0, s, p, (const int32_t*)nullptr,
                      (const int64_t*)nullptr);
   const int64_t dmax = lv_max_degree(n, m);              // no vertex of this graph has more neighbours: skip the lists that must be empty
   if (dmax > LV_DEG_WAVE)
-    hipLaunchKernelGGL((ppr_step_kernel<BP, QPL, true>), dim3(grid(n * chunks, 1, 2048)), dim3(256), 0, s, p, (const int32_t*)g.list[2],
+    hipLaunchKernelGGL((ppr_step_kernel<BP, QPL, true, TYPED>), dim3(grid(n * chunks, 1, 2048)), dim3(256), 0, s, p, (const int32_t*)g.list[2],
                        (const int64_t*)&g.hdr[LV_H_LIST + 2]);
   if (dmax > LV_DEG_LDS)
-    hipLaunchKernelGGL((ppr_step_kernel<BP, QPL, true>), dim3(grid((n / LV_DEG_LDS + 1) * chunks, 1, 2048)), dim3(256), 0, s, p,
+    hipLaunchKernelGGL((ppr_step_kernel<BP, QPL, true, TYPED>), dim3(grid((n / LV_DEG_LDS + 1) * chunks, 1, 2048)), dim3(256), 0, s, p,
                        (const int32_t*)g.list[3], (const int64_t*)&g.hdr[LV_H_LIST + 3]);
+}
+
+// the form: vertex-parallel up to PPR_VERTEX_PARALLEL_MAX_B queries (BP = the power of two >= B), query-parallel beyond,
+// two queries per lane when B is even and more than one wave wide
+template <bool TYPED>
+static void ppr_pick_step(const PprStepArgs& p, const LvGraph& g, int64_t n, int64_t m, hipStream_t s) {
+  const int nq = p.B;
+  if (nq > PPR_VERTEX_PARALLEL_MAX_B) {
+    if (nq > 64 && nq % 2 == 0) ppr_launch_step<64, 2, TYPED>(p, g, n, m, s);
+    else ppr_launch_step<64, 1, TYPED>(p, g, n, m, s);
+  } else if (nq > 16) ppr_launch_step<32, 1, TYPED>(p, g, n, m, s);
+  else if (nq > 8) ppr_launch_step<16, 1, TYPED>(p, g, n, m, s);
+  else if (nq > 4) ppr_launch_step<8, 1, TYPED>(p, g, n, m, s);
+  else if (nq > 2) ppr_launch_step<4, 1, TYPED>(p, g, n, m, s);
+  else if (nq > 1) ppr_launch_step<2, 1, TYPED>(p, g, n, m, s);
+  else ppr_launch_step<1, 1, TYPED>(p, g, n, m, s);
 }
 
 extern "C" int rarc_ppr_step(const void* d_graph, size_t graph_bytes, int64_t n, int64_t m, int nq, int damping_q16, int64_t tolerance,
@@ -415,6 +515,8 @@ extern "C" int rarc_ppr_step(const void* d_graph, size_t graph_bytes, int64_t n,
   p.adj = g.adj;
   p.adj_w = g.adj_w;
   p.k = g.k;
+  p.mask = nullptr;
+  p.filters = nullptr;
   p.t = ws.t;
   p.p = ws.p;
   p.c_old = ws.c[cur];
@@ -425,17 +527,76 @@ extern "C" int rarc_ppr_step(const void* d_graph, size_t graph_bytes, int64_t n,
   p.B = nq;
   p.a = (uint32_t)damping_q16;
   RARC_HIP_CHECK(hipMemsetAsync(ws.delta, 0, (size_t)PPR_MAX_B * 8, s));
-  // the form: vertex-parallel up to PPR_VERTEX_PARALLEL_MAX_B queries (BP = the power of two >= B), query-parallel beyond,
-  // two queries per lane when B is even and more than one wave wide
-  if (nq > PPR_VERTEX_PARALLEL_MAX_B) {
-    if (nq > 64 && nq % 2 == 0) ppr_launch_step<64, 2>(p, g, n, m, s);
-    else ppr_launch_step<64, 1>(p, g, n, m, s);
-  } else if (nq > 16) ppr_launch_step<32, 1>(p, g, n, m, s);
-  else if (nq > 8) ppr_launch_step<16, 1>(p, g, n, m, s);
-  else if (nq > 4) ppr_launch_step<8, 1>(p, g, n, m, s);
-  else if (nq > 2) ppr_launch_step<4, 1>(p, g, n, m, s);
-  else if (nq > 1) ppr_launch_step<2, 1>(p, g, n, m, s);
-  else ppr_launch_step<1, 1>(p, g, n, m, s);
+  ppr_pick_step<false>(p, g, n, m, s);
+  hipLaunchKernelGGL(ppr_mark_kernel, dim3(1), dim3(256), 0, s, nq, (const u64*)ws.delta, (u64)tolerance, ws.done, d_done_out);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+// ---- typed PPR: the entries ------------------------------------------------------------------------------------------
+#define PPR_ALIGNED(P, A) (((uintptr_t)(P) & (uintptr_t)((A)-1)) == 0)
+// what the typed entries add to the untyped checks: the weighted typed adjacency and the filters
+#define PPR_TYPED_CHECKS(NAME)                                                                                                          \
+  RARC_REQUIRE(PPR_ALIGNED(d_types, 256), RARC_E_INVALID, NAME ": the typed adjacency is not 256-byte aligned");                   \
+  RARC_REQUIRE(PPR_ALIGNED(d_filters, 4), RARC_E_INVALID, NAME ": the filters are not 4-byte aligned");                            \
+  PPR_SHAPE_CHECKS(NAME);                                                                                                               \
+  const LvGraph g = lv_graph_carve(d_graph, n, m);                                                                                      \
+  RARC_REQUIRE(graph_bytes >= g.bytes, RARC_E_WORKSPACE, NAME ": graph workspace of %zu bytes, %zu needed", graph_bytes, g.bytes);      \
+  const KhopTypes ty = khop_types_carve(d_types, n, m);                                                                                 \
+  RARC_REQUIRE(types_bytes == ty.weighted_bytes, RARC_E_WORKSPACE,                                                                      \
+               NAME ": typed adjacency of %zu bytes, not the %zu of rarc_graph_types_weighted (the unweighted one has no weight plane)", \
+               types_bytes, ty.weighted_bytes)
+
+extern "C" int rarc_ppr_seed_typed(const void* d_graph, size_t graph_bytes, const void* d_types, size_t types_bytes, const uint32_t* d_filters,
+                                   int64_t n, int64_t m, const int64_t* d_seeds, const uint32_t* d_seed_weights, int nq, int n_slots, void* d_ws,
+                                   size_t ws_bytes, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_graph && d_types && d_filters && d_seeds && d_seed_weights && d_ws, RARC_E_INVALID, "rarc_ppr_seed_typed: null pointer");
+  PPR_TYPED_CHECKS("rarc_ppr_seed_typed");
+  RARC_REQUIRE(n_slots >= 1 && n_slots <= PPR_MAX_SEEDS, RARC_E_INVALID, "rarc_ppr_seed_typed: %d seed slots out of range (1 <= s <= %d)",
+               n_slots, PPR_MAX_SEEDS);
+  hipStream_t s = (hipStream_t)stream;
+  RARC_HIP_CHECK(hipMemsetAsync(ws.delta, 0, PPR_CTL_BYTES, s));
+  RARC_HIP_CHECK(hipMemsetAsync(ws.t, 0, (size_t)n * nq * 8, s));
+  hipLaunchKernelGGL(ppr_seed_kernel, dim3(1), dim3(256), 0, s, d_seeds, d_seed_weights, nq, n_slots, n, ws.t);
+  hipLaunchKernelGGL(ppr_init_kernel<true>, dim3(lv_grid(n * nq, 256, 4096)), dim3(256), 0, s, n, nq, (const uint32_t*)nullptr, (const u64*)ws.t,
+                     ws.p, ws.c[0]);
+  hipLaunchKernelGGL(ppr_seed_typed_kernel, dim3((nq * n_slots + 3) / 4), dim3(256), 0, s, d_seeds, d_filters, nq, n_slots, n,
+                     (const int64_t*)g.row_ptr, (const uint32_t*)ty.mask, (const uint32_t*)ty.w, (const u64*)ws.t, ws.c[0]);
+  RARC_HIP_CHECK(hipGetLastError());
+  return RARC_OK;
+}
+
+extern "C" int rarc_ppr_step_typed(const void* d_graph, size_t graph_bytes, const void* d_types, size_t types_bytes, const uint32_t* d_filters,
+                                   int64_t n, int64_t m, int nq, int damping_q16, int64_t tolerance, int cur, void* d_ws, size_t ws_bytes,
+                                   uint32_t* d_done_out, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(d_graph && d_types && d_filters && d_ws, RARC_E_INVALID, "rarc_ppr_step_typed: null pointer");
+  PPR_TYPED_CHECKS("rarc_ppr_step_typed");
+  RARC_REQUIRE(damping_q16 >= 0 && damping_q16 < 65536, RARC_E_INVALID,
+               "rarc_ppr_step_typed: damping %d / 65536 out of range (0 <= damping < 1)", damping_q16);
+  RARC_REQUIRE(tolerance >= 0 && tolerance <= (1ll << PPR_ONE_SHIFT), RARC_E_INVALID,
+               "rarc_ppr_step_typed: tolerance of %lld units out of range (0 <= tolerance <= 2^40)", (long long)tolerance);
+  RARC_REQUIRE(cur == 0 || cur == 1, RARC_E_INVALID, "rarc_ppr_step_typed: slot %d is neither 0 nor 1", cur);
+  hipStream_t s = (hipStream_t)stream;
+  PprStepArgs p;
+  p.row_ptr = g.row_ptr;
+  p.adj = ty.adj;
+  p.adj_w = ty.w;
+  p.k = nullptr;
+  p.mask = ty.mask;
+  p.filters = d_filters;
+  p.t = ws.t;
+  p.p = ws.p;
+  p.c_old = ws.c[cur];
+  p.c_new = ws.c[cur ^ 1];
+  p.delta = ws.delta;
+  p.done = ws.done;
+  p.n = n;
+  p.B = nq;
+  p.a = (uint32_t)damping_q16;
+  RARC_HIP_CHECK(hipMemsetAsync(ws.delta, 0, (size_t)PPR_MAX_B * 8, s));
+  ppr_pick_step<true>(p, g, n, m, s);
   hipLaunchKernelGGL(ppr_mark_kernel, dim3(1), dim3(256), 0, s, nq, (const u64*)ws.delta, (u64)tolerance, ws.done, d_done_out);
   RARC_HIP_CHECK(hipGetLastError());
   return RARC_OK;
@@ -626,7 +787,6 @@ extern "C" size_t rarc_ppr_chunks_workspace_bytes(int64_t n_chunks, int nq) {
   return ppr_chunk_carve(nullptr, n_chunks, nq).bytes;
 }
 
-#define PPR_ALIGNED(P, A) (((uintptr_t)(P) & (uintptr_t)((A)-1)) == 0)
 #define PPR_CHUNK_SHAPE_CHECKS(NAME)                                                                                                     \
   RARC_REQUIRE(n_chunks >= 1 && n_chunks < PPR_CHUNK_N_LIMIT, RARC_E_INVALID, NAME ": n_chunks=%lld out of range (1 <= n_chunks < 2^31 - 1)", \
                (long long)n_chunks);                                                                                                     \

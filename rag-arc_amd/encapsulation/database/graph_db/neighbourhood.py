@@ -198,8 +198,26 @@ def _single_filter(graph, relation_types):
     return filters
 
 
-def typed_adjacency(graph):
-    """The graph's typed slot arrays (rarc_graph_types), built on the first typed call and kept -> the device buffer"""
+def typed_adjacency(graph, weighted: bool = False):
+    """The graph's typed slot arrays (rarc_graph_types), built on the first typed call and kept -> the device buffer.
+    weighted: the same arrays with their weight plane behind them (rarc_graph_types_weighted), built on the first
+    typed PPR call and kept; from then on the k-hop entries are handed its prefix, so a graph holds one copy of the planes"""
+    tw = getattr(graph, "_typed_adj_weighted", None)
+    if weighted and tw is None:
+        t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m
+        need, prefix = int(lib.rarc_graph_types_weighted_workspace_bytes(n, m)), int(lib.rarc_graph_types_workspace_bytes(n, m))
+        if need == 0:
+            raise B.RarcError(f"typed PageRank: n={n}, m={m} refused by rarc_graph_types_weighted_workspace_bytes")
+        tw = t.empty(need, dtype=t.uint8, device=graph.device)
+        stream = t.cuda.current_stream(graph.device).cuda_stream
+        pw = graph._pair_weights
+        B.check(lib.rarc_graph_types_weighted(graph._graph.data_ptr(), graph._graph.numel(), n, m, graph._pairs.data_ptr(),
+                                              graph._type_masks.data_ptr(), pw.data_ptr() if pw is not None else None, tw.data_ptr(), tw.numel(),
+                                              stream), "rarc_graph_types_weighted")
+        graph._typed_adj_weighted = tw
+        graph._typed_adj = tw[:prefix]                                  # (an unweighted blob built earlier is let go)
+    if weighted:
+        return tw
     ta = getattr(graph, "_typed_adj", None)
     if ta is None:
         t, lib, n, m = graph.torch, graph.lib, graph.n, graph.m

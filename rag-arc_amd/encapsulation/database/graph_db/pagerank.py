@@ -301,8 +301,19 @@ class EntityGraph:
         return t.from_numpy(sd).to(self.device), t.from_numpy(wq.view(np.int32)).to(self.device)
 
     # ---------------------------------------------------------------------------------------------------------------- the run
-    def _iterate(self, sd, wd, a: int, tol: int, max_iterations: int) -> int:
-        """seeds one launch batch (<= 256 queries) and runs its steps in the workspace -> `cur`, as the next step would get it"""
+    def _typed_filters(self, relation_types, seeds=None):
+        """relation_types as the query calls take it -> None (the untyped run), or host uint32 filters; checked as the traversal
+        calls check theirs, before anything is uploaded.  seeds: where the batch is known here, the filter count is checked too"""
+        from . import neighbourhood as K
+
+        filters = K.check_typed(self, relation_types)
+        if filters is not None and seeds is not None:
+            K.spread_filters(filters, int(seeds.shape[0]) if hasattr(seeds, "shape") else len(seeds))
+        return filters
+
+    def _iterate(self, sd, wd, a: int, tol: int, max_iterations: int, filters=None) -> int:
+        """seeds one launch batch (<= 256 queries) and runs its steps in the workspace -> `cur`, as the next step would get it.
+        filters: None, or a device int32 [nq] of uint32 filters — the typed seed and step over the weighted typed adjacency"""
         t, lib, n, m = self.torch, self.lib, self.n, self.m
         nq, s = int(sd.shape[0]), int(sd.shape[1])
         need = int(lib.rarc_ppr_workspace_bytes(n, m, nq))
@@ -313,23 +324,34 @@ class EntityGraph:
             self._ws = t.empty(need, dtype=t.uint8, device=self.device)
         g, gb, ws, wb = self._graph.data_ptr(), self._graph.numel(), self._ws.data_ptr(), self._ws.numel()
         stream = t.cuda.current_stream(self.device).cuda_stream
-        B.check(lib.rarc_ppr_seed(g, gb, n, m, sd.data_ptr(), wd.data_ptr(), nq, s, ws, wb, stream), "rarc_ppr_seed")
+        if filters is not None:
+            from .neighbourhood import typed_adjacency
+
+            ta = typed_adjacency(self, weighted=True)
+            ty, tb, fd = ta.data_ptr(), ta.numel(), filters.data_ptr()
+            B.check(lib.rarc_ppr_seed_typed(g, gb, ty, tb, fd, n, m, sd.data_ptr(), wd.data_ptr(), nq, s, ws, wb, stream), "rarc_ppr_seed_typed")
+        else:
+            B.check(lib.rarc_ppr_seed(g, gb, n, m, sd.data_ptr(), wd.data_ptr(), nq, s, ws, wb, stream), "rarc_ppr_seed")
         done = t.zeros(nq, dtype=t.int32, device=self.device) if tol > 0 else None
         cur = 0
         for _ in range(max_iterations):
-            B.check(lib.rarc_ppr_step(g, gb, n, m, nq, a, tol, cur, ws, wb, done.data_ptr() if done is not None else None, stream),
-                    "rarc_ppr_step")
+            if filters is not None:
+                B.check(lib.rarc_ppr_step_typed(g, gb, ty, tb, fd, n, m, nq, a, tol, cur, ws, wb, done.data_ptr() if done is not None else None,
+                                                stream), "rarc_ppr_step_typed")
+            else:
+                B.check(lib.rarc_ppr_step(g, gb, n, m, nq, a, tol, cur, ws, wb, done.data_ptr() if done is not None else None, stream),
+                        "rarc_ppr_step")
             cur ^= 1
             if done is not None and bool(done.all().item()):        # B words per iteration, only under a tolerance
                 break
         return cur
 
-    def _run(self, sd, wd, a: int, tol: int, max_iterations: int, top_k, mentions=None):
+    def _run(self, sd, wd, a: int, tol: int, max_iterations: int, top_k, mentions=None, filters=None):
         """one launch batch (<= 256 queries) -> device tensors: scores [B][n], or (ids, scores, counts); with `mentions` (a
         MentionMap) the same over its chunks: the iterations are shared, only the tail differs"""
         t, lib, n, m = self.torch, self.lib, self.n, self.m
         nq = int(sd.shape[0])
-        cur = self._iterate(sd, wd, a, tol, max_iterations)
+        cur = self._iterate(sd, wd, a, tol, max_iterations, filters)
         if mentions is not None:
             return mentions.project(n, m, nq, cur, self._ws, top_k)
         ws, wb = self._ws.data_ptr(), self._ws.numel()
@@ -344,10 +366,17 @@ class EntityGraph:
         B.check(lib.rarc_ppr_topk(n, m, nq, top_k, cur, ws, wb, ids.data_ptr(), sc.data_ptr(), cnt.data_ptr(), stream), "rarc_ppr_topk")
         return ids, sc, cnt
 
-    def _ranked(self, sd, wd, a, tol, max_iterations, top_k, as_device, mentions=None):
+    def _ranked(self, sd, wd, a, tol, max_iterations, top_k, as_device, mentions=None, filters=None):
+        """cuts the queries at 256 per launch batch, and the host `filters` (None: untyped) with them"""
         t = self.torch
         more = {} if mentions is None else {"mentions": mentions}
-        parts = [self._run(sd[s0:s0 + MAX_BATCH], wd[s0:s0 + MAX_BATCH], a, tol, int(max_iterations), top_k, **more)
+        fd = None
+        if filters is not None:
+            from .neighbourhood import _device_filters
+
+            fd = _device_filters(self, filters, int(sd.shape[0]))
+        parts = [self._run(sd[s0:s0 + MAX_BATCH], wd[s0:s0 + MAX_BATCH], a, tol, int(max_iterations), top_k,
+                           **(more if fd is None else {**more, "filters": fd[s0:s0 + MAX_BATCH]}))
                  for s0 in range(0, int(sd.shape[0]), MAX_BATCH)]
         if top_k is None:
             out = parts[0] if len(parts) == 1 else t.cat(parts)
@@ -356,7 +385,7 @@ class EntityGraph:
         return out if as_device else tuple(x.cpu().numpy() for x in out)
 
     def personalized_pagerank(self, seeds, seed_weights=None, damping: float = 0.85, max_iterations: int = 20, tolerance: float = 0.0,
-                              top_k=None, as_device: bool = False):
+                              top_k=None, as_device: bool = False, relation_types=None):
         """Personalized PageRank from each query's seeds.
         seeds: a list of lists of vertices, or a device int64 [B][s] tensor padded with -1; at most 64 per query, a vertex may
         repeat.  seed_weights: per seed, floats >= 0 (each query scaled so its largest is 1, then round(w * 2^20)); unit by
@@ -364,24 +393,36 @@ class EntityGraph:
         tolerance: a query whose largest change in a step is <= tolerance stops there, on its own; 0 runs max_iterations steps.
         -> float64 [B][n] scores (p / 2^40, exact), or with top_k (ids int64 [B][k], scores float64 [B][k], counts int32 [B]):
         the vertices of positive score by (score descending, vertex ascending), (-1, -inf) past the count.
-        as_device=True leaves the results on the GPU.  ValueError for a negative or non-finite weight, a vertex outside [0, n)
-        or more than 64 seeds."""
+        relation_types (a graph built with types only): None — the untyped run, today's code path — or the
+        relation types each query may cross, as neighbourhood takes them: one iterable of type ids as one filter for every
+        query, a sequence of B iterables, or a uint32 array [B] of masks.  Query q then runs the same rule on the graph of the
+        edges whose mask shares a type with its filter, each at its full weight: its weighted degrees are those of that graph,
+        and a vertex without an allowed edge keeps its mass.  A pair's mask is the OR and its weight the sum over its
+        duplicates, so a pair that carries types {0, 1} is crossed at its whole weight under filter {0}: per-type weights are
+        not kept.  Row q equals the untyped call on the filtered pair list, bit for bit; an empty filter leaves p = t.
+        as_device=True leaves the results on the GPU.  ValueError for a negative or non-finite weight, a vertex outside [0, n),
+        more than 64 seeds, relation_types on a graph without masks, a type outside [0, 32) or a filter count other than 1 or B."""
         a, tol = self._check_run(damping, max_iterations, tolerance, top_k, self.n)
+        if relation_types is not None and not hasattr(seeds, "shape"):
+            seeds = list(seeds)
+        filters = self._typed_filters(relation_types, seeds)
         with self.torch.cuda.device(self.device):
             sd, wd = self._seed_tensors(seeds, seed_weights)
-            return self._ranked(sd, wd, a, tol, max_iterations, None if top_k is None else int(top_k), as_device)
+            return self._ranked(sd, wd, a, tol, max_iterations, None if top_k is None else int(top_k), as_device, filters=filters)
 
     def retrieve(self, index, queries, seeds_per_query: int = 5, top_k: int = 10, damping: float = 0.85, max_iterations: int = 20,
-                 tolerance: float = 0.0, as_device: bool = False):
+                 tolerance: float = 0.0, as_device: bool = False, relation_types=None):
         """Graph retrieval for embedded queries: row i of `index` (a FlatIndexF16) is the embedding of vertex i; each query's
         seeds are the index's own top-`seeds_per_query` (id, score) answer, the scores clipped at 0 as weights, taken on the
         device — the answer feeds rarc_ppr_seed directly, nothing leaves HBM between the search and the ranking.
+        relation_types: as personalized_pagerank takes it, one filter for every query or one per query.
         -> (ids, scores, counts) as personalized_pagerank(top_k=top_k)."""
         self._check_index(index, seeds_per_query)
         a, tol = self._check_run(damping, max_iterations, tolerance, top_k, self.n)
+        filters = self._typed_filters(relation_types)
         sd, wd = self._index_seeds(index, queries, seeds_per_query)
         with self.torch.cuda.device(self.device):
-            return self._ranked(sd, wd, a, tol, max_iterations, int(top_k), as_device)
+            return self._ranked(sd, wd, a, tol, max_iterations, int(top_k), as_device, filters=filters)
 
     def _check_index(self, index, seeds_per_query):
         if int(index.ntotal) != self.n:
@@ -417,26 +458,33 @@ class EntityGraph:
         return a, tol
 
     def rank_chunks(self, mentions, seeds, seed_weights=None, damping: float = 0.85, max_iterations: int = 20, tolerance: float = 0.0,
-                    top_k=None, as_device: bool = False):
+                    top_k=None, as_device: bool = False, relation_types=None):
         """personalized_pagerank, ending in chunks: the state of every query is pushed through `mentions` (a MentionMap over
         this graph's vertices), S(c) = (sum over c's mentions (e, w) of w * p(e)) >> 12, without leaving the device.
         -> float64 [B][n_chunks] scores (S / 2^28, exact), or with top_k (ids int64 [B][k], scores float64 [B][k], counts
         int32 [B]): the chunks of positive score by (score descending, chunk ascending), (-1, -inf) past the count — a chunk
-        without mentions is never returned.  Every other argument as personalized_pagerank."""
+        without mentions is never returned.  Every other argument as personalized_pagerank, relation_types included: the
+        projection reads the typed state as it reads the untyped one."""
         a, tol = self._check_chunks(mentions, damping, max_iterations, tolerance, top_k)
+        if relation_types is not None and not hasattr(seeds, "shape"):
+            seeds = list(seeds)
+        filters = self._typed_filters(relation_types, seeds)
         with self.torch.cuda.device(self.device):
             sd, wd = self._seed_tensors(seeds, seed_weights)
-            return self._ranked(sd, wd, a, tol, max_iterations, None if top_k is None else int(top_k), as_device, mentions=mentions)
+            return self._ranked(sd, wd, a, tol, max_iterations, None if top_k is None else int(top_k), as_device, mentions=mentions,
+                                filters=filters)
 
     def retrieve_chunks(self, index, queries, mentions, seeds_per_query: int = 5, top_k: int = 10, damping: float = 0.85,
-                        max_iterations: int = 20, tolerance: float = 0.0, as_device: bool = False):
+                        max_iterations: int = 20, tolerance: float = 0.0, as_device: bool = False, relation_types=None):
         """retrieve, ending in chunks: the seeds are the index's own top-`seeds_per_query` answer, the ranking is rank_chunks'.
+        relation_types: as personalized_pagerank takes it.
         -> (ids, scores, counts) as rank_chunks(top_k=top_k)."""
         self._check_index(index, seeds_per_query)
         a, tol = self._check_chunks(mentions, damping, max_iterations, tolerance, top_k)
+        filters = self._typed_filters(relation_types)
         sd, wd = self._index_seeds(index, queries, seeds_per_query)
         with self.torch.cuda.device(self.device):
-            return self._ranked(sd, wd, a, tol, max_iterations, int(top_k), as_device, mentions=mentions)
+            return self._ranked(sd, wd, a, tol, max_iterations, int(top_k), as_device, mentions=mentions, filters=filters)
 
     # ---------------------------------------------------------------------------------------------------------------- traversal
     def neighbourhood(self, seeds, hops: int = 2, max_vertices=None, as_device: bool = False, early_stop: bool = False, relation_types=None):
@@ -584,6 +632,13 @@ class EntityGraph:
         return C.same_component(self, a, b)
 
 
-def personalized_pagerank(n: int, pairs, seeds, weights=None, device: int = 0, **kw):
-    """The one-shot form: EntityGraph(n, pairs, weights, device).personalized_pagerank(seeds, **kw)."""
-    return EntityGraph(n, pairs, weights=weights, device=device).personalized_pagerank(seeds, **kw)
+def personalized_pagerank(n: int, pairs, seeds, weights=None, device: int = 0, types=None, **kw):
+    """The one-shot form: EntityGraph(n, pairs, weights, types, device).personalized_pagerank(seeds, **kw).  types: one relation
+    type per pair, as k_hop takes it; relation_types= needs it, and is checked before the graph is built: a bad filter raises
+    with no device visible."""
+    from .neighbourhood import _check_one_shot_types
+
+    if kw.get("relation_types") is not None and not hasattr(seeds, "shape"):
+        seeds = list(seeds)
+    _check_one_shot_types(types, kw, None if hasattr(seeds, "is_cuda") else len(seeds))
+    return EntityGraph(n, pairs, weights=weights, types=types, device=device).personalized_pagerank(seeds, **kw)

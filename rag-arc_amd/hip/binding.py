@@ -290,6 +290,12 @@ SIGNATURES = {
                                       c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rarc_khop_path_edges_typed": (c_int, [c_int64, c_int64, c_int, c_int, c_void_p, c_size_t, c_void_p, c_int64, c_void_p, c_int, c_void_p,
                                            c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_graph_types_weighted_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "rarc_graph_types_weighted": (c_int, [c_void_p, c_size_t, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "rarc_ppr_seed_typed": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int,
+                                    c_void_p, c_size_t, c_void_p]),
+    "rarc_ppr_step_typed": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_int64, c_int64, c_int, c_int, c_int64, c_int, c_void_p,
+                                    c_size_t, c_void_p, c_void_p]),
     "rarc_sort_reduce_workspace_bytes": (c_size_t, [c_int64]),
     "rarc_sort_reduce": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rarc_sort_reduce_limits": (c_int, [ctypes.POINTER(c_int)]),
