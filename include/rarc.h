@@ -1229,6 +1229,51 @@ int rarc_merge_relations(const int64_t* d_rel, int64_t r, const int64_t* d_new_i
                          int64_t* d_out_rel, int64_t* d_out_rows, int64_t* d_out3, void* stream);
 
 /*
+ * Graph ingest: what the reference's store_graph(documents) does per batch of documents (event_graphrag_neo4j.py: _store_mentions,
+ * _store_entity_relations, _create_chunk_entity_relations MERGE into what is there) — raw extraction rows, in any orientation, with
+ * duplicates, typed and weighted, become the unique sorted lists EntityGraph.from_device and MentionMap.from_device_csr adopt, and
+ * a resident list is extended by a batch, without the rows or the list crossing to the host.  The rule (restated by
+ * tests/ingest_ref.py) is in integers: the same bytes for any order of the rows and from run to run (csrc/merge.hip: one key per
+ * row, rarc_sort_reduce's sort and segmented sum, a writer).  Pointers aligned to their element, workspaces to 256 bytes, each
+ * *_workspace_bytes returning 0 for a refused shape; everything is refused before any launch; launches only — the caller reads the
+ * count words back.  0 <= base count, 0 <= r, 1 <= base count + r < 2^31 (rarc_sort_reduce's count limit); a side of length 0 may
+ * pass null pointers.
+ *
+ * rarc_ingest_pairs — d_rows int64 [r][2] in any orientation; d_row_weights uint32 [r] or null (1 each); d_row_types int32 [r] or
+ *   null.  The base: d_base_pairs int64 [m0][2], unique pairs i < j in ANY order (what an EntityGraph keeps), d_base_weights uint32
+ *   [m0] or null (1 each), d_base_masks uint32 [m0] or null.  2 <= n < 2^31 - 1 as rarc_graph_csr takes it.  Typed iff d_out_masks
+ *   is given: then every side present must carry its types / masks, else none may (RARC_E_INVALID).  A new row is skipped and
+ *   counted under the first that applies of {an end outside [0, n), a == b, weight 0, a type outside [0, 32)}; a base row outside
+ *   its contract (i >= j, out of range, weight 0) is skipped and counted apart.  Every other row gives its weight to the pair
+ *   (min, max) and its mask — 1 << type, a base row's whole mask — to the pair's mask: W = the 64-bit sum, mask = the OR.  Unit
+ *   mode, when neither side has weights: every W is 1.  d_out_pairs int64 [m0 + r][2] by (i, j) ascending; d_out_weights uint32
+ *   [m0 + r] (the low 32 bits of W; may be null in unit mode, else written as 1); d_out_masks uint32 [m0 + r] or null; d_out8 int64
+ *   [8] = {edges, largest W, total W, rows skipped out of range, as self-loops, for weight 0, for a bad type, base rows skipped}.
+ *   No slot at or past `edges` is written.  A largest W >= 2^32 or a total >= 2^31 is the caller's to refuse.
+ * rarc_ingest_mentions — d_rows int64 [r][2] of (chunk, entity); d_row_weights uint32 [r] or null (1 each).  The base: the CSR by
+ *   chunk of a mention map over base_chunks <= n_chunks chunks and nnz0 entries, as rarc_ppr_chunks takes it (ranges clamped to
+ *   [0, nnz0]; an entry with an entity outside [0, n_entities) or a weight outside [1, 2^12) skipped and counted apart).  1 <=
+ *   n_chunks < 2^31 - 1, 1 <= n_entities < 2^31 - 1.  A new row is skipped and counted under the first that applies of {a chunk
+ *   outside [0, n_chunks), an entity outside [0, n_entities), a weight outside [1, 2^12)}.  W(c, e) = the sum of the weights.  The
+ *   output is rarc_merge_mentions': d_out_row_ptr int64 [n_chunks + 1], d_out_ent int32 [nnz0 + r] (each row ascending, no
+ *   repeats), d_out_w uint32 [nnz0 + r], d_out_split int32 [n_chunks]: the chunks of more than 64 mentions, ascending; d_out8 int64
+ *   [8] = {mentions written, largest W, chunks in the split list, rows skipped for the chunk, for the entity, for the weight, 0,
+ *   base entries skipped}.  A largest W >= 2^12 is the caller's to refuse before it uses the result.
+ * rarc_ingest_limits — out4 = {relation types of a mask, bits of a mention weight, the split degree, log2 of the count limit}.
+ */
+size_t rarc_ingest_pairs_workspace_bytes(int64_t m0, int64_t r);
+int rarc_ingest_pairs(const int64_t* d_rows, const uint32_t* d_row_weights, const int32_t* d_row_types, int64_t r,
+                      const int64_t* d_base_pairs, const uint32_t* d_base_weights, const uint32_t* d_base_masks, int64_t m0, int64_t n,
+                      void* d_ws, size_t ws_bytes, int64_t* d_out_pairs, uint32_t* d_out_weights, uint32_t* d_out_masks, int64_t* d_out8,
+                      void* stream);
+size_t rarc_ingest_mentions_workspace_bytes(int64_t n_chunks, int64_t nnz0, int64_t r);
+int rarc_ingest_mentions(const int64_t* d_rows, const uint32_t* d_row_weights, int64_t r, const int64_t* d_base_row_ptr,
+                         const int32_t* d_base_ent, const uint32_t* d_base_w, int64_t base_chunks, int64_t nnz0, int64_t n_chunks,
+                         int64_t n_entities, void* d_ws, size_t ws_bytes, int64_t* d_out_row_ptr, int32_t* d_out_ent, uint32_t* d_out_w,
+                         int32_t* d_out_split, int64_t* d_out8, void* stream);
+int rarc_ingest_limits(int* out4);
+
+/*
  * Connected components: which vertices of the graph rarc_graph_csr built are joined at all, how many pieces it has and how large
  * they are — CALL gds.wcc.stream(graph) — next to the resident CSR.  The rule (restated by
  * tests/components_ref.py): a parent word p[v] per vertex, p[v] = v at first.  A round starts from a star forest and hooks — for

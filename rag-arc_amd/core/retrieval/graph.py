@@ -49,6 +49,7 @@ class HipGraphRetriever(BaseRetriever):
         self.max_iterations, self.tolerance = int(max_iterations), float(tolerance)
         self.expansion, self.hops, self.decay = expansion, int(hops), None
         self.relation_types = relation_types
+        self._cooccurrence = None                                                # from_arrays(pairs=None): the projection's arguments
         if expansion == "k_hop":                                                 # the refusals of expand_chunks, up front
             from ...encapsulation.database.graph_db.neighbourhood import check_decay, check_hops
 
@@ -118,7 +119,63 @@ class HipGraphRetriever(BaseRetriever):
         index = FlatIndexF16(int(x.shape[1]), metric=metric, device=device)
         index.add(x)
         docs = [Document(content=t, metadata=m, id=i) for t, m, i in zip(texts, metadatas, ids)]
-        return cls(embedding, index, graph, mention_map, docs, **kwargs)
+        self = cls(embedding, index, graph, mention_map, docs, **kwargs)
+        if pairs is None:                                                           # add_documents rebuilds the projection with these
+            self._cooccurrence = {"weight": cooccurrence_weight, "min_weight": min_weight, "max_mentions": max_mentions}
+        return self
+
+    # -- growth -----------------------------------------------------------------------------------------------------------
+    def add_documents(self, texts: Iterable[str], mentions, mention_weights=None, entity_embeddings=None, pairs=None, pair_weights=None,
+                      pair_types=None, ids: Optional[Iterable[str]] = None, metadatas: Optional[Iterable[Dict[str, Any]]] = None) -> List[str]:
+        """One more batch of documents, the way the reference's store_graph(documents) is called per batch.
+        texts (and ids, metadatas): the new chunks, numbered from len(self.docs); mentions / mention_weights: (chunk, entity)
+        links naming chunks by those ABSOLUTE numbers (a link from an old chunk to a new entity is allowed);
+        entity_embeddings: float32 [k][d] rows appended to the index, which become vertices graph.n .. graph.n + k - 1;
+        pairs / pair_weights / pair_types: relations that extend the graph (EntityGraph.extended).  A retriever built with
+        pairs=None rebuilds its co-occurrence projection from the extended map, with the arguments it was built with, and refuses
+        pairs= here.  The graph and the map are extended on the device (graph_db/ingest.py) into NEW objects; every check runs
+        before anything is changed, and the index, self.graph, self.mentions and self.docs are replaced together at the end: a
+        call that raises leaves the retriever answering as before.  -> the ids of the new documents."""
+        texts = [str(t) for t in texts]
+        if not texts:
+            raise ValueError("texts must not be empty")
+        if mentions is None:
+            raise ValueError("mentions must be given: the (chunk, entity) links of the new chunks")
+        metadatas = list(metadatas) if metadatas is not None else [{} for _ in texts]
+        ids = [str(i) for i in ids] if ids is not None else [str(uuid.uuid4()) for _ in texts]
+        if len(metadatas) != len(texts) or len(ids) != len(texts):
+            raise ValueError(f"{len(texts)} texts, {len(metadatas)} metadatas, {len(ids)} ids")
+        x = None
+        if entity_embeddings is not None:
+            x = np.ascontiguousarray(entity_embeddings, dtype=np.float32)
+            if x.ndim != 2 or x.shape[1] != self.index.dim:
+                raise ValueError(f"expected [k][{self.index.dim}] entity embeddings, got an array of shape {x.shape}")
+            if x.shape[0] == 0:
+                x = None
+        n = self.graph.n + (0 if x is None else int(x.shape[0]))
+        if self._cooccurrence is not None and (pairs is not None or pair_weights is not None or pair_types is not None):
+            raise ValueError("pairs with a co-occurrence graph: this retriever was built with pairs=None, its graph is the projection of "
+                             "the mention map and is rebuilt from the extended map")
+        if pairs is None and (pair_weights is not None or pair_types is not None):
+            raise ValueError("pair_weights or pair_types without pairs")
+        new_mentions = self.mentions.extended(mentions, weights=mention_weights, n_chunks=len(self.docs) + len(texts), n_entities=n)
+        if self._cooccurrence is not None:
+            from ...encapsulation.database.graph_db.cooccurrence import check_arguments
+
+            check_arguments(n, self._cooccurrence["weight"], self._cooccurrence["min_weight"], self._cooccurrence["max_mentions"])
+            new_graph = new_mentions.cooccurrence(**self._cooccurrence)
+        elif pairs is not None or n != self.graph.n:
+            rows = np.zeros((0, 2), np.int64) if pairs is None else pairs
+            types = pair_types if pairs is not None else (np.zeros(0, np.int64) if self.graph.typed else None)
+            new_graph = self.graph.extended(rows, weights=pair_weights, types=types, n=n)
+        else:
+            new_graph = self.graph
+        self._check_relation_types(self.expansion, new_graph, self.relation_types)
+        if x is not None:
+            self.index.add(x)
+        docs = self.docs + [Document(content=t, metadata=m, id=i) for t, m, i in zip(texts, metadatas, ids)]
+        self.graph, self.mentions, self.docs = new_graph, new_mentions, docs
+        return ids
 
     # -- queries ----------------------------------------------------------------------------------------------------------
     def _embed(self, texts: List[str]):

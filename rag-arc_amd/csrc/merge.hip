@@ -431,14 +431,19 @@ __global__ __launch_bounds__(256) void mg_mention_key_kernel(const int64_t* __re
     }
   }
 }
+// d_skip: a device word holding how many leading keys are left out (the ingest's placeholder key), or null for none
 __global__ __launch_bounds__(256) void mg_mention_unpack_kernel(const u64* __restrict__ keys, const u64* __restrict__ sums, int64_t cap,
-                                                                const int64_t* __restrict__ d_len, int lo_bits, int64_t n_chunks,
-                                                                int32_t* __restrict__ out_ent, uint32_t* __restrict__ out_w, uint32_t* deg) {
-  const int64_t len = mg_len(d_len, cap);
+                                                                const int64_t* __restrict__ d_len, const int64_t* __restrict__ d_skip, int lo_bits,
+                                                                int64_t n_chunks, int32_t* __restrict__ out_ent, uint32_t* __restrict__ out_w,
+                                                                uint32_t* deg) {
+  const int64_t skip = d_skip ? (*d_skip > 0 ? 1 : 0) : 0;
+  int64_t len = mg_len(d_len, cap);
+  len = len > cap - skip ? cap - skip : len;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < len; i += (int64_t)gridDim.x * 256) {
-    const int64_t c = (int64_t)(keys[i] >> lo_bits);
-    out_ent[i] = (int32_t)(keys[i] & ((1ull << lo_bits) - 1ull));
-    out_w[i] = (uint32_t)sums[i];
+    const u64 key = keys[i + skip];
+    const int64_t c = (int64_t)(key >> lo_bits);
+    out_ent[i] = (int32_t)(key & ((1ull << lo_bits) - 1ull));
+    out_w[i] = (uint32_t)sums[i + skip];
     if (c < n_chunks) atomicAdd(&deg[c], 1u);
   }
 }
@@ -483,6 +488,20 @@ static MgMapWs mg_map_carve(const void* base, int64_t cap, int64_t n_chunks) {
   w.sort = mg_sort_carve(b ? b + o : nullptr, cap);
   w.bytes = o + w.sort.bytes;
   return w;
+}
+
+// the reduced (chunk << lo_bits | entity) keys, ascending, become the CSR by chunk: entities and weights, the degrees (deg: zeroed by
+// the caller), row_ptr and the list of the chunks of more than MG_SPLIT_DEGREE mentions, whose length goes to *d_split_count
+static void mg_mention_rows(const u64* red_keys, const u64* red_sums, int64_t cap, const int64_t* d_len, const int64_t* d_skip, int lo_bits,
+                            int64_t n_chunks, uint32_t* deg, uint32_t* cflag, uint32_t* cpos, u64* cbsum, int64_t* d_out_row_ptr,
+                            int32_t* d_out_ent, uint32_t* d_out_w, int32_t* d_out_split, int64_t* d_split_count, hipStream_t s) {
+  const unsigned grid = lv_grid(cap, 256, 16384), cgrid = lv_grid(n_chunks, 256, 16384);
+  hipLaunchKernelGGL(mg_mention_unpack_kernel, dim3(grid), dim3(256), 0, s, red_keys, red_sums, cap, d_len, d_skip, lo_bits, n_chunks, d_out_ent,
+                     d_out_w, deg);
+  mg_scan<int64_t>(deg, n_chunks, cbsum, d_out_row_ptr, true, nullptr, s);
+  hipLaunchKernelGGL(mg_split_flag_kernel, dim3(cgrid), dim3(256), 0, s, (const uint32_t*)deg, n_chunks, cflag);
+  mg_scan<uint32_t>(cflag, n_chunks, cbsum, cpos, true, d_split_count, s);
+  hipLaunchKernelGGL(mg_split_write_kernel, dim3(cgrid), dim3(256), 0, s, (const uint32_t*)cflag, (const uint32_t*)cpos, n_chunks, d_out_split);
 }
 
 // ---- relations: map, flag, scan, stable write -------------------------------------------------------------------------------------
@@ -658,7 +677,7 @@ extern "C" int rarc_merge_mentions(const int64_t* d_row_ptr, const int32_t* d_en
   hipStream_t s = (hipStream_t)stream;
   int64_t* ctl = w.sort.ctl;
   const int lo_bits = mg_bits(n);                                      // key = chunk << bits(n) | entity: at most 31 + 31 bits
-  const unsigned grid = lv_grid(nnz, 256, 16384), cgrid = lv_grid(n_chunks, 256, 16384);
+  const unsigned grid = lv_grid(nnz, 256, 16384);
   RARC_HIP_CHECK(hipMemsetAsync(ctl, 0, MG_CTL_BYTES, s));
   RARC_HIP_CHECK(hipMemsetAsync(w.sort.flag, 0, (size_t)nnz * 4, s));             // (a slot no chunk's range covers carries nothing)
   RARC_HIP_CHECK(hipMemsetAsync(w.deg, 0, (size_t)n_chunks * 4, s));
@@ -668,12 +687,8 @@ extern "C" int rarc_merge_mentions(const int64_t* d_row_ptr, const int32_t* d_en
   hipLaunchKernelGGL(mg_compact_kernel, dim3(grid), dim3(256), 0, s, (const u64*)w.raw_keys, d_w, nnz, (const uint32_t*)w.sort.flag,
                      (const uint32_t*)w.sort.pos, w.keys, w.vals);
   mg_sort_reduce(w.keys, w.vals, nnz, &ctl[MG_C_LEN], lo_bits + mg_bits(n_chunks), w.sort, w.red_keys, w.red_sums, s);
-  hipLaunchKernelGGL(mg_mention_unpack_kernel, dim3(grid), dim3(256), 0, s, (const u64*)w.red_keys, (const u64*)w.red_sums, nnz,
-                     (const int64_t*)&ctl[MG_C_DISTINCT], lo_bits, n_chunks, d_out_ent, d_out_w, w.deg);
-  mg_scan<int64_t>(w.deg, n_chunks, w.cbsum, d_out_row_ptr, true, nullptr, s);
-  hipLaunchKernelGGL(mg_split_flag_kernel, dim3(cgrid), dim3(256), 0, s, (const uint32_t*)w.deg, n_chunks, w.cflag);
-  mg_scan<uint32_t>(w.cflag, n_chunks, w.cbsum, w.cpos, true, &ctl[MG_C_SPLIT], s);
-  hipLaunchKernelGGL(mg_split_write_kernel, dim3(cgrid), dim3(256), 0, s, (const uint32_t*)w.cflag, (const uint32_t*)w.cpos, n_chunks, d_out_split);
+  mg_mention_rows(w.red_keys, w.red_sums, nnz, &ctl[MG_C_DISTINCT], nullptr, lo_bits, n_chunks, w.deg, w.cflag, w.cpos, w.cbsum, d_out_row_ptr,
+                  d_out_ent, d_out_w, d_out_split, &ctl[MG_C_SPLIT], s);
   RARC_HIP_CHECK(hipGetLastError());
   RARC_HIP_CHECK(hipMemcpyAsync(d_out6, &ctl[MG_C_DISTINCT], 48, hipMemcpyDeviceToDevice, s));
   return RARC_OK;
@@ -706,5 +721,310 @@ extern "C" int rarc_merge_relations(const int64_t* d_rel, int64_t r, const int64
   RARC_HIP_CHECK(hipMemcpyAsync(d_out3, &w.ctl[MG_C_LEN], 8, hipMemcpyDeviceToDevice, s));
   RARC_HIP_CHECK(hipMemcpyAsync(d_out3 + 1, &w.ctl[MG_C_DROPPED], 8, hipMemcpyDeviceToDevice, s));
   RARC_HIP_CHECK(hipMemcpyAsync(d_out3 + 2, &w.ctl[MG_C_BAD], 8, hipMemcpyDeviceToDevice, s));
+  return RARC_OK;
+}
+
+// ---- graph ingest: raw extraction rows, and a resident list to extend, become the unique sorted lists ----------------
+// Every row — a base row or a new one — takes one slot of the sort.  A row the rule skips takes the key 0 with value 0 and mask 0:
+// for pairs key 0 is (0, 0), which no edge has, so the writer leaves that one key out; for mentions key 0 is (chunk 0, entity 0),
+// which a real mention may have — a skipped row adds 0 to its sum, and the key is left out only when its whole sum is 0 (a valid
+// weight is >= 1).  Key 0 sorts first, so "left out" is one word: the writers start at slot `skip`.  No compaction, no cursor.
+enum { IG_C_SKIP = 8, IG_C_KEPT = 9, IG_C_LARGEST = 10, IG_C_TOTAL = 11, IG_C_KIND0 = 12, IG_C_KIND1 = 13, IG_C_KIND2 = 14, IG_C_KIND3 = 15,
+       IG_C_BASE = 16, IG_C_ROWS = 17 };
+enum { IG_PAIRS = 0, IG_PAIRS_UNIT = 1, IG_MENTIONS = 2 };
+constexpr int IG_TYPES = 32;
+
+// slots [0, m0): the base rows (i < j, each once by contract; one outside it is counted as damaged); slots [m0, m0 + r): the new
+// rows.  vals == nullptr: unit mode, the sort counts 1 a row; masks == nullptr: untyped
+__global__ __launch_bounds__(256) void ig_pair_key_kernel(const int64_t* __restrict__ rows, const uint32_t* __restrict__ rw,
+                                                          const int32_t* __restrict__ rt, int64_t r, const int64_t* __restrict__ base,
+                                                          const uint32_t* __restrict__ bw, const uint32_t* __restrict__ bm, int64_t m0, int64_t n,
+                                                          int lo_bits, u64* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                          uint32_t* __restrict__ masks, int64_t* ctl) {
+  const int64_t cap = m0 + r;
+  const int64_t rounds = (cap + (int64_t)gridDim.x * 256 - 1) / ((int64_t)gridDim.x * 256);
+  for (int64_t k = 0; k < rounds; ++k) {                               // (every lane of a wave makes every round: mg_count shuffles)
+    const int64_t i = (k * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
+    const bool valid = i < cap, is_base = valid && i < m0, is_new = valid && !is_base;
+    int64_t a = -1, b = -1;
+    uint32_t w = 1u, mask = 0u;
+    int t = 0;
+    if (is_base) {
+      a = base[2 * i];
+      b = base[2 * i + 1];
+      if (bw) w = bw[i];
+      if (bm) mask = bm[i];
+    } else if (is_new) {
+      const int64_t e = i - m0;
+      a = rows[2 * e];
+      b = rows[2 * e + 1];
+      if (rw) w = rw[e];
+      if (rt) t = rt[e];
+      mask = (t >= 0 && t < IG_TYPES) ? 1u << t : 0u;
+    }
+    const bool in_range = a >= 0 && a < n && b >= 0 && b < n;
+    const bool damaged = is_base && !(in_range && a < b && w != 0u);
+    const bool k_range = is_new && !in_range;
+    const bool k_loop = is_new && in_range && a == b;
+    const bool k_weight = is_new && in_range && a != b && w == 0u;
+    const bool k_type = is_new && in_range && a != b && w != 0u && (t < 0 || t >= IG_TYPES);
+    const bool keep = valid && !damaged && !k_range && !k_loop && !k_weight && !k_type;
+    if (valid) {
+      keys[i] = keep ? ((u64)(a < b ? a : b) << lo_bits) | (u64)(a < b ? b : a) : 0ull;
+      if (vals) vals[i] = keep ? w : 0u;
+      if (masks) masks[i] = keep ? mask : 0u;
+    }
+    mg_count(k_range, 0, &ctl[IG_C_KIND0], nullptr);
+    mg_count(k_loop, 0, &ctl[IG_C_KIND1], nullptr);
+    mg_count(k_weight, 0, &ctl[IG_C_KIND2], nullptr);
+    mg_count(k_type, 0, &ctl[IG_C_KIND3], nullptr);
+    mg_count(damaged, 0, &ctl[IG_C_BASE], nullptr);
+    mg_count(keep, (u64)w, &ctl[IG_C_ROWS], &ctl[IG_C_TOTAL]);
+  }
+}
+
+// new (chunk, entity) rows into their slots (keys / vals point at the first of them); w == nullptr: 1 each
+__global__ __launch_bounds__(256) void ig_mention_key_kernel(const int64_t* __restrict__ rows, const uint32_t* __restrict__ rw, int64_t r,
+                                                             int64_t n_chunks, int64_t n_entities, int lo_bits, u64* __restrict__ keys,
+                                                             uint32_t* __restrict__ vals, int64_t* ctl) {
+  const int64_t rounds = (r + (int64_t)gridDim.x * 256 - 1) / ((int64_t)gridDim.x * 256);
+  for (int64_t k = 0; k < rounds; ++k) {
+    const int64_t i = (k * gridDim.x + blockIdx.x) * 256 + threadIdx.x;
+    const bool valid = i < r;
+    const int64_t c = valid ? rows[2 * i] : -1, e = valid ? rows[2 * i + 1] : -1;
+    const uint32_t w = valid && rw ? rw[i] : 1u;
+    const bool k_chunk = valid && (c < 0 || c >= n_chunks);
+    const bool k_entity = valid && !k_chunk && (e < 0 || e >= n_entities);
+    const bool k_weight = valid && !k_chunk && !k_entity && (w < 1u || w >= (1u << PPR_CHUNK_WEIGHT_BITS));
+    const bool keep = valid && !k_chunk && !k_entity && !k_weight;
+    if (valid) {
+      keys[i] = keep ? ((u64)c << lo_bits) | (u64)e : 0ull;
+      vals[i] = keep ? w : 0u;
+    }
+    mg_count(k_chunk, 0, &ctl[IG_C_KIND0], nullptr);
+    mg_count(k_entity, 0, &ctl[IG_C_KIND1], nullptr);
+    mg_count(k_weight, 0, &ctl[IG_C_KIND2], nullptr);
+  }
+}
+// the base CSR into slots [0, nnz0), a wave per chunk, its ranges clamped as rarc_ppr_chunks clamps them (the slots no range
+// covers were zeroed by the caller); an entry outside the rule is counted as damaged
+__global__ __launch_bounds__(256) void ig_mention_base_kernel(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ ent,
+                                                              const uint32_t* __restrict__ w, int64_t base_chunks, int64_t nnz0,
+                                                              int64_t n_entities, int lo_bits, u64* __restrict__ keys,
+                                                              uint32_t* __restrict__ vals, int64_t* ctl) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int64_t c = (int64_t)blockIdx.x * 4 + wave; c < base_chunks; c += (int64_t)gridDim.x * 4) {
+    int64_t r0 = row_ptr[c], r1 = row_ptr[c + 1];
+    r0 = r0 < 0 ? 0 : (r0 > nnz0 ? nnz0 : r0);
+    r1 = r1 < r0 ? r0 : (r1 > nnz0 ? nnz0 : r1);
+    for (int64_t i0 = r0; i0 < r1; i0 += 64) {                         // (i0 is wave-uniform)
+      const int64_t i = i0 + lane;
+      const bool valid = i < r1;
+      const int64_t e = valid ? (int64_t)ent[i] : -1;
+      const uint32_t x = valid ? w[i] : 0u;
+      const bool keep = valid && e >= 0 && e < n_entities && x >= 1u && x < (1u << PPR_CHUNK_WEIGHT_BITS);
+      if (valid) {
+        keys[i] = keep ? ((u64)c << lo_bits) | (u64)e : 0ull;
+        vals[i] = keep ? x : 0u;
+      }
+      mg_count(valid && !keep, 0, &ctl[IG_C_BASE], nullptr);
+    }
+  }
+}
+
+// one thread, after the sort: whether the first key is the placeholder, what is kept, and the unit mode's own largest and total
+__global__ void ig_finish_kernel(const u64* __restrict__ red_keys, const u64* __restrict__ red_sums, int64_t cap, int mode, int64_t* ctl) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  int64_t distinct = ctl[MG_C_DISTINCT];
+  distinct = distinct < 0 ? 0 : (distinct > cap ? cap : distinct);
+  const int64_t skip = distinct >= 1 && red_keys[0] == 0ull && (mode != IG_MENTIONS || red_sums[0] == 0ull) ? 1 : 0;
+  const int64_t kept = distinct - skip;
+  ctl[IG_C_SKIP] = skip;
+  ctl[IG_C_KEPT] = kept;
+  if (mode == IG_PAIRS_UNIT) {
+    ctl[IG_C_LARGEST] = kept ? 1 : 0;
+    ctl[IG_C_TOTAL] = kept;
+  } else {
+    ctl[IG_C_LARGEST] = ctl[MG_C_MAX];                                 // (the placeholder's sum is 0: it raises no maximum)
+  }
+}
+
+// out_w == nullptr: not asked for; unit: every W is 1; out_masks: cleared here for the kept edges, ORed into by ig_mask_kernel
+__global__ __launch_bounds__(256) void ig_pair_write_kernel(const u64* __restrict__ red_keys, const u64* __restrict__ red_sums, int64_t cap,
+                                                            const int64_t* __restrict__ ctl, int lo_bits, bool unit,
+                                                            int64_t* __restrict__ out_pairs, uint32_t* __restrict__ out_w,
+                                                            uint32_t* __restrict__ out_masks) {
+  const int64_t skip = ctl[IG_C_SKIP] > 0 ? 1 : 0;
+  int64_t kept = ctl[IG_C_KEPT];
+  kept = kept < 0 ? 0 : (kept > cap - skip ? cap - skip : kept);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < kept; i += (int64_t)gridDim.x * 256) {
+    const u64 key = red_keys[i + skip];
+    out_pairs[2 * i] = (int64_t)(key >> lo_bits);
+    out_pairs[2 * i + 1] = (int64_t)(key & ((1ull << lo_bits) - 1ull));
+    if (out_w) out_w[i] = unit ? 1u : (uint32_t)red_sums[i + skip];    // (the caller narrows: the largest sum is reported)
+    if (out_masks) out_masks[i] = 0u;
+  }
+}
+// every contributing row finds its pair among the kept keys (ascending: a binary search) and ORs its mask into that edge's word:
+// integer ORs commute, so the word is the same bits for any order of the rows
+__global__ __launch_bounds__(256) void ig_mask_kernel(const u64* __restrict__ raw_keys, const uint32_t* __restrict__ raw_masks, int64_t cap,
+                                                      const u64* __restrict__ red_keys, const int64_t* __restrict__ ctl, uint32_t* out_masks) {
+  const int64_t skip = ctl[IG_C_SKIP] > 0 ? 1 : 0;
+  int64_t kept = ctl[IG_C_KEPT];
+  kept = kept < 0 ? 0 : (kept > cap - skip ? cap - skip : kept);
+  const u64* sorted = red_keys + skip;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < cap; i += (int64_t)gridDim.x * 256) {
+    const uint32_t mask = raw_masks[i];
+    if (!mask) continue;
+    const u64 key = raw_keys[i];
+    int64_t lo = 0, hi = kept;                                         // the first slot whose key is >= key
+    while (lo < hi) {
+      const int64_t mid = lo + ((hi - lo) >> 1);
+      if (sorted[mid] < key) lo = mid + 1;
+      else hi = mid;
+    }
+    if (lo < kept && sorted[lo] == key) atomicOr(&out_masks[lo], mask);
+  }
+}
+
+struct IgWs {
+  u64* raw_keys;
+  uint32_t* raw_vals;
+  uint32_t* raw_masks;
+  u64* red_keys;
+  u64* red_sums;
+  uint32_t* deg;
+  uint32_t* cflag;
+  uint32_t* cpos;
+  u64* cbsum;
+  MgSortWs sort;
+  size_t bytes;
+};
+// n_chunks == 0: the pairs' workspace, without the per-chunk arrays
+static IgWs ig_carve(const void* base, int64_t cap, int64_t n_chunks) {
+  char* b = (char*)base;
+  size_t o = 0;
+  IgWs w;
+  auto take = [&](size_t bytes) { char* p = b + o; o += lv_align(bytes); return p; };
+  w.raw_keys = (u64*)take((size_t)cap * 8);
+  w.raw_vals = (uint32_t*)take((size_t)cap * 4);
+  w.raw_masks = (uint32_t*)take((size_t)cap * 4);
+  w.red_keys = (u64*)take((size_t)cap * 8);
+  w.red_sums = (u64*)take((size_t)cap * 8);
+  w.deg = (uint32_t*)take((size_t)n_chunks * 4);
+  w.cflag = (uint32_t*)take((size_t)n_chunks * 4);
+  w.cpos = (uint32_t*)take((size_t)(n_chunks + 1) * 4);
+  w.cbsum = (u64*)take((size_t)(mg_tiles(n_chunks) + 1) * 8);
+  w.sort = mg_sort_carve(b ? b + o : nullptr, cap);
+  w.bytes = o + w.sort.bytes;
+  return w;
+}
+static inline bool ig_counts_ok(int64_t base, int64_t r) { return base >= 0 && r >= 0 && base < MG_COUNT_LIMIT && r < MG_COUNT_LIMIT && mg_count_ok(base + r); }
+
+extern "C" int rarc_ingest_limits(int* out4) {
+  RARC_REQUIRE(out4, RARC_E_INVALID, "rarc_ingest_limits: null pointer");
+  out4[0] = IG_TYPES;
+  out4[1] = PPR_CHUNK_WEIGHT_BITS;
+  out4[2] = MG_SPLIT_DEGREE;
+  out4[3] = 31;                                                        // base + new rows < 2^31
+  return RARC_OK;
+}
+
+extern "C" size_t rarc_ingest_pairs_workspace_bytes(int64_t m0, int64_t r) {
+  if (!ig_counts_ok(m0, r)) return 0;
+  return ig_carve(nullptr, m0 + r, 0).bytes;
+}
+
+extern "C" int rarc_ingest_pairs(const int64_t* d_rows, const uint32_t* d_row_weights, const int32_t* d_row_types, int64_t r,
+                                 const int64_t* d_base_pairs, const uint32_t* d_base_weights, const uint32_t* d_base_masks, int64_t m0, int64_t n,
+                                 void* d_ws, size_t ws_bytes, int64_t* d_out_pairs, uint32_t* d_out_weights, uint32_t* d_out_masks,
+                                 int64_t* d_out8, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(ig_counts_ok(m0, r), RARC_E_INVALID, "rarc_ingest_pairs: m0=%lld base pairs and r=%lld rows out of range (1 <= m0 + r < 2^31)",
+               (long long)m0, (long long)r);
+  const bool typed = d_out_masks != nullptr, unit = !d_row_weights && !d_base_weights;
+  RARC_REQUIRE(d_ws && d_out_pairs && d_out8 && (r == 0 || d_rows) && (m0 == 0 || d_base_pairs) && (unit || d_out_weights), RARC_E_INVALID,
+               "rarc_ingest_pairs: null pointer");
+  RARC_REQUIRE(typed ? (r == 0 || d_row_types) && (m0 == 0 || d_base_masks) : !d_row_types && !d_base_masks, RARC_E_INVALID,
+               "rarc_ingest_pairs: typed and untyped inputs are mixed (d_out_masks asks for masks: then every side present carries types)");
+  RARC_REQUIRE(MG_ALIGNED(d_rows, 8) && MG_ALIGNED(d_row_weights, 4) && MG_ALIGNED(d_row_types, 4) && MG_ALIGNED(d_base_pairs, 8) &&
+                   MG_ALIGNED(d_base_weights, 4) && MG_ALIGNED(d_base_masks, 4) && MG_ALIGNED(d_out_pairs, 8) && MG_ALIGNED(d_out_weights, 4) &&
+                   MG_ALIGNED(d_out_masks, 4) && MG_ALIGNED(d_out8, 8),
+               RARC_E_INVALID, "rarc_ingest_pairs: an array is not aligned to its element (pairs, rows and the counts 8 bytes, every other 4)");
+  RARC_REQUIRE(n >= 2 && n < LV_N_LIMIT, RARC_E_INVALID, "rarc_ingest_pairs: n=%lld out of range (2 <= n < 2^31 - 1)", (long long)n);
+  RARC_REQUIRE(MG_ALIGNED(d_ws, 256), RARC_E_INVALID, "rarc_ingest_pairs: the workspace is not 256-byte aligned");
+  const int64_t cap = m0 + r;
+  const IgWs w = ig_carve(d_ws, cap, 0);
+  RARC_REQUIRE(ws_bytes >= w.bytes, RARC_E_WORKSPACE, "rarc_ingest_pairs: workspace of %zu bytes, %zu needed", ws_bytes, w.bytes);
+  hipStream_t s = (hipStream_t)stream;
+  int64_t* ctl = w.sort.ctl;
+  const int lo_bits = mg_bits(n);                                      // key = min << bits(n) | max: 2 bits(n) <= 62 bits
+  const unsigned grid = lv_grid(cap, 256, 16384);
+  RARC_HIP_CHECK(hipMemsetAsync(ctl, 0, MG_CTL_BYTES, s));
+  hipLaunchKernelGGL(ig_pair_key_kernel, dim3(grid), dim3(256), 0, s, d_rows, d_row_weights, d_row_types, r, d_base_pairs, d_base_weights,
+                     d_base_masks, m0, n, lo_bits, w.raw_keys, unit ? (uint32_t*)nullptr : w.raw_vals, typed ? w.raw_masks : (uint32_t*)nullptr, ctl);
+  mg_sort_reduce(w.raw_keys, unit ? (const uint32_t*)nullptr : w.raw_vals, cap, nullptr, 2 * lo_bits, w.sort, w.red_keys, w.red_sums, s);
+  hipLaunchKernelGGL(ig_finish_kernel, dim3(1), dim3(64), 0, s, (const u64*)w.red_keys, (const u64*)w.red_sums, cap, unit ? IG_PAIRS_UNIT : IG_PAIRS,
+                     ctl);
+  hipLaunchKernelGGL(ig_pair_write_kernel, dim3(grid), dim3(256), 0, s, (const u64*)w.red_keys, (const u64*)w.red_sums, cap, (const int64_t*)ctl,
+                     lo_bits, unit, d_out_pairs, d_out_weights, d_out_masks);
+  if (typed)
+    hipLaunchKernelGGL(ig_mask_kernel, dim3(grid), dim3(256), 0, s, (const u64*)w.raw_keys, (const uint32_t*)w.raw_masks, cap,
+                       (const u64*)w.red_keys, (const int64_t*)ctl, d_out_masks);
+  RARC_HIP_CHECK(hipGetLastError());
+  RARC_HIP_CHECK(hipMemcpyAsync(d_out8, &ctl[IG_C_KEPT], 64, hipMemcpyDeviceToDevice, s));
+  return RARC_OK;
+}
+
+extern "C" size_t rarc_ingest_mentions_workspace_bytes(int64_t n_chunks, int64_t nnz0, int64_t r) {
+  if (!ig_counts_ok(nnz0, r) || n_chunks < 1 || n_chunks >= PPR_CHUNK_N_LIMIT) return 0;
+  return ig_carve(nullptr, nnz0 + r, n_chunks).bytes;
+}
+
+extern "C" int rarc_ingest_mentions(const int64_t* d_rows, const uint32_t* d_row_weights, int64_t r, const int64_t* d_base_row_ptr,
+                                    const int32_t* d_base_ent, const uint32_t* d_base_w, int64_t base_chunks, int64_t nnz0, int64_t n_chunks,
+                                    int64_t n_entities, void* d_ws, size_t ws_bytes, int64_t* d_out_row_ptr, int32_t* d_out_ent, uint32_t* d_out_w,
+                                    int32_t* d_out_split, int64_t* d_out8, void* stream) {
+  RARC_RANGE();
+  RARC_REQUIRE(ig_counts_ok(nnz0, r), RARC_E_INVALID, "rarc_ingest_mentions: nnz0=%lld base mentions and r=%lld rows out of range (1 <= nnz0 + r < 2^31)",
+               (long long)nnz0, (long long)r);
+  RARC_REQUIRE(d_ws && d_out_row_ptr && d_out_ent && d_out_w && d_out_split && d_out8 && (r == 0 || d_rows) &&
+                   (nnz0 == 0 || (d_base_row_ptr && d_base_ent && d_base_w)),
+               RARC_E_INVALID, "rarc_ingest_mentions: null pointer");
+  RARC_REQUIRE(MG_ALIGNED(d_rows, 8) && MG_ALIGNED(d_row_weights, 4) && MG_ALIGNED(d_base_row_ptr, 8) && MG_ALIGNED(d_base_ent, 4) &&
+                   MG_ALIGNED(d_base_w, 4) && MG_ALIGNED(d_out_row_ptr, 8) && MG_ALIGNED(d_out_ent, 4) && MG_ALIGNED(d_out_w, 4) &&
+                   MG_ALIGNED(d_out_split, 4) && MG_ALIGNED(d_out8, 8),
+               RARC_E_INVALID, "rarc_ingest_mentions: an array is not aligned to its element (rows, row_ptr and the counts 8 bytes, every other 4)");
+  RARC_REQUIRE(mg_n_ok(n_entities), RARC_E_INVALID, "rarc_ingest_mentions: n_entities=%lld out of range (1 <= n_entities < 2^31 - 1)",
+               (long long)n_entities);
+  RARC_REQUIRE(n_chunks >= 1 && n_chunks < PPR_CHUNK_N_LIMIT, RARC_E_INVALID, "rarc_ingest_mentions: n_chunks=%lld out of range (1 <= n_chunks < 2^31 - 1)",
+               (long long)n_chunks);
+  RARC_REQUIRE(base_chunks >= (nnz0 ? 1 : 0) && base_chunks <= n_chunks, RARC_E_INVALID,
+               "rarc_ingest_mentions: base_chunks=%lld out of range (the base's chunks are the first of the n_chunks=%lld)", (long long)base_chunks,
+               (long long)n_chunks);
+  RARC_REQUIRE(MG_ALIGNED(d_ws, 256), RARC_E_INVALID, "rarc_ingest_mentions: the workspace is not 256-byte aligned");
+  const int64_t cap = nnz0 + r;
+  const IgWs w = ig_carve(d_ws, cap, n_chunks);
+  RARC_REQUIRE(ws_bytes >= w.bytes, RARC_E_WORKSPACE, "rarc_ingest_mentions: workspace of %zu bytes, %zu needed", ws_bytes, w.bytes);
+  hipStream_t s = (hipStream_t)stream;
+  int64_t* ctl = w.sort.ctl;
+  const int lo_bits = mg_bits(n_entities);                             // key = chunk << bits(n_entities) | entity: at most 31 + 31 bits
+  RARC_HIP_CHECK(hipMemsetAsync(ctl, 0, MG_CTL_BYTES, s));
+  RARC_HIP_CHECK(hipMemsetAsync(w.deg, 0, (size_t)n_chunks * 4, s));
+  if (nnz0) {
+    RARC_HIP_CHECK(hipMemsetAsync(w.raw_keys, 0, (size_t)nnz0 * 8, s));           // (a slot no chunk's range covers carries nothing)
+    RARC_HIP_CHECK(hipMemsetAsync(w.raw_vals, 0, (size_t)nnz0 * 4, s));
+    hipLaunchKernelGGL(ig_mention_base_kernel, dim3(lv_grid(base_chunks, 4, 16384)), dim3(256), 0, s, d_base_row_ptr, d_base_ent, d_base_w,
+                       base_chunks, nnz0, n_entities, lo_bits, w.raw_keys, w.raw_vals, ctl);
+  }
+  if (r)
+    hipLaunchKernelGGL(ig_mention_key_kernel, dim3(lv_grid(r, 256, 16384)), dim3(256), 0, s, d_rows, d_row_weights, r, n_chunks, n_entities, lo_bits,
+                       w.raw_keys + nnz0, w.raw_vals + nnz0, ctl);
+  mg_sort_reduce(w.raw_keys, w.raw_vals, cap, nullptr, lo_bits + mg_bits(n_chunks), w.sort, w.red_keys, w.red_sums, s);
+  hipLaunchKernelGGL(ig_finish_kernel, dim3(1), dim3(64), 0, s, (const u64*)w.red_keys, (const u64*)w.red_sums, cap, (int)IG_MENTIONS, ctl);
+  mg_mention_rows(w.red_keys, w.red_sums, cap, &ctl[IG_C_KEPT], &ctl[IG_C_SKIP], lo_bits, n_chunks, w.deg, w.cflag, w.cpos, w.cbsum, d_out_row_ptr,
+                  d_out_ent, d_out_w, d_out_split, &ctl[IG_C_TOTAL], s);
+  RARC_HIP_CHECK(hipGetLastError());
+  RARC_HIP_CHECK(hipMemcpyAsync(d_out8, &ctl[IG_C_KEPT], 64, hipMemcpyDeviceToDevice, s));
   return RARC_OK;
 }

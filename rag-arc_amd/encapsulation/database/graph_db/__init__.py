@@ -8,10 +8,13 @@ two of them are connected (neighbourhood.py); and the last step of the
 de-duplication, merging each cluster into one entity (Base_Neo4j.py:714-890), which contracts that graph where it lies
 (merge.py); and what gds.wcc answers about that graph, its connected components (components.py).  The graph database itself is
 out of scope.  Where nobody extracted relations, the graph itself is the co-occurrence projection of the mention links
-(cooccurrence.py)."""
+(cooccurrence.py).  What the reference's
+store_graph does per batch of documents — MERGE new mentions, entities and relations into what is there — is ingest.py: graphs and
+mention maps built from raw rows and extended on the device."""
 from .communities import entity_clusters, louvain_communities
 from .components import Components, connected_components
 from .cooccurrence import Cooccurrence, cooccurrence_graph, cooccurrence_pairs
+from . import ingest
 from .merge import MergedEntities, MergePlan, deduplicate_entities, merge_entities, merge_plan
 from .neighbourhood import RelationList, k_hop, k_hop_subgraph
 from .neighbourhood import all_shortest_paths as shortest_paths
@@ -22,4 +25,4 @@ from .similarity import knn_graph, similar_pairs
 __all__ = ["similar_pairs", "knn_graph", "louvain_communities", "entity_clusters", "EntityGraph", "personalized_pagerank", "MentionMap",
            "k_hop", "k_hop_subgraph", "shortest_paths", "RelationList", "merge_plan", "merge_entities", "deduplicate_entities", "MergePlan",
            "MergedEntities", "connected_components", "Components", "cooccurrence_pairs",
-           "cooccurrence_graph", "Cooccurrence"]
+           "cooccurrence_graph", "Cooccurrence", "ingest"]

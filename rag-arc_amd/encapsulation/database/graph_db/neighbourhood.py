@@ -435,6 +435,14 @@ class RelationList:
     def typed(self) -> bool:
         return getattr(self, "_types", None) is not None
 
+    def extended(self, rows, weights=None, types=None, n_entities=None):
+        """A NEW RelationList over n_entities >= self.n_entities entities: this table's rows, then `rows` — existing rows keep
+        their row numbers, so the caller's types and descriptions stay valid.  Concatenated on the device (graph_db/ingest.py).
+        ValueError when the rows carry weights or types and this list does not, or the reverse."""
+        from . import ingest
+
+        return ingest.relations_extended(self, rows, weights=weights, types=types, n_entities=n_entities)
+
 
 def check_relations(graph, relations, typed: bool = False):
     """ValueError for anything but None or a RelationList over the graph's vertices on the graph's device; typed: the call has

@@ -226,6 +226,29 @@ class EntityGraph:
         self._components = {}
         return self
 
+    @classmethod
+    def from_rows(cls, n: int, rows, weights=None, types=None, device: int = 0, on_invalid: str = "raise"):
+        """The graph of raw extraction rows, normalised on the device (graph_db/ingest.py): `rows` a host array-like
+        or an int64 device tensor [r][2], in any orientation, with duplicates; `weights` integers per row (host, or a device int32
+        tensor of uint32 bits), unit by default; `types` one relation type per row (host, or a device int32 tensor).  Nothing is
+        normalised on the host; the result equals EntityGraph(n, rows, weights, types) where that takes the rows.
+        A row with an end outside [0, n), a == b, weight 0 or a type outside [0, 32) is no edge: on_invalid="raise" raises
+        ValueError naming the kinds and counts, "skip" leaves such rows out and reports {kind: count} as `.skipped`.
+        Refused as the constructor refuses: no edge at all (ValueError); a summed edge weight >= 2^32, a total >= 2^31, or
+        2^31 rows and more (RarcUnsupported)."""
+        from . import ingest
+
+        return ingest.graph_from_rows(cls, n, rows, weights=weights, types=types, device=device, on_invalid=on_invalid)
+
+    def extended(self, rows, weights=None, types=None, n=None, on_invalid: str = "raise"):
+        """A NEW EntityGraph over n >= self.n vertices (default: as many): this graph's edges and `rows`, as from_rows takes them,
+        folded together on the device — equal to the constructor on this graph's rows followed by the new ones.  This graph is not
+        modified, so calls in flight on it are unaffected.  When only one side carries weights the other side's rows count 1
+        each.  ValueError, before any launch, for n < self.n, or when the graph carries types and the rows do not or the reverse."""
+        from . import ingest
+
+        return ingest.graph_from_rows(type(self), self.n if n is None else n, rows, weights=weights, types=types, on_invalid=on_invalid, base=self)
+
     # ---------------------------------------------------------------------------------------------------------------- arguments
     @staticmethod
     def _check_run(damping, max_iterations, tolerance, top_k, n):

@@ -143,6 +143,27 @@ class MentionMap:
         self._cws = None
         return self
 
+    @classmethod
+    def from_rows(cls, n_chunks: int, n_entities: int, rows, weights=None, device: int = 0, on_invalid: str = "raise"):
+        """The map of raw (chunk, entity) rows, built on the device (graph_db/ingest.py): `rows` a host array-like
+        or an int64 device tensor [r][2], `weights` integers per row (host, or a device int32 tensor of uint32 bits), 1 by
+        default.  Equal to MentionMap(n_chunks, n_entities, rows, weights) where that takes the rows.  A row with a chunk outside
+        [0, n_chunks), an entity outside [0, n_entities) or a weight outside [1, 2^12) is no mention: on_invalid="raise" raises
+        ValueError naming the kinds and counts, "skip" leaves such rows out and reports {kind: count} as `.skipped`.
+        ValueError for no mention at all, RarcUnsupported for a summed weight >= 2^12."""
+        from . import ingest
+
+        return ingest.mentions_from_rows(cls, n_chunks, n_entities, rows, weights=weights, device=device, on_invalid=on_invalid)
+
+    def extended(self, rows, weights=None, n_chunks=None, n_entities=None, on_invalid: str = "raise"):
+        """A NEW MentionMap over n_chunks >= self.n_chunks chunks and n_entities >= self.n_entities entities (default: as many):
+        this map's mentions and `rows`, as from_rows takes them, folded together on the device.  This map is not modified."""
+        from . import ingest
+
+        return ingest.mentions_from_rows(type(self), self.n_chunks if n_chunks is None else n_chunks,
+                                         self.n_entities if n_entities is None else n_entities, rows, weights=weights, on_invalid=on_invalid,
+                                         base=self)
+
     def cooccurrence_pairs(self, weight: str = "count", min_weight: int = 1, max_mentions: int = 64, as_device: bool = False):
         """The edges of the co-occurrence projection (graph_db/cooccurrence.py): two entities are joined when a chunk
         mentions both, W(a, b) = the chunks that do (weight="count") or the sum of w_a * w_b over them (weight="product"); a chunk

@@ -296,6 +296,13 @@ SIGNATURES = {
                                     c_void_p, c_size_t, c_void_p]),
     "rarc_ppr_step_typed": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_int64, c_int64, c_int, c_int, c_int64, c_int, c_void_p,
                                     c_size_t, c_void_p, c_void_p]),
+    "rarc_ingest_pairs_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "rarc_ingest_pairs": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_size_t,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_ingest_mentions_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "rarc_ingest_mentions": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                     c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rarc_ingest_limits": (c_int, [ctypes.POINTER(c_int)]),
     "rarc_sort_reduce_workspace_bytes": (c_size_t, [c_int64]),
     "rarc_sort_reduce": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "rarc_sort_reduce_limits": (c_int, [ctypes.POINTER(c_int)]),
