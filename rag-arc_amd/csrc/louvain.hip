@@ -538,6 +538,10 @@ __global__ void lv_counts_kernel(const int64_t* newid, int64_t n, const int64_t*
   out[0] = newid[n];
   out[1] = scal[LV_S_EDGES];
 }
+// the start of the atomicMin below: above every vertex index (n0 < 2^31 - 1), which no byte fill can say
+__global__ __launch_bounds__(256) void lv_int_max_kernel(int64_t n0, int* minv) {
+  for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n0; v += (int64_t)gridDim.x * 256) minv[v] = INT_MAX;
+}
 __global__ __launch_bounds__(256) void lv_min_kernel(int64_t n0, const int64_t* __restrict__ labels, int* minv) {
   for (int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x; v < n0; v += (int64_t)gridDim.x * 256) {
     const int64_t x = labels[v];
@@ -721,7 +725,7 @@ extern "C" int rarc_louvain_labels(int64_t* d_labels, int64_t n0, void* d_ws, si
   RARC_REQUIRE(ws_bytes >= lv_align((size_t)n0 * 4), RARC_E_WORKSPACE, "rarc_louvain_labels: workspace of %zu bytes, %zu needed", ws_bytes,
                lv_align((size_t)n0 * 4));
   hipStream_t s = (hipStream_t)stream;
-  RARC_HIP_CHECK(hipMemsetAsync(d_ws, 0x7f, (size_t)n0 * 4, s));
+  hipLaunchKernelGGL(lv_int_max_kernel, dim3(lv_grid(n0, 256, 2048)), dim3(256), 0, s, n0, (int*)d_ws);
   hipLaunchKernelGGL(lv_min_kernel, dim3(lv_grid(n0, 256, 2048)), dim3(256), 0, s, n0, (const int64_t*)d_labels, (int*)d_ws);
   hipLaunchKernelGGL(lv_relabel_kernel, dim3(lv_grid(n0, 256, 2048)), dim3(256), 0, s, n0, d_labels, (const int*)d_ws);
   RARC_HIP_CHECK(hipGetLastError());

@@ -1,5 +1,6 @@
 """The Louvain rule of DESIGN §4.13c restated in plain Python integers: the normative definition csrc/louvain.hip must agree with
-label for label (tests/test_gpu_louvain.py), and the host checks of the rule itself (tests/test_louvain_ref_host.py).
+label for label (tests/test_gpu_louvain.py) and step for step (tests/test_gpu_louvain_steps.py), and the host checks of the rule
+itself (tests/test_louvain_ref_host.py).
 
 One input, one answer: n vertices, m unique undirected edges (i, j) with i < j, each of weight 1 -> labels[v] = the smallest
 original vertex of v's community.  Nothing depends on the order of the edge list.  Python integers do not overflow; the kernels
@@ -160,6 +161,128 @@ def louvain(n: int, edges, max_iterations: int = 10, max_levels: int = 10, trace
     for v, c in enumerate(labels):
         first.setdefault(c, v)
     return [first[c] for c in labels]
+
+
+def build(n: int, edges, weights=None, loops=None):
+    """One level's graph from its lists -> (adj, loops, k, m2): unique pairs 0 <= i < j < n, a weight per pair (1 where None),
+    a loop weight per vertex (0 where None)."""
+    adj: List[Dict[int, int]] = [dict() for _ in range(n)]
+    for e, (a, b) in enumerate(edges):
+        a, b = int(a), int(b)
+        assert 0 <= a < b < n and b not in adj[a], (a, b)
+        adj[a][b] = adj[b][a] = 1 if weights is None else int(weights[e])
+    lp = [0] * n if loops is None else [int(x) for x in loops]
+    assert len(lp) == n
+    k = [sum(adj[v].values()) + 2 * lp[v] for v in range(n)]
+    return adj, lp, k, sum(k)
+
+
+def degree_classes(adj, limits) -> List[List[int]]:
+    """The vertices by number of neighbours: class b holds those with limits[b - 1] < deg <= limits[b] (limits ascending, one
+    class more than limits: the last is unbounded), each ascending.  A vertex without a neighbour is in none."""
+    out: List[List[int]] = [[] for _ in range(len(limits) + 1)]
+    for v, row in enumerate(adj):
+        if row:
+            out[sum(len(row) > lim for lim in limits)].append(v)
+    return out
+
+
+# ---- numpy forms, for inputs of a million edges: each is held to the Python integers above in tests/test_louvain_ref_host.py ----
+def arrays_of(adj):
+    """The adjacency as int64 arrays (src, dst, w): every edge from both ends, by (src, dst) ascending."""
+    import numpy as np
+
+    src = [v for v, row in enumerate(adj) for _ in row]
+    dst = [u for row in adj for u in sorted(row)]
+    w = [row[u] for row in adj for u in sorted(row)]
+    return np.asarray(src, np.int64), np.asarray(dst, np.int64), np.asarray(w, np.int64)
+
+
+def csr_np(n: int, pairs, weights=None, loops=None):
+    """`build` in numpy -> dict: row_ptr [n + 1], (src, dst, w) by (src, dst) ascending, k, loop, m2 (a Python integer)"""
+    import numpy as np
+
+    p = np.asarray(pairs, np.int64).reshape(-1, 2)
+    assert ((0 <= p[:, 0]) & (p[:, 0] < p[:, 1]) & (p[:, 1] < n)).all()
+    key = p[:, 0] * n + p[:, 1]
+    assert len(np.unique(key)) == len(key)
+    wt = np.ones(len(p), np.int64) if weights is None else np.asarray(weights, np.int64)
+    lp = np.zeros(n, np.int64) if loops is None else np.asarray(loops, np.int64)
+    src, dst, w = np.concatenate([p[:, 0], p[:, 1]]), np.concatenate([p[:, 1], p[:, 0]]), np.concatenate([wt, wt])
+    order = np.lexsort((dst, src))
+    src, dst, w = src[order], dst[order], w[order]
+    row_ptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(src, minlength=n), out=row_ptr[1:])
+    k = np.zeros(n, np.int64)
+    np.add.at(k, src, w)
+    k += 2 * lp
+    return {"row_ptr": row_ptr, "src": src, "dst": dst, "w": w, "k": k, "loop": lp, "m2": int(k.sum())}
+
+
+def quality_np(src, dst, w, loops, k, m2: int, comm) -> int:
+    """`quality` over the arrays of `arrays_of` / `csr_np`; every sum stays below 2^63 for m < 2^30 and is taken in int64"""
+    import numpy as np
+
+    comm = np.asarray(comm, np.int64)
+    tot = np.zeros(len(comm), np.int64)
+    np.add.at(tot, comm, np.asarray(k, np.int64))
+    inside = int(w[comm[src] == comm[dst]].sum()) + 2 * int(np.asarray(loops, np.int64).sum())
+    return int(m2) * inside - int((tot * tot).sum())
+
+
+def sweep_np(src, dst, w, k, m2: int, comm, t: int):
+    """`sweep` over the arrays: (new labels, moved, targets)"""
+    import numpy as np
+
+    comm, k = np.asarray(comm, np.int64), np.asarray(k, np.int64)
+    n = len(comm)
+    tot = np.zeros(n, np.int64)
+    np.add.at(tot, comm, k)
+    size = np.bincount(comm, minlength=n)
+    mover = ((((np.arange(n, dtype=np.uint64) * np.uint64(HASH)) & np.uint64(0xFFFFFFFF)) >> np.uint64(16 + t % 16)) & np.uint64(1)) == 0
+    sel = mover[src]
+    key, inv = np.unique(src[sel] * n + comm[dst[sel]], return_inverse=True)      # one entry per (mover, neighbouring label)
+    w_c = np.zeros(len(key), np.int64)
+    np.add.at(w_c, inv.ravel(), w[sel])
+    v, c = key // n, key % n
+    a = comm[v]
+    w_a = np.zeros(n, np.int64)
+    w_a[v[c == a]] = w_c[c == a]
+    g = int(m2) * (w_c - w_a[v]) - k[v] * (tot[c] - (tot[a] - k[v]))
+    cand = (c != a) & (g > 0)
+    v, c, g = v[cand], c[cand], g[cand]
+    order = np.lexsort((c, -g, v))                                               # per mover: the largest G, then the smallest label
+    v, c = v[order], c[order]
+    first = np.ones(len(v), bool)
+    first[1:] = v[1:] != v[:-1]
+    v, c = v[first], c[first]
+    go = ~((size[comm[v]] == 1) & (size[c] == 1) & (c > comm[v]))
+    new = comm.copy()
+    new[v[go]] = c[go]
+    return new, int(go.sum()), len(v)
+
+
+def aggregate_np(src, dst, w, loops, comm):
+    """`aggregate` over the arrays -> (n_c, the pairs (a, b, weight) with a < b by (a, b) ascending, new loops, ids [n]: label ->
+    new vertex, -1 for a label without members)"""
+    import numpy as np
+
+    comm = np.asarray(comm, np.int64)
+    n = len(comm)
+    used = np.bincount(comm, minlength=n) > 0
+    ids = np.where(used, np.cumsum(used) - 1, -1)
+    n_c = int(used.sum())
+    once = src < dst
+    a, b, ww = ids[comm[src[once]]], ids[comm[dst[once]]], w[once]
+    nloops = np.zeros(n_c, np.int64)
+    np.add.at(nloops, ids[comm], np.asarray(loops, np.int64))
+    np.add.at(nloops, a[a == b], ww[a == b])
+    out = a != b
+    lo, hi = np.minimum(a[out], b[out]), np.maximum(a[out], b[out])
+    key, inv = np.unique(lo * n_c + hi, return_inverse=True)
+    pw = np.zeros(len(key), np.int64)
+    np.add.at(pw, inv.ravel(), ww[out])
+    return n_c, (key // n_c, key % n_c, pw), nloops, ids
 
 
 def levels_run(trace: list) -> int:

@@ -82,6 +82,69 @@ def test_limits_on_sweeps_and_levels():
         R.normalise(3, [(0, 3)])
 
 
+def weighted_graph(n: int, m: int, seed: int):
+    """m unique random pairs on n vertices, weights from {1, 1, 2, 3, 7, 1000}, a loop of 1..5 on every third vertex"""
+    rng = random.Random(seed)
+    pairs = set()
+    while len(pairs) < m:
+        a, b = rng.randrange(n), rng.randrange(n)
+        if a != b:
+            pairs.add((min(a, b), max(a, b)))
+    pairs = sorted(pairs)
+    rng.shuffle(pairs)
+    return n, pairs, [rng.choice([1, 1, 2, 3, 7, 1000]) for _ in pairs], [rng.randrange(1, 6) if v % 3 == 0 else 0 for v in range(n)]
+
+
+NP_INPUTS = {
+    "ring": lambda: R.ring_of_cliques(30, 5) + (None, None),
+    "grid": lambda: R.grid_graph(12, 9) + (None, None),
+    "k30-30": lambda: R.complete_bipartite(30, 30) + (None, None),
+    "edge": lambda: (2, [(0, 1)], [(1 << 30) - 1], None),
+    "weighted": lambda: weighted_graph(300, 1500, 4),
+    "weighted-sparse": lambda: weighted_graph(500, 260, 5),          # isolated vertices
+}
+
+
+def test_build_and_degree_classes():
+    adj, loops, k, m2 = R.build(5, [(0, 1), (1, 3), (0, 3)], [2, 5, 7], [0, 1, 0, 0, 4])
+    assert adj == [{1: 2, 3: 7}, {0: 2, 3: 5}, {}, {1: 5, 0: 7}, {}]
+    assert loops == [0, 1, 0, 0, 4] and k == [9, 9, 0, 12, 8] and m2 == 38
+    assert R.build(3, [(0, 2)]) == ([{2: 1}, {}, {0: 1}], [0, 0, 0], [1, 0, 1], 2)
+    n, edges = R.star_and_triangles(9, 2)
+    star = R.build(n, edges)[0]
+    assert R.degree_classes(star, [1, 2, 8]) == [list(range(1, 10)), list(range(10, 16)), [], [0]]
+    assert R.degree_classes(star, [2, 9]) == [list(range(1, 16)), [0], []]
+    assert R.degree_classes([{}, {0: 1}], [8]) == [[1], []]
+
+
+@pytest.mark.parametrize("name", list(NP_INPUTS))
+def test_the_numpy_forms_equal_the_python_integers(name):
+    """csr_np, quality_np, sweep_np and aggregate_np against build, quality, sweep and aggregate: after init, after every one of
+    eight kept sweeps (kept whether Qn rose or not), and for a sweep index beyond 15."""
+    import numpy as np
+
+    n, edges, weights, loops = NP_INPUTS[name]()
+    adj, lp, k, m2 = R.build(n, edges, weights, loops)
+    c = R.csr_np(n, edges, weights, loops)
+    src, dst, w = R.arrays_of(adj)
+    assert np.array_equal(c["src"], src) and np.array_equal(c["dst"], dst) and np.array_equal(c["w"], w)
+    assert c["k"].tolist() == k and c["loop"].tolist() == lp and c["m2"] == m2
+    assert c["row_ptr"].tolist() == [0] + np.cumsum([len(r) for r in adj]).tolist()
+    comm = list(range(n))
+    for t in list(range(8)) + [1 << 20]:
+        assert R.quality_np(src, dst, w, lp, k, m2, comm) == R.quality(adj, lp, k, m2, comm)
+        n_c, (pa, pb, pw), nloops, ids = R.aggregate_np(src, dst, w, lp, comm)
+        nadj, want_loops, want_ids = R.aggregate(adj, lp, comm)
+        assert n_c == len(nadj) and nloops.tolist() == want_loops
+        assert {c_: int(ids[c_]) for c_ in set(comm)} == want_ids and (ids >= 0).sum() == n_c
+        assert {(int(a), int(b)): int(x) for a, b, x in zip(pa, pb, pw)} == {(a, b): x for a in range(n_c) for b, x in nadj[a].items() if a < b}
+        assert len(pa) == sum(len(r) for r in nadj) // 2
+        new, moved, targets = R.sweep_np(src, dst, w, k, m2, comm, t)
+        assert (new.tolist(), moved, targets) == R.sweep(adj, lp, k, m2, comm, t)
+        comm = new.tolist()
+    assert name in ("k30-30", "edge") or len(set(comm)) < n
+
+
 def _nx_inputs(nx):
     return {
         "ring": nx.ring_of_cliques(30, 5),
