@@ -1,5 +1,5 @@
 """The oracle, the comparison and the seeded inputs of the knn_graph tests (tests/test_knn_ref_host.py on the CPU,
-tests/test_gpu_knn_graph.py on the GPU).  Plain numpy.
+tests/test_gpu_knn_graph.py and tests/test_gpu_self_join_lists.py on the GPU).  Plain numpy.
 
 The arithmetic is the one oracle/cpu_ref.py: similar_pairs_f64 restates from scikit-learn's cosine_similarity (the function the
 reference calls for its other self-join): rows divided by their float64 norms, zero rows left alone, then xn @ xn.T.  A kNN graph
@@ -196,6 +196,97 @@ def identical_copies(seed=41, n=1000, d=48, copies=40):
     at = np.sort(rng.choice(n, copies, replace=False))
     x[at] = x[at[0]]
     return x, at
+
+
+# ---- long nomination lists (tests/test_gpu_self_join_lists.py; proven on the CPU in tests/test_knn_ref_host.py) ---------------
+
+def pairs_eps(d_pad):
+    """csrc/pairs_common.h: pairs_eps — the bound on |approximate - exact| cosine both self-joins prune with."""
+    return 2.0 ** -10 + d_pad * 2.0 ** -23 + 1e-6
+
+
+def d_pad_of(d):
+    """csrc/pairs_common.h: pairs_d_pad."""
+    return max(256, (d + 63) // 64 * 64)
+
+
+LONG_PAIRS_SEED, LONG_PAIRS_N, LONG_PAIRS_THR = 71, 2973, 0.2   # n: the smallest with 256 long columns (the host test counts them)
+LONG_PAIRS_OVER = 1024 + 64                        # a column is "long" with more true pairs than one 1024-entry block and a margin
+
+
+def long_pair_lists(n=LONG_PAIRS_N, seed=LONG_PAIRS_SEED, lead=0):
+    """n Gaussian rows in 3 dimensions: about 40 % of all pairs reach cosine 0.2, so column j holds ~0.4 j true pairs and more
+    nominees — similar_pairs walks the lists of the last columns in several blocks of 1024.  `lead` zero rows are put in
+    FRONT: a zero row pairs with nothing, so the answer is the same pairs shifted by `lead` (Gaussian rows there would add
+    ~0.4 (lead n + lead^2 / 2) pairs: 8 million at lead = 4097), while the long columns lie in a later super-block."""
+    x = np.random.default_rng(seed).standard_normal((n, 3)).astype(np.float32)
+    return np.concatenate([np.zeros((lead, 3), np.float32), x]) if lead else x
+
+
+def pairs_from_sim(sim, threshold):
+    """(pairs int64 [m][2] ordered by (i, j), cosines float64 [m]): the i < j with sim >= threshold — oracle/cpu_ref.py:
+    similar_pairs_f64's loop in one numpy call (its 1.8 M appends take seconds)."""
+    i, j = np.nonzero(np.triu(sim >= threshold, 1))
+    return np.stack([i, j], axis=1).astype(np.int64), sim[i, j]
+
+
+TIGHT_SIGMA = 2.5e-3
+# (seed, m): one cluster past the finalize's 1024-entry buffer, one past the tighten's 4096 LDS keys
+TIGHT_SMALL, TIGHT_LARGE = (101, 1100), (107, 4300)
+TIGHT_D, TIGHT_BACKGROUND = 16, 700
+# top_k per input: 10 (the reference's), 256 (the limit); 1 on the large input for the probe row
+TIGHT_TOP_KS = {TIGHT_SMALL: (10, 256), TIGHT_LARGE: (1, 10, 256)}
+TIGHT_PROBE = 0.995                # the large input's probe row (tight_cluster)
+
+
+def tight_cluster(seed, m, d=TIGHT_D, background=TIGHT_BACKGROUND, sigma=TIGHT_SIGMA, zero_rows=0, group=0, probe=0.0):
+    """m rows = one unit vector + sigma x Gaussian noise, each scaled by a factor in [0.2, 5], and `background` Gaussian rows,
+    the cluster's indices shuffled through the whole range: a cluster column's nearest neighbours arrive in every chunk of rows
+    and in every round of the finalize.  sigma is small enough that every cluster row stays nominated in every cluster column
+    (the host test proves it from the oracle), and the noise decides the order: no ties.
+    Then, on background rows picked at random: zero_rows of them are zeroed; `group` are overwritten with scaled noisy copies of
+    one more (each of the group + 1 has `group` neighbours near cosine 0.99 and hardly another above 0.85); with probe = p one
+    becomes a unit row at cosine p to the cluster's centre — for p near 0.99 the whole cluster lies within a few 1e-4 of ITS
+    best neighbour, far under its own score of 1: the column whose list is long while its own row must stay out of a_K.
+    Returns (x, cluster indices ascending, {"zeroed": indices, "group": indices, "probe": index or -1})."""
+    rng = np.random.default_rng(seed)
+    centre = rng.standard_normal(d)
+    centre /= np.linalg.norm(centre)
+    rows = (centre[None, :] + sigma * rng.standard_normal((m, d))) * rng.uniform(0.2, 5.0, (m, 1))
+    n = m + background
+    perm = rng.permutation(n)
+    at, rest = np.sort(perm[:m]), np.sort(perm[m:])
+    x = np.empty((n, d), np.float32)
+    x[at] = rows.astype(np.float32)
+    x[rest] = rng.standard_normal((background, d)).astype(np.float32)
+    n_grp = group + 1 if group else 0
+    picked = rng.choice(rest, zero_rows + n_grp + 1, replace=False)
+    zeroed, grp, at_probe = np.sort(picked[:zero_rows]), np.sort(picked[zero_rows:zero_rows + n_grp]), int(picked[-1])
+    x[zeroed] = 0.0
+    if group:
+        x[grp[1:]] = x[grp[0]] * rng.uniform(0.5, 2.0, (group, 1)).astype(np.float32) + 0.05 * rng.standard_normal((group, d)).astype(np.float32)
+    if probe:
+        side = rng.standard_normal(d)
+        side -= side.dot(centre) * centre
+        x[at_probe] = (probe * centre + np.sqrt(1.0 - probe * probe) * side / np.linalg.norm(side)).astype(np.float32)
+    return x, at, {"zeroed": zeroed, "group": grp, "probe": at_probe if probe else -1}
+
+
+def cluster_cosines(sim, at):
+    """The float64 cosines of the cluster's pairs i < j."""
+    sub = sim[np.ix_(at, at)]
+    return sub[np.triu_indices(len(at), 1)]
+
+
+def tight_cutoffs(sim, at):
+    """The cutoffs of the tight-cluster cases: none, the reference's 0.85 (every cluster pair passes, hardly any other)
+    and the median in-cluster cosine (half of the cluster's pairs pass: counts differ by row)."""
+    return (-1.0, 0.85, float(np.median(cluster_cosines(sim, at))))
+
+
+def many_identical_copies(seed=109, n=1500, d=8, copies=1300):
+    """`copies` bit-identical rows among n Gaussian ones: more than one finalize buffer.  Returns (x, the copies' indices)."""
+    return identical_copies(seed, n, d, copies)
 
 
 def one_dimension(seed=43, n=60):

@@ -120,3 +120,107 @@ def test_tie_inputs_are_ties():
     x, at = R.identical_copies()
     assert len(at) == 40 and all(np.array_equal(x[a], x[at[0]]) for a in at)
     assert R.band_rows(R.cosine_matrix_f64(R.one_dimension()), 10, 0.0) > 0
+
+
+# ---- the long-list inputs of tests/test_gpu_self_join_lists.py -------------------------------------------------------------------
+
+def test_long_pair_lists_is_the_smallest_input_with_256_columns_past_one_block():
+    """The float64 cosine matrix itself shows 256 columns with more than 1024 + 64 true pairs (the nominees are a superset of
+    them: a lower bound on the lists similar_pairs walks), one row fewer shows 255, and no cosine lies within 1e-9 of the
+    threshold: the pair set is decided."""
+    x = R.long_pair_lists()
+    n, thr = R.LONG_PAIRS_N, R.LONG_PAIRS_THR
+    assert x.shape == (n, 3) and x.dtype == np.float32
+    sim = R.cosine_matrix_f64(x)
+    per_column = np.triu(sim >= thr, 1).sum(axis=0)
+    long_cols = np.nonzero(per_column > R.LONG_PAIRS_OVER)[0]
+    assert len(long_cols) == 256 and long_cols[-1] == n - 1 and long_cols[0] > 2600
+    assert np.abs(sim[np.triu_indices(n, 1)] - thr).min() > 1e-9
+    pairs, cos = R.pairs_from_sim(sim, thr)
+    assert len(pairs) == per_column.sum() > 1_700_000 and np.all(pairs[:, 0] < pairs[:, 1]) and np.all(cos >= thr)
+    assert np.array_equal(np.bincount(pairs[:, 1], minlength=n), per_column)
+    key = pairs[:, 0] * n + pairs[:, 1]
+    assert np.all(key[1:] > key[:-1])                                                  # ordered by (i, j), as the reference's loop
+    few = R.long_pair_lists(n=300)                                                     # pairs_from_sim is the oracle's double loop
+    from oracle import cpu_ref
+    p300, c300 = R.pairs_from_sim(R.cosine_matrix_f64(few), thr)
+    assert cpu_ref.similar_pairs_f64(few, thr) == list(zip(p300[:, 0].tolist(), p300[:, 1].tolist(), c300.tolist()))
+    led = R.long_pair_lists(lead=4097)                                                 # the same rows behind 4097 zero rows
+    assert led.shape == (4097 + n, 3) and not led[:4097].any() and np.array_equal(led[4097:], x)
+
+
+def _tight(which):
+    seed, m = which
+    x, at, marks = R.tight_cluster(seed, m, probe=R.TIGHT_PROBE if which == R.TIGHT_LARGE else 0.0)
+    return x, at, marks, R.cosine_matrix_f64(x)
+
+
+@pytest.mark.parametrize("which,top_k", [(w, k) for w in (R.TIGHT_SMALL, R.TIGHT_LARGE) for k in R.TIGHT_TOP_KS[w]],
+                         ids=lambda v: "m%d" % v[1] if isinstance(v, tuple) else "k%d" % v)
+def test_tight_cluster_keeps_every_list_long_and_every_answer_decided(which, top_k):
+    """What the GPU file relies on, from the oracle alone.  (1) Every in-cluster cosine exceeds 1 - eps / 2: a cluster row's
+    approximate score is then above 1 - 1.5 eps, and no threshold a_K - 2 eps can pass 1 - eps, so every cluster column's list
+    holds all m cluster rows to the end.  (2) The band excuses nothing for any (top_k, cutoff) used, and consecutive cosines of
+    every answer differ by more than 1e-14: a float64 cosine of 16 dimensions carries at most about a dozen roundings of
+    1.1e-16, the kernel's and the oracle's together under 3e-15 per pair, so a gap above 1e-14 cannot close — the order of the
+    ids is the oracle's.  (3) The cluster's indices reach into every chunk of rows."""
+    x, at, marks, sim = _tight(which)
+    m, n = which[1], which[1] + R.TIGHT_BACKGROUND
+    assert x.shape == (n, R.TIGHT_D) and len(at) == m and np.all(np.diff(at) > 0)
+    eps = R.pairs_eps(R.d_pad_of(R.TIGHT_D))
+    inside = R.cluster_cosines(sim, at)
+    assert inside.min() > 1.0 - eps / 2, 1.0 - inside.min()
+    for lo, hi in ((0, 512), (512, 768), (768, 2560), (n - 256, n)):                  # the chunk edges of top_k 10 and 256
+        assert np.count_nonzero((at >= lo) & (at < hi)) > (hi - lo) // 3
+    norms = np.linalg.norm(x[at].astype(np.float64), axis=1)
+    assert norms.min() < 0.3 and norms.max() > 4.0                                     # any scale: the kernel normalises
+    cutoffs = R.tight_cutoffs(sim, at)
+    assert cutoffs[:2] == (-1.0, 0.85) and inside.min() < cutoffs[2] < inside.max()
+    in_cluster = np.zeros(n, bool)
+    in_cluster[at] = True
+    for cutoff in cutoffs:
+        assert R.band_rows(sim, top_k, cutoff) == 0, (top_k, cutoff)
+        want = R.knn_from_sim(sim, top_k, cutoff)
+        assert R.min_gap_in_answers(want) > 1e-14, (top_k, cutoff)
+        ids, _, cnt = want
+        assert in_cluster[ids[at][ids[at] >= 0]].all()                                 # a cluster row's neighbours are cluster rows
+        if cutoff < 0.9:
+            assert np.all(cnt[at] == top_k)
+        elif top_k == 256:                                                             # the median cutoff thins: counts differ by row
+            assert 0 < np.count_nonzero(cnt[at] < top_k) < m and cnt[at].max() == top_k
+
+
+def test_tight_cluster_probe_row_has_the_whole_cluster_near_its_best_neighbour():
+    """The large input's probe column: its best neighbour's cosine is ~0.996, so with top_k = 1 its threshold settles 2 eps
+    under that — and nearly the whole cluster lies above: a list past 4096 entries while the column's own score of 1 stands
+    2 eps clear of every other.  (Expected, not proven: the count below leaves eps / 2 for the actual errors of the approximate
+    scores, which are a few 1e-4; a library whose select counts the own row returns no neighbour for this column.)"""
+    x, at, marks, sim = _tight(R.TIGHT_LARGE)
+    p, eps = marks["probe"], R.pairs_eps(R.d_pad_of(R.TIGHT_D))
+    assert p >= 0 and p not in at and abs(np.linalg.norm(x[p]) - 1.0) < 1e-6
+    others = np.delete(sim[p], p)
+    assert others.max() < 1.0 - 2.0 * eps - 1e-3
+    assert np.count_nonzero(others >= others.max() - 1.5 * eps) > 4096 + 64
+
+
+def test_thinned_input_has_a_zero_row_a_short_answer_and_rows_without_neighbours():
+    seed, m = R.TIGHT_SMALL
+    x, at, marks = R.tight_cluster(seed, m, zero_rows=1, group=4)
+    plain = R.tight_cluster(seed, m)[0]
+    changed = np.nonzero((x != plain).any(axis=1))[0]
+    assert set(changed) == set(marks["zeroed"]) | set(marks["group"][1:]) and marks["probe"] == -1
+    sim = R.cosine_matrix_f64(x)
+    assert R.band_rows(sim, 10, 0.85) == 0
+    ids, cos, cnt = R.knn_from_sim(sim, 10, 0.85)
+    assert R.min_gap_in_answers((ids, cos, cnt)) > 1e-14
+    assert not x[marks["zeroed"]].any() and np.all(cnt[marks["zeroed"]] == 0) and not np.isin(ids, marks["zeroed"]).any()
+    assert len(marks["group"]) == 5 and np.all(cnt[marks["group"]] == 4)             # fewer than top_k survivors
+    assert np.all(cnt[at] == 10) and np.count_nonzero(cnt == 0) > 600                 # most background rows: no neighbour at all
+
+
+def test_many_identical_copies_are_bit_identical_and_fill_more_than_a_buffer():
+    x, at = R.many_identical_copies()
+    assert x.shape == (1500, 8) and len(at) == 1300 > 1024 + 64 and np.all(np.diff(at) > 0)
+    assert all(np.array_equal(x[a], x[at[0]]) for a in at)
+    rest = np.setdiff1d(np.arange(1500), at)
+    assert not any(np.array_equal(x[r], x[at[0]]) for r in rest)
