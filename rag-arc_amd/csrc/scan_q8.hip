@@ -199,18 +199,19 @@ inline bool q8_tail_plan(uint32_t t_begin, uint32_t n_tiles, uint32_t g, uint32_
 inline uint32_t q8_tail_unit(int d_pad) { return d_pad <= 384 ? 4u : 2u; }
 
 // ABL (tools/scan_q8_bench): 1 = no pruning, 2 = no global loads after the prologue, 4 = no MFMA,
-// 8 = no threshold refresh, 16 = no conversion, 32768 = fp8: converted but not written to LDS, 32 = prune fast path only, 64 = never flush,
+// 8 = no threshold / histogram refresh (neither the loads nor their use), 16 = no conversion, 32768 = fp8: converted but not written to LDS, 32 = prune fast path only, 64 = never flush,
 // 256 = no ping-pong between the wave groups, 512 = barrier at the end of the iteration where EB would put it behind the matrix phase, 1024 = s_memtime timeline of workgroup 0 into p.dbg,
 // 131072 = fp8 / shadow form: only the first two k steps' A fragments are read from LDS (the MFMAs reuse them: what the other 7/8 of the ds_read_b128 cost),
 // 65536 = waves 4-7 issue no MFMAs (fp8 / shadow form: half the matrix work per CU, everything else unchanged — round 5's overlap question),
 // 262144 = plain row chunk loads (the policy before the non-temporal row stream; results are right),
+// 524288 = the tile's metadata pair is a constant (no load of it at all),
 // 16384 = every survivor updates the histogram, 4096 = survivors walked per lane (no LDS transposition), 8192 = parked scores walked at once (no batching), 2048 = fast path carries the position of the best score along (the earlier form; 0.5 % slower at 100M rows)
 //
 // Vector-memory discipline.  The prefetched tile registers are consumed with counted waits
 // ("all but the newest N operations have returned"), which the compiler derives per program path and
 // merges to the minimum over paths.  So (1) every iteration issues the SAME sequence of loads on every
-// path — tile chunks, tile scale, refreshed threshold, one histogram word — with out-of-range tiles
-// redirected to tile 0 instead of skipped; and (2) nothing else touches vector memory in the steady
+// path — tile chunks, tile scale and, once per loop unit, refreshed threshold and one histogram word — with out-of-range
+// tiles redirected to tile 0 instead of skipped; and (2) nothing else touches vector memory in the steady
 // state: survivors are staged in LDS and flushed (stores + histogram atomics) only now and then, the
 // owner publishes a threshold only when it rose.  An extra store in the queue would not break
 // anything, but the counted wait behind it would sit until that store is acknowledged — microseconds
@@ -320,7 +321,8 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
   const uint32_t* hword = p.hist + (size_t)own_q * RARC_NB + 32 * wave + row;
 
   // One "fetch group" per tile, identical on every path: the tile's chunks, its (scale, 1/scale)
-  // pair, this lane's refreshed threshold, one word of the owned query's histogram.  Everything in a
+  // pair, and in one group per loop unit this lane's refreshed threshold and one
+  // word of the owned query's histogram.  Everything on the vector path of a
   // group lands together (vector-memory returns are in order), two iterations after it was issued.
   struct Fetch {
     uint4 c[CPT];
@@ -336,8 +338,10 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
   // `refresh`: also re-read the lane's published threshold and the owner's histogram word.  With four fetch groups
   // (narrow rows) only one group in four does: at D = 384 the three small loads were half of a tile's vector-memory
   // instructions, and a CU issues one wave-instruction per ~45 cycles whatever its size (48 per tile = the tile period).
+  // With two groups, or one, it is once per loop unit as well (Q8_RF_FETCH at the loop).
   auto fetch = [&](Fetch& f, uint32_t tile, auto refresh) {
-    f.meta = *(const float2*)(p.tmeta + (size_t)tile * MSTRIDE);
+    if constexpr (ABL & 524288) f.meta = make_float2(__uint_as_float(0x7c003c00u), 1.0f);   // (ablation: scale 1, R_t = +inf, no load)
+    else f.meta = *(const float2*)(p.tmeta + (size_t)tile * MSTRIDE);
     if constexpr (FMT == 1) {
 #pragma unroll
       for (int j = 0; j < CPT; ++j)
@@ -433,7 +437,9 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
       // (narrow rows: the chain is short and the pruning reads the scores right behind a branch — a window with free
       //  instructions in it once the walk of tests/codeobj.py follows branches; the wide instantiations have the next tile's
       //  conversion between the last MFMA and the first read and are left as measured)
-      if constexpr (D <= 512) RARC_MFMA_SETTLE(c11);
+      // (D = 1024: a build of this kernel with fewer loads per tile had the pruning's first read one state short behind an
+      //  s_waitcnt in that window — tests/test_codeobj.py; the pad costs five cycles per tile)
+      if constexpr (D <= 512 || D > 768) RARC_MFMA_SETTLE(c11);
       // as the MFMAs leave them: elements 0-7 = the lane's scores of query block 0 (rows 16 (r >> 2) + 4 rq + (r & 3)), 8-15 = block 1
       return (i32x16){c00[0], c00[1], c00[2], c00[3], c10[0], c10[1], c10[2], c10[3],
                       c01[0], c01[1], c01[2], c01[3], c11[0], c11[1], c11[2], c11[3]};
@@ -721,8 +727,15 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
   if ((ABL & 1024) && blockIdx.x == 0 && it >= 1000 && it < 1016 && lane == 0)                                 \
     p.dbg[8 + ((it - 1000) * Q8_WAVES + wave) * 8 + (slot)] = __builtin_amdgcn_s_memtime();
 // G = the fetch group this iteration converts (tile cur + stride), GP = the one the previous iteration converted
-// RF(g): does fetch group g carry the threshold / histogram refresh (all of them unless NG == 4: then group 1 only)
-#define Q8_RF(g) (NG != 4 || (g) == 1)
+// Does fetch group g carry the threshold / histogram refresh?  Once per loop unit: group 1 of four or of two; with ONE group
+// the fetch issued in the odd half of the unrolled pair, which the even half consumes (the prologue's group refreshes and
+// is consumed by an even half too).  A published threshold that is a tile or two staler only weakens the pruning, and the
+// owner looks at s_hland every fourth tile, by when it has been rewritten twice.  (In the first 16 tiles of a launch the owner
+// looks on every tile and, with two groups or one, finds the histogram unchanged on every other one: it computes the same
+// threshold again and publishes nothing.)  (ABL 8 drops the loads as well as their use.)
+// RF_FETCH(g, par): the refill issued in an iteration of parity par re-reads them; RF_USE(g, par): the group consumed there has them
+#define Q8_RF_FETCH(g, par) (!(ABL & 8) && (NG == 1 ? (par) == 1 : (g) == 1))
+#define Q8_RF_USE(g, par) (!(ABL & 8) && (NG == 1 ? (par) == 0 : (g) == 1))
 #define Q8_ITER(PAR, GB, G, GP)                                                                               \
   {                                                                                                           \
     Q8_STAMP(0)                                                                                               \
@@ -732,7 +745,7 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
       acc = mfma_convert(PAR, f[G]);                                                                  \
       mcur[(PAR) ^ 1] = f[G].meta;                                                                    \
       Q8_STAMP(1)                                                                                             \
-      if (!(ABL & 8) && Q8_RF(G)) {                                                                           \
+      if (Q8_RF_USE(G, PAR)) {                                                                                \
         thr = fmaxf(thr, __uint_as_float(f[G].thr));                                                  \
         if (lane < 32) s_hland[32 * wave + lane] = f[G].hw;                                           \
       }                                                                                                       \
@@ -745,17 +758,17 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
       else if (q8_all16(acc) == 0x7fffffff) p.cnt2[0] = 1; /* keep ALL the MFMAs alive (M16: four accumulators) */ \
       Q8_STAMP(2)                                                                                             \
       /* refill that group with tile cur+3·stride */                                                          \
-      if (!(ABL & 2)) fetch(f[G], clamp_tile(cur + (NG + 1) * stride), Q8Flag<Q8_RF(G)>{});           \
+      if (!(ABL & 2)) fetch(f[G], clamp_tile(cur + (NG + 1) * stride), Q8Flag<Q8_RF_FETCH(G, PAR)>{});        \
     } else { /* ---- group B: prune(previous tile), refill the group consumed last iteration, then MFMA ---- */ \
       if (!(ABL & 1) && live_prev) prune(acc_b, cur - stride, mcur[(PAR) ^ 1].y, mcur[(PAR) ^ 1].x);          \
       live_prev = live;                                                                                       \
       Q8_STAMP(1)                                                                                             \
-      if (!(ABL & 2)) fetch(f[GP], clamp_tile(cur + NG * stride), Q8Flag<Q8_RF(GP)>{});                       \
+      if (!(ABL & 2)) fetch(f[GP], clamp_tile(cur + NG * stride), Q8Flag<Q8_RF_FETCH(GP, PAR)>{});            \
       __builtin_amdgcn_sched_barrier(0); /* the chunk loads must be ISSUED before the matrix phase */          \
       Q8_STAMP(2)                                                                                             \
       acc_b = mfma_convert(PAR, f[G]);                                                                        \
       mcur[(PAR) ^ 1] = f[G].meta;                                                                            \
-      if (!(ABL & 8) && Q8_RF(G)) {                                                                           \
+      if (Q8_RF_USE(G, PAR)) {                                                                                \
         thr = fmaxf(thr, __uint_as_float(f[G].thr));                                                          \
         if (lane < 32) s_hland[32 * wave + lane] = f[G].hw;                                                   \
       }                                                                                                       \
@@ -816,7 +829,8 @@ __global__ __launch_bounds__(Q8_THREADS) void rarc_scan_q8_kernel(const ScanQ8Pa
 #undef Q8_STEP
 #undef Q8_LOOP
 #undef Q8_ITER
-#undef Q8_RF
+#undef Q8_RF_FETCH
+#undef Q8_RF_USE
   // group B still owes the pruning of its last tile (the second half of the last pair: LDS buffer 1)
   if (grp_b && !(ABL & 1) && live_prev)
     prune(acc_b, t0 + (((t_end - 1 - t0) / stride) | (NG == 4 ? 3u : 1u)) * stride, mcur[1].y, mcur[1].x);
@@ -940,6 +954,11 @@ static int launch_scan_q8(const ScanQ8Params& p, int grid, hipStream_t s) {
     if (abl == 4) return launch_scan_q8<D, FMT, 4>(p, grid, s);
     if (abl == 5) return launch_scan_q8<D, FMT, 5>(p, grid, s);
     if (abl == 9) return launch_scan_q8<D, FMT, 9>(p, grid, s);
+    // what the loads of a tile that carry no row bytes cost (tools/q8_abl.sh ... 0 8 524288 524296): no threshold / histogram
+    // refresh, the tile's metadata pair a constant, both
+    if (abl == 8) return launch_scan_q8<D, FMT, 8>(p, grid, s);
+    if (abl == 524288) return launch_scan_q8<D, FMT, 524288>(p, grid, s);
+    if (abl == 524296) return launch_scan_q8<D, FMT, 524296>(p, grid, s);
     if constexpr (FMT == 1) {
       if (abl == 1024 || abl == 1025) {   // s_memtime timeline of workgroup 0, iterations 1000-1015 -> the file RARC_Q8_TIMELINE names
         static unsigned long long* d_dbg = nullptr;
